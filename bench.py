@@ -21,6 +21,11 @@ Metric (BASELINE.json): "aggregated edges/sec + training epochs/sec, full-graph 
   spmm_edges_per_s = E' / mean aggregation kernel time (HIP events on the launch stream)
   roofline         = algorithmic bytes of one aggregation launch / its mean duration vs 8 TB/s HBM
 
+A plain run sets up, warms up, times --steps steps and prints the line; `--full` adds, on one GPU, every secondary leg
+after the headline (yardstick, parity checks, CPU baseline, training-step-only and hipGraph timings and, for the GCN on
+workload L, the other graphs, sizes and shapes). `--dump-outputs DIR` writes what the last timed step computed as .npy
+files (dump_outputs).
+
 Launch: `python bench.py [--gpus 1]`; `python bench.py --gpus N` starts N ranks (one per GPU) as child
 processes under torch.distributed.run; the driver's own `python -m torch.distributed.run ... bench.py --gpus N`
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment) runs the ranks directly. The graph is then 1-D
@@ -624,6 +629,36 @@ def time_steps(step, steps, warmup, fence=None, tick=None, per_step=True):
     return total, last, per
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, last, model):
+    """--dump-outputs: what the last timed step handed back — the epoch's five numbers (train loss, val loss, val accuracy,
+    test loss, test accuracy; float64) — and what it left in the model: parameters after the optimizer step, their
+    gradients, the floating-point buffers (BatchNorm running statistics); float32. Should the arrays together exceed
+    DUMP_LIMIT_BYTES, every array above an equal share of it is cut to a fixed, seeded sample of its elements (file
+    `<name>.sample.npy`); with the same arguments every run writes the same names."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [("epoch_stats", np.asarray([float(v) for v in last], dtype=np.float64))]
+    grads = []
+    for name, p in model.named_parameters():
+        arrays.append((f"param.{name}", p.detach().float().cpu().numpy()))
+        if p.grad is not None:
+            grads.append((f"grad.{name}", p.grad.detach().float().cpu().numpy()))
+    arrays += grads
+    arrays += [(f"buffer.{name}", b.detach().float().cpu().numpy()) for name, b in model.named_buffers()
+               if b.is_floating_point()]
+    share = DUMP_LIMIT_BYTES // len(arrays) - 4096  # (4 KB per file for the .npy header)
+    over = sum(a.nbytes for _, a in arrays) > DUMP_LIMIT_BYTES - 4096 * len(arrays)
+    for name, a in arrays:
+        if over and a.nbytes > share:
+            keep = share // a.itemsize
+            idx = torch.randperm(a.size, generator=torch.Generator().manual_seed(1234572))[:keep].sort().values.numpy()
+            a, name = a.reshape(-1)[idx], f"{name}.sample"
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def median(v):
     v = sorted(v)
     n = len(v)
@@ -1005,8 +1040,15 @@ def main():
                     help="run ONLY the real-shape block (bench.real_shape_block) for one model on workload L's graph, "
                          "e.g. gcn:1433:7 — the command profiled under rocprofv3 for profiles/r05_real_shape_*")
     ap.add_argument("--primary-only", action="store_true",
-                    help="skip the secondary legs (hipGraph replay, configs[0]/[1] blocks, undirected run): clean "
-                         "rocprofv3 runs")
+                    help="with --full: skip the secondary legs (hipGraph replay, configs[0]/[1] blocks, undirected run): "
+                         "clean rocprofv3 runs")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the headline, also run every secondary leg (yardstick, parity checks, CPU baseline, "
+                         "training-step-only and hipGraph timings, the other graphs, sizes and shapes of workload L). Off: "
+                         "the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the epoch's five numbers, the "
+                         "parameters, buffers and gradients of the model) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1212,6 +1254,9 @@ def main():
         elapsed = t.item()
 
     hbm_peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9 if on_gpu else None  # structures + one epoch's tensors
+    if args.dump_outputs and rank == 0:
+        # before any secondary leg (--full) moves the weights further
+        dump_outputs(args.dump_outputs, last, getattr(runner, "model", model))
     trace, events = events, [r for r in events if not r[0].startswith("@")]  # "@issue" / "@wait": the emulated comm's marks
     by_kind, by_variant = {}, {}
     for k, s, e in events:
@@ -1432,10 +1477,10 @@ def main():
                                               {**by_kind, **by_variant}.items()
                                               if KERNEL_OF_KIND.get(k.split("[")[0]) == "spmm_linear_kernel"}
             return y
-        if kind in ("gcn", "mean", "sum"):
+        if kind in ("gcn", "mean", "sum") and args.full:
             secondary("yardstick", yardstick_leg)
 
-    if rank == 0 and parts == 1 and on_gpu and not args.no_cpu_baseline:
+    if rank == 0 and parts == 1 and on_gpu and args.full and not args.no_cpu_baseline:
         x_d, ei_d = step.device_inputs
 
         def fused_output():
@@ -1455,7 +1500,7 @@ def main():
         if args.model == "gcn" and args.workload in ("L", "S") and not args.primary_only:
             secondary("parity_gradients_at_S", lambda: gradient_parity_S(dev))
 
-    if parts == 1 and on_gpu and not args.primary_only:
+    if parts == 1 and on_gpu and args.full and not args.primary_only:
         # SURVEY 8d secondary: the training step without the two eval forwards (after the headline: it moves the
         # weights further, which the timed epochs above must not see)
         def train_only_leg():
@@ -1464,7 +1509,7 @@ def main():
                     "what": "train forward + backward + Adam, no eval forwards (itexperiments.py:427-440)"}
         secondary("train_step_only", train_only_leg)
         secondary("hip_graph_replay", lambda: time_graphed(step, args.steps, args.warmup))
-    if parts == 1 and on_gpu and args.workload == "L" and args.model == "gcn" and not args.primary_only:
+    if parts == 1 and on_gpu and args.full and args.workload == "L" and args.model == "gcn" and not args.primary_only:
         del step, model
         from rgb_experiment_amd.graph import clear_cache
         from rgb_experiment_amd.utils import to_undirected

@@ -259,3 +259,76 @@ def test_other_ranks_wait_for_rank_0_while_it_is_alive(tmp_path):
     t0 = time.monotonic()
     assert sv._await_rank0(d, 0, [ok], quiet_limit=30.0, hard_limit=0.4) is None
     assert time.monotonic() - t0 < 2.0
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: the last timed step's five numbers (the line's final losses among them) and the model it left
+    behind, as float32 / float64 .npy files; the same arguments give the same inputs, so two runs write the same arrays."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        proc = _run(["--gpus", "2", "--workload", "T", "--steps", "2", "--warmup", "1", "--exchange", "reshard",
+                     "--dump-outputs", str(d)])
+        assert proc.returncode == 0, proc.stderr[-3000:]
+        res = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0
+        arrays = {p.name[:-4]: np.load(p) for p in d.iterdir()}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 * 10**6
+        stats = arrays["epoch_stats"]
+        assert stats.dtype == np.float64 and stats.shape == (5,)
+        fl = res["final_losses"]
+        assert list(stats[[0, 1, 3]]) == [fl["train"], fl["val"], fl["test"]]
+        assert {"param.convs.0.lin.weight", "grad.convs.0.lin.weight", "buffer.bns.0.running_mean"} <= set(arrays)
+        dumps.append(arrays)
+    assert set(dumps[0]) == set(dumps[1])
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
+def test_dump_outputs_sample_what_would_exceed_the_limit(tmp_path, monkeypatch):
+    """Arrays that together exceed the limit: each one above an equal share is cut to a seeded sample of its elements,
+    the same positions every time; small arrays are written whole."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200_000)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(200, 300), torch.nn.BatchNorm1d(300))
+    model(torch.randn(8, 200)).sum().backward()
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / f"d{k}"), (1.0, 2.0, 0.5, 3.0, 0.25), model)
+    files = {p.name: p for p in (tmp_path / "d0").iterdir()}
+    assert sum(p.stat().st_size for p in files.values()) <= 200_000
+    assert "param.0.weight.sample.npy" in files and "grad.0.weight.sample.npy" in files
+    assert "param.0.bias.npy" in files and "buffer.1.running_var.npy" in files
+    w = model[0].weight.detach().numpy().reshape(-1)
+    got = np.load(files["param.0.weight.sample.npy"])
+    assert got.dtype == np.float32 and 0 < got.size < w.size and np.isin(got, w).all()
+    assert np.array_equal(got, np.load(tmp_path / "d1" / "param.0.weight.sample.npy"))
+    assert np.array_equal(np.load(files["epoch_stats.npy"]), [1.0, 2.0, 0.5, 3.0, 0.25])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_full_adds_the_secondary_legs(tmp_path):
+    """`bench.py --gpus 1` on the toy workload: the plain line has the headline and the timed steps' own figures and no
+    secondary leg; --full adds them after the same headline; --dump-outputs writes the last step's arrays."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RGBX_DIST_BACKEND"):
+        env.pop(k, None)
+    lines = {}
+    for mode in ("plain", "full"):
+        args = ["--gpus", "1", "--workload", "T", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / mode)]
+        proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + (["--full"] if mode == "full" else []),
+                              env=env, capture_output=True, text=True, timeout=300)
+        assert proc.returncode == 0, proc.stderr[-3000:]
+        res = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
+        assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+        assert res["unit"] == "edges/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+        stats = np.load(tmp_path / mode / "epoch_stats.npy")
+        assert list(stats[[0, 1, 3]]) == [res["final_losses"][k] for k in ("train", "val", "test")]
+        lines[mode] = res
+    legs = {"yardstick", "parity", "cpu_baseline", "train_step_only", "hip_graph_replay"}
+    assert not legs & set(lines["plain"])
+    assert legs <= set(lines["full"]), sorted(lines["full"])

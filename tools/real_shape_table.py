@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the real-shape block(s) of a bench.py line (`--real-shape` output or the default line's real_shape_same_run)."""
+"""Print the real-shape block(s) of a bench.py line (`--real-shape` output or the `--full` line's real_shape_same_run)."""
 import json
 import sys
 
