@@ -328,6 +328,37 @@ int rgbx_dagnn_gate_bwd_f32(const float* h0, int64_t ld0, const float* hops, int
                             int64_t ldd0, float* dk, int64_t d_stride, int64_t ldd, float* g_s, float* g_b,
                             void* ws, size_t ws_bytes, int64_t N, int64_t d, int K, rgbx_stream_t stream);
 
+/* ---- GGNN: one GatedGraphConv step (PyG GatedGraphConv, reference models/ggnn.py) ----------- */
+
+/* One propagation step on the state x [N, C] with the GRUCell's gates in the column order (r, z, n):
+ *   pre = (A x) Weffᵀ + x Wrootᵀ + bias   [N, 4C], columns [ r, z pre-activations (2C) | gi_n (C) | gh_n (C) ]
+ *   r = σ(pre_r), z = σ(pre_z), n = tanh(gi_n + r ⊙ gh_n),   out = (1 - z) ⊙ n + z ⊙ x
+ * A = the plain edge sum over the target-grouped CSR (rowptr, col), no weights. wt = Weffᵀ and wt_root = Wrootᵀ are
+ * [C, 4C] row-major, bias [4C], all on the device (Weff = [W_ih[r,z]; W_ih[n]; 0] weight[i]ᵀ,
+ * Wroot = [W_hh[r,z]; 0; W_hh[n]], bias = [b_ih[r,z] + b_hh[r,z]; b_ih[n]; b_hh[n]]).
+ * ONE kernel: the gather, both MFMA products and the GRU epilogue; only `out` is written, plus (training) the
+ * aggregate A x into z_out [N, C] and pre into pre_out [N, 4C] when they are not NULL.
+ * C % 8 == 0, 8 <= C <= 64 (rgbx_gru_step_supported); x, out, z_out, pre_out 16-byte aligned, leading dimensions % 4 == 0;
+ * out must not alias x. `split`: as rgbx_spmm_linear_f32 — split->partial must hold (n_chunks + n_long) * C floats. */
+int rgbx_gru_step_supported(int64_t C);
+int rgbx_gru_step_f32(const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx, const float* wt,
+                      const float* wt_root, const float* bias, float* out, int64_t ldo, float* z_out, int64_t ldz,
+                      float* pre_out, int64_t ldp, int64_t N, int64_t C, const rgbx_row_split_t* split,
+                      rgbx_stream_t stream);
+
+/* The GRU cell alone over a finished pre [N, 4C] (ldp) as rgbx_gru_step_f32 lays it out: out [N, C] = the new state
+ * for the old state x. C % 4 == 0; every matrix 16-byte aligned with leading dimension % 4 == 0. */
+int rgbx_gru_gate_fwd_f32(const float* pre, int64_t ldp, const float* x, int64_t ldx, float* out, int64_t ldo,
+                          int64_t N, int64_t C, rgbx_stream_t stream);
+
+/* Backward of the cell for gout = dL/dout [N, C]:
+ *   dpre [N, 4C] = [ dr ⊙ r(1-r) | dz ⊙ z(1-z) | dgi_n | dgi_n ⊙ r ],  dgi_n = gout (1 - z)(1 - n²), dr = dgi_n ⊙ gh_n,
+ *   dz = gout ⊙ (x - n);   dx [N, C] = gout ⊙ z (the direct part of the state's gradient; the parts through A and
+ *   Wroot are the caller's products). Same shape rules as rgbx_gru_gate_fwd_f32. */
+int rgbx_gru_gate_bwd_f32(const float* pre, int64_t ldp, const float* x, int64_t ldx, const float* gout, int64_t ldg,
+                          float* dpre, int64_t lddp, float* dx, int64_t lddx, int64_t N, int64_t C,
+                          rgbx_stream_t stream);
+
 /* ---- GAT: fused score + edge-softmax + aggregate ------------------------------------------ */
 
 /* a_src[n,h] = <hfeat[n,h,:], att_src[h,:]>, a_dst likewise; hfeat is [n, H*C] (ld = ldh). */

@@ -8,7 +8,7 @@ class InitialParameters:
     default_data_path = os.environ.get("RGB_DATA_ROOT", os.path.join(os.path.dirname(_PKG), "data"))
     default_pics_path = os.path.join(os.path.dirname(_PKG), "pics")
 
-    model_names = ["MLP", "GCN", "GraphSAGE", "GAT", "APPNPStack", "GraphSAGE2", "PTA", "DAGNN", "SGC", "GIN"]
+    model_names = ["MLP", "GCN", "GraphSAGE", "GAT", "APPNPStack", "GraphSAGE2", "PTA", "DAGNN", "SGC", "GIN", "GGNN"]
     # reference initial_params.py:24-35
     default_init_params = [
         {"num_layers": 3, "hidden_unit": 64, "dropout_rate": 0.5},
@@ -21,6 +21,7 @@ class InitialParameters:
         {"hidden_dim": 64, "K": 10, "dropout_rate": 0.5},
         {"K": 2},
         {"num_layers": 2, "hidden_unit": 64, "dropout_rate": 0.5},
+        {"num_layers": 2, "hidden_unit": 64, "dropout_rate": 0.5},  # GGNN, reference initial_params.py:28
     ]
 
     # reference initial_params.py:42

@@ -6,7 +6,7 @@ Scope: data loading / mask remake / feature normalisation / 
 lower-cased ``model_name`` / full-batch Adam + NLLLoss loop with early stopping / the PTA branch
 (label propagation + soft-label loss + propagated inference, reference :351-374, :422-462) / metrics
 dict / Correct & Smooth post-processing (reference :514-534). Out of scope and rejected with
-``NotImplementedError``: plots, PCA (reference :536-601) and the GGNN / SuperGAT / FAGCN zoo members.
+``NotImplementedError``: plots, PCA (reference :536-601) and the SuperGAT / FAGCN zoo members.
 
 Deliberate deviations from reference quirks:
   * ``compare_pred_label(need_all_metrics=False)`` returns zeros instead of raising
@@ -29,11 +29,11 @@ from torch import Tensor
 from . import ops
 from .data import Data
 from .initial_params import InitialParameters
-from .models import REGISTRY
+from .models import MODELS
 from .rd2pd import RD2PD
 from .utils import get_classification_mask, get_random_mask, get_whole_mask, to_undirected
 
-_OUT_OF_SCOPE = ("ggnn", "supergat", "fagcn")
+_OUT_OF_SCOPE = ("supergat", "fagcn")
 
 
 def _macro_prf(label, pred):
@@ -257,8 +257,8 @@ def experiment(model_init_param: dict, *,
     name = model_name.lower()
     if name in _OUT_OF_SCOPE:
         raise NotImplementedError(f"model_name={model_name!r} is outside the MI355X hot-path scope "
-                                  f"(supported: {sorted(REGISTRY)})")
-    if name not in REGISTRY:
+                                  f"(supported: {sorted(MODELS)})")
+    if name not in MODELS:
         raise ValueError(f"unknown model_name {model_name!r}")
     if print_pics or vis_feat:
         raise NotImplementedError("print_pics / vis_feat are reporting features outside the hot-path scope")
@@ -332,10 +332,10 @@ def experiment(model_init_param: dict, *,
         idx = [m.nonzero(as_tuple=True)[0] for m in (train_mask, val_mask, test_mask)]
         K, alpha = model_init_param["K"], model_init_param["alpha"]
         y_soft = [label_propagation(adj, y, i, K, alpha) for i in idx]
-        net = REGISTRY[name](nfeat=input_dim, nclass=output_dim, **model_init_param)
+        net = MODELS[name](nfeat=input_dim, nclass=output_dim, **model_init_param)
         fwd = {"x": features}
     else:
-        net = REGISTRY[name](input_dim=input_dim, output_dim=output_dim, **model_init_param)
+        net = MODELS[name](input_dim=input_dim, output_dim=output_dim, **model_init_param)
         fwd = {"x": features} if name == "mlp" else {"x": features, "edge_index": data.edge_index}
     net.to(device)
     if cache_input_aggregate == "auto":  # memory guard: the kept aggregate is one more [N, F] fp32 matrix in HBM

@@ -6,6 +6,7 @@ computing their ``propagate`` in HIP kernels (rgb_experiment_amd.ops).
   MySAGEConv <- my_SAGEConv                       (reference models/graphsage.py:36-62)
   GATConv    <- torch_geometric.nn.conv.GATConv   (reference models/gat.py:3,18-21)
   APPNP      <- torch_geometric.nn.conv.APPNP     (reference models/appnp_stack.py:3,22)
+  GatedGraphConv <- torch_geometric.nn.GatedGraphConv (reference models/ggnn.py:3,18)
 
 Dense X·W^T products go through hipBLASLt (forward, input gradient) and rgbx_gemm_tn_f32 (weight
 gradient, split-K fp32 MFMA); everything indexed by edge_index goes through librgbx_hip.so.
@@ -15,7 +16,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
 from ..graph import LOOPS_ADD_REMAINING, LOOPS_KEEP, LOOPS_REMOVE_ADD, get_graph
 
 
@@ -564,3 +565,49 @@ class GINConv(nn.Module):
                 h = layer(h)
             return h
         return self.nn(ops.propagate_sum(x, graph) + (1 + self.eps) * x)
+
+
+class GatedGraphConv(nn.Module):
+    """Gated graph convolution: the input (zero-padded to out_channels columns; wider inputs raise) runs through
+    num_layers steps of m = x weight[i], agg_i = sum_{j -> i} m_j (edges as given, duplicates counted, no loops added,
+    no normalisation), x = GRUCell(agg, x) [PyG GatedGraphConv(out_channels, num_layers, aggr='add', bias=True), as
+    built at reference models/ggnn.py:18; parameter names weight, rnn.weight_ih / weight_hh / bias_ih / bias_hh, so a
+    reference state_dict loads with strict=True]. Parity with PyG itself is not pinned (PyG is not available to the
+    tests): the spec is the restatement in ops.gru_operands / csrc/gru.hip, checked against a float64 copy of it.
+    Every step is one HIP launch where the fused kernel takes the width (ops.gru_step_supported), else the general form;
+    state widths that are no multiple of 4 run on zero-padded state and weights, sliced off at the end."""
+
+    def __init__(self, out_channels, num_layers, aggr="add", bias=True):
+        super().__init__()
+        if aggr != "add":
+            raise NotImplementedError(f"GatedGraphConv: only aggr='add' (the reference's) is implemented, got {aggr!r}")
+        self.out_channels, self.num_layers, self.aggr = out_channels, num_layers, aggr
+        self.weight = nn.Parameter(torch.empty(num_layers, out_channels, out_channels))
+        self.rnn = nn.GRUCell(out_channels, out_channels, bias=bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.out_channels)  # PyG's uniform(size, tensor)
+        with torch.no_grad():
+            self.weight.uniform_(-bound, bound)
+        self.rnn.reset_parameters()
+
+    def forward(self, x, edge_index):
+        C = self.out_channels
+        if x.size(-1) > C:
+            raise ValueError(f"GatedGraphConv: the number of input channels ({x.size(-1)}) must not exceed "
+                             f"out_channels ({C})")
+        if not x.is_cuda:
+            _lib.require_device(x)
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        Cp = (C + 3) // 4 * 4
+        if x.size(-1) < Cp:  # PyG's zero columns up to C, and the pad columns up to Cp in the same copy
+            x = torch.nn.functional.pad(x, (0, Cp - x.size(-1)))
+        rnn = self.rnn
+        for i in range(self.num_layers):
+            weff, wroot, b = ops.gru_operands(self.weight[i], rnn.weight_ih, rnn.weight_hh, rnn.bias_ih, rnn.bias_hh, Cp)
+            x = ops.gru_step(x, graph, weff, wroot, b)
+        return x if Cp == C else x[:, :C]
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.out_channels}, num_layers={self.num_layers})"

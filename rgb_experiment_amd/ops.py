@@ -1172,6 +1172,161 @@ def dagnn_prop(x, graph, K, proj_weight, proj_bias=None):
     return out if xp is x else out[:, :d]
 
 
+# ---- GGNN: one GatedGraphConv step (csrc/gru.hip) -----------------------------------------------------------------
+
+GRU_FORMS = ("fused", "composed", "general")
+# None = the default choice (gru_step_form): the fused step wherever it applies, else the general form. The A/B tool
+# (tools/ggnn_bench.py) sets a form explicitly.
+GRU_FORM = None
+
+
+def gru_step_supported(C):
+    """The fused step (rgbx_gru_step_f32) takes state width C (a multiple of 4): 4 C a multiple of 32 and <= 256."""
+    return bool(_lib.load().rgbx_gru_step_supported(int(C)))
+
+
+def gru_step_form(C, form=None):
+    form = form or GRU_FORM
+    if form is None:
+        return "fused" if gru_step_supported(C) else "general"
+    if form not in GRU_FORMS:
+        raise ValueError(f"unknown GRU step form {form!r} (one of {GRU_FORMS})")
+    if form != "general" and not gru_step_supported(C):
+        raise RuntimeError(f"the {form} GRU step needs 4 C a multiple of 32 and at most 256 (C = {C}); use 'general'")
+    return form
+
+
+def gru_operands(weight_i, w_ih, w_hh, b_ih, b_hh, Cp):
+    """(Weff [4Cp, Cp], Wroot [4Cp, Cp], bias [4Cp]) of one step at padded width Cp >= C, from the step's weight [C, C]
+    and the GRUCell's parameters (gates r, z, n): pre = (A x) Weffᵀ + x Wrootᵀ + bias has the columns
+    [r, z pre-activations | gi_n | gh_n], each block Cp wide (pad rows and columns zero: a zero pad column of the state
+    stays zero). Differentiable torch ops on the parameters: autograd carries dWeff back to W_ih and weight_i."""
+    C = weight_i.size(0)
+    p = Cp - C
+    pad = torch.nn.functional.pad
+    wi = (w_ih @ weight_i.t()).view(3, C, C)  # (A x) weight_i W_ihᵀ = (A x) (W_ih weight_iᵀ)ᵀ
+    wh = w_hh.view(3, C, C)
+    if p:
+        wi, wh = pad(wi, (0, p, 0, p)), pad(wh, (0, p, 0, p))
+    zero = wi.new_zeros(Cp, Cp)
+    weff = torch.cat([wi[0], wi[1], wi[2], zero], 0)
+    wroot = torch.cat([wh[0], wh[1], zero, wh[2]], 0)
+    if b_ih is None:
+        bias = wi.new_zeros(4 * Cp)
+    else:
+        bi, bh = b_ih.view(3, C), b_hh.view(3, C)
+        if p:
+            bi, bh = pad(bi, (0, p)), pad(bh, (0, p))
+        bias = torch.cat([bi[0] + bh[0], bi[1] + bh[1], bi[2], bh[2]], 0)
+    return weff, wroot, bias
+
+
+def gru_gate_fwd(pre, x, out=None):
+    """The GRU cell over a finished pre [N, 4C] (rgbx_gru_gate_fwd_f32): the new state [N, C]."""
+    _lib.require_device(pre, x)
+    N, C = x.shape
+    if out is None:
+        out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    pp, ldp = _lib.mat(pre, "pre")
+    px, ldx = _lib.mat(x, "x")
+    po, ldo = _lib.mat(out, "out")
+    with _Timed("gru_gate_fwd", f"d{C}" if _EVENT_SINK is not None else None):
+        _lib.check(_lib.load().rgbx_gru_gate_fwd_f32(pp, ldp, px, ldx, po, ldo, N, C, _lib.stream_ptr()),
+                   "rgbx_gru_gate_fwd_f32")
+    return out
+
+
+def gru_gate_bwd(pre, x, gout):
+    """(dpre [N, 4C], dx_direct [N, C] = gout ⊙ z) of the GRU cell (rgbx_gru_gate_bwd_f32)."""
+    _lib.require_device(pre, x, gout)
+    N, C = x.shape
+    dpre = torch.empty((N, 4 * C), dtype=torch.float32, device=x.device)
+    dx = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    pp, ldp = _lib.mat(pre, "pre")
+    px, ldx = _lib.mat(x, "x")
+    pg, ldg = _lib.mat(gout, "gout")
+    with _Timed("gru_gate_bwd", f"d{C}" if _EVENT_SINK is not None else None):
+        _lib.check(_lib.load().rgbx_gru_gate_bwd_f32(pp, ldp, px, ldx, pg, ldg, dpre.data_ptr(), 4 * C, dx.data_ptr(), C,
+                                                     N, C, _lib.stream_ptr()), "rgbx_gru_gate_bwd_f32")
+    return dpre, dx
+
+
+def gru_step_raw(x, graph, weff, wroot, bias, form, want_saved=False):
+    """One step without autograd: returns (x', z = A x or None, pre or None); z and pre only when `want_saved`.
+    fused: rgbx_gru_step_f32 (gather, both products and the cell in one kernel). composed: the fused aggregate +
+    transform kernel writes pre (rgbx_spmm_linear_f32 with the root term), the gate kernel follows. general: the sum
+    aggregation at width C (rgbx_spmm_csr_f32), pre by two dense products, the gate kernel."""
+    _lib.require_device(x, weff, wroot, bias)
+    N, C = x.shape
+    dev = x.device
+    b = bias.detach().contiguous()
+    if form == "fused":
+        out = torch.empty((N, C), dtype=torch.float32, device=dev)
+        z = torch.empty((N, C), dtype=torch.float32, device=dev) if want_saved else None
+        pre = torch.empty((N, 4 * C), dtype=torch.float32, device=dev) if want_saved else None
+        wt, wtr = weff.detach().t().contiguous(), wroot.detach().t().contiguous()
+        px, ldx = _lib.mat(x, "x")
+        split, _scratch = graph.fwd.split_arg(C, dev, hub_rows=True)
+        with _Timed("gru_step_fwd", f"d{C}{'+z+pre' if want_saved else ''}" if _EVENT_SINK is not None else None):
+            _lib.check(_lib.load().rgbx_gru_step_f32(
+                _lib.ptr(graph.fwd.rowptr), _lib.ptr(graph.fwd.col), px, ldx, _lib.ptr(wt), _lib.ptr(wtr), _lib.ptr(b),
+                _lib.ptr(out), C, _lib.ptr(z), C, _lib.ptr(pre), 4 * C, N, C,
+                None if split is None else ctypes.byref(split), _lib.stream_ptr()), "rgbx_gru_step_f32")
+        return out, z, pre
+    if form == "composed":
+        pre, z = spmm_linear_raw(graph.fwd, None, None, x, weff.detach().t().contiguous(), b, want_saved, x,
+                                 wroot.detach().t().contiguous(), kind="gru_linear_fwd")
+    elif form == "general":
+        z = spmm_raw(graph.fwd, None, None, x, kind="sum_fwd")
+        pre = torch.addmm(b, z, weff.detach().t())
+        pre.addmm_(x, wroot.detach().t())
+    else:
+        raise ValueError(form)
+    return gru_gate_fwd(pre, x), z, pre
+
+
+class _GRUStep(torch.autograd.Function):
+    """x' = GRU cell of pre = (A x) Weffᵀ + x Wrootᵀ + bias (see gru_operands). Backward: dpre and the direct part
+    dx' ⊙ z from the gate backward kernel; dWeff = dpreᵀ (A x) and dbias = column sums of dpre in one pass of the split-K
+    MFMA kernel, dWroot = dpreᵀ x; dx = Aᵀ(dpre Weff) + dpre Wroot + dx' ⊙ z with the transposed gather at width C."""
+
+    @staticmethod
+    def forward(ctx, x, graph, weff, wroot, bias, form):
+        x = x.contiguous()
+        want = any(ctx.needs_input_grad)
+        out, z, pre = gru_step_raw(x, graph, weff, wroot, bias, form, want_saved=want)
+        if want:
+            ctx.save_for_backward(x, z, pre, weff, wroot)
+            ctx.graph = graph
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, z, pre, weff, wroot = ctx.saved_tensors
+        dpre, dxd = gru_gate_bwd(pre, x, gout.contiguous())
+        gw = gb = gwr = gx = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[4]:
+            gw, gb = gemm_tn(dpre, z, colsum=True)  # dpre is read once for dWeff and dbias
+        if ctx.needs_input_grad[3]:
+            gwr = gemm_tn(dpre, x)
+        if ctx.needs_input_grad[0]:
+            g1 = dpre @ weff.detach()
+            g2 = torch.addmm(dxd, dpre, wroot.detach())
+            gx = spmm_raw(ctx.graph.bwd, None, None, g1, y=g2, a=1.0, b=1.0, out=g2, kind="sum_bwd")
+        return gx, None, gw, gwr, gb, None
+
+
+def gru_step(x, graph, weff, wroot, bias, form=None):
+    """One GatedGraphConv step on the state x [N, Cp] (Cp % 4 == 0, single-GPU graph); operands from gru_operands.
+    `form`: one of GRU_FORMS, None = gru_step_form's default."""
+    if _is_dist(graph):
+        raise RuntimeError("GatedGraphConv has no node-partitioned form: run it on one GPU")
+    C = x.size(1)
+    if C % 4:
+        raise RuntimeError(f"gru_step: the state width must be a multiple of 4 (got {C}); pad it (GatedGraphConv does)")
+    return _GRUStep.apply(x, graph, weff, wroot, bias, gru_step_form(C, form))
+
+
 class _GATScores(torch.autograd.Function):
     """a_src[n,h] = <hfeat[n,h,:], att_src[h,:]> and a_dst likewise (GATConv.forward [PyG])."""
 
