@@ -226,6 +226,20 @@ typedef struct rgbx_ce_epilogue {
    * for statistics set 0 / set 1 — stats[0:3] and stats[3:6] — so that ONE eval forward serves the val and the test
    * metrics of an epoch (itexperiments.py:464-473 runs two identical forwards for them). */
   int32_t mask_groups;
+  /* Selected rows only (single-GPU callers; all zero = every row as before). A row is SELECTED when its mask bit(s) are
+   * set (any of the two with mask_groups == 2) AND its label lies in [0, C): the epilogue's own predicate, which the
+   * row list and rgbx_fused_layer_t.col_sel of the backward must restate exactly.
+   *   rows / n_rows: statistics only (grad_scale == NULL, no z_out), an aggregating launch of rgbx_spmm_linear_f32 /
+   *     rgbx_fused_layer_f32: the ascending int32 device list of the selected rows (with mask_groups == 2 those of the
+   *     union of both masks). Tile t aggregates rows[32 t .. 32 t + 31]; ceil(n_rows / 32) tiles, records and workgroups
+   *     instead of ceil(N / 32); unlisted rows are not gathered at all. Statistics as without the list (the nll sum up to
+   *     the order of its fp64 additions). Hub rows of `split` keep working for listed rows.
+   *   skip_unselected != 0: the tiles map to rows as without a list, but a row that is not selected issues no gather;
+   *     its z_out row is written as 0 (pre_* not applied), its `out` row (loss gradient) is 0 as always. The gradient,
+   *     the statistics and dW = dy^T z are unchanged (the gradient row is 0 there). Not with w_pos (ignored). */
+  const int32_t* rows;
+  int64_t n_rows;
+  int32_t skip_unselected;
 } rgbx_ce_epilogue_t;
 
 int rgbx_spmm_linear_supported(int64_t K, int64_t Nout, int has_root);
@@ -289,6 +303,14 @@ typedef struct rgbx_fused_layer {
    * no rs / pre_* / out_blk; with `split`, split->partial must hold n_chunks * K + 2 * n_long * K floats. */
   const float* w_pos;
   float* z_pos_out;
+  /* Column selection (optional, NULL = every slot gathered): a slot whose column c has col_sel[c] == 0 issues no gather
+   * and adds 0, exactly as a slot whose gathered row is 0 would (per-slot weights >= 0, e.g. gcn_norm / mean). For the
+   * transposed launch of a last layer whose output gradient is 0 outside the rows its loss selects (rgbx_ce_epilogue_t:
+   * mask bit AND a label in [0, C)): those rows are not read, and every slot keeps its place in the summation, so the
+   * result is bit-identical to the full gather. An aggregating launch without ce / w_pos / blocked layouts; col_sel must
+   * have an entry for every column of the CSR. Honoured for K in {64, 128, 256} and Nout <= 128 without blocked layouts;
+   * elsewhere, and for the hub rows of `split`, every slot is gathered (the same result). */
+  const uint8_t* col_sel;
 } rgbx_fused_layer_t;
 
 int rgbx_fused_layer_f32(const rgbx_fused_layer_t* layer, rgbx_stream_t stream);

@@ -28,7 +28,8 @@ class RowSplit(ctypes.Structure):
 class CeEpilogue(ctypes.Structure):
     """rgbx_ce_epilogue_t"""
     _fields_ = [("y", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("grad_scale", ctypes.c_void_p),
-                ("stats", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("mask_groups", ctypes.c_int32)]
+                ("stats", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("mask_groups", ctypes.c_int32),
+                ("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int64), ("skip_unselected", ctypes.c_int32)]
 
 
 class SpmmEpilogue(ctypes.Structure):
@@ -45,7 +46,7 @@ class FusedLayer(ctypes.Structure):
                 ("ldo", _I64), ("out_blk", _P), ("ob_cols", _I64), ("ob_stride", _I64), ("z_out", _P), ("ldz", _I64),
                 ("pre_scale", _P), ("pre_shift", _P), ("pre_rowsum", _P), ("out_colsums", _P), ("stats_ws", _P),
                 ("stats_ws_bytes", ctypes.c_size_t), ("ce", _P), ("N", _I64), ("K", _I64), ("Nout", _I64),
-                ("split", _P), ("w_pos", _P), ("z_pos_out", _P)]
+                ("split", _P), ("w_pos", _P), ("z_pos_out", _P), ("col_sel", _P)]
 
 
 # name -> argtypes, exactly the declarations of include/rgbx_hip.h

@@ -633,6 +633,8 @@ extern "C" int rgbx_spmm_csr_epilogue_f32(const int32_t* rowptr, const int32_t* 
       return fail(RGBX_E_ARG, "spmm_epilogue: mask_groups must be 0, 1 or 2 (got %d)", (int)ce->mask_groups);
     if (ce->mask_groups == 2 && (ce->grad_scale || !ce->mask))
       return fail(RGBX_E_ARG, "spmm_epilogue: two statistics sets (mask_groups == 2) need a mask and no loss gradient");
+    if (ce->rows || ce->n_rows || ce->skip_unselected)
+      return fail(RGBX_E_ARG, "spmm_epilogue: rows / skip_unselected are for rgbx_spmm_linear_f32 (this gather skips unselected rows itself)");
     if (epi->n_classes < 0 || epi->n_classes > d) return fail(RGBX_E_ARG, "spmm_epilogue: n_classes must lie in [0, d]");
     if (epi->n_classes > 0) C = (int)epi->n_classes;
   }

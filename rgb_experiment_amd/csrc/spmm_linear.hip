@@ -85,6 +85,14 @@ struct FusedArgs {
   const float* w2;
   float* zpos_out;
   const float* zlong_pos;
+  // loss epilogue over selected rows only (rgbx_ce_epilogue_t.rows / skip_unselected; single-GPU callers):
+  // ce_rows: tile t aggregates rows ce_rows[32 t .. 32 t + 31] of an ascending list of ce_n_rows selected rows (statistics
+  // only); ce_skip: a row the epilogue does not select issues no gather, its aggregate (zt, z_out) is 0
+  const int* ce_rows;
+  int ce_n_rows;
+  int ce_skip;
+  // column selection (rgbx_fused_layer_t.col_sel): a slot whose column is not selected is not gathered and adds 0
+  const uint8_t* col_sel;
 };
 
 __device__ __forceinline__ const float* blocked_at(const float* base, int64_t bc, int64_t bs, int64_t ld, int row,
@@ -253,6 +261,36 @@ tile_stats_finish_kernel(const double* __restrict__ part2, int G, int width2, do
 }
 
 
+// The loss epilogue's row selection: the row's mask bit(s) AND a label in [0, Nout) (labels outside deselect a row, as in
+// rgbx_masked_ce_fwd_f32). ONE predicate for everything that selects rows: the epilogue's statistics and gradient, the
+// in-place gather skip of phase 1 (ce_skip), and — restated on the host from the same two tensors — the row list of the
+// statistics-only form and the column selection of the backward's transposed gather (ops.ce_selection, col_sel). Returns the selecting mask
+// bits (bit 0 / bit 1 = statistics set 0 / 1) and the label in *t, or 0 and *t = -1.
+__device__ __forceinline__ int ce_select(const FusedArgs& A, int row, int* t) {
+  int bits = A.ce_mask ? (int)A.ce_mask[row] : 1;
+  bits = A.ce_groups == 2 ? (bits & 3) : (bits ? 1 : 0);
+  *t = -1;
+  if (bits) {
+    const int64_t ti = A.ce_y[row];
+    if (ti >= 0 && ti < A.Nout) *t = (int)ti;
+  }
+  return *t >= 0 ? bits : 0;
+}
+
+// Row of slot r of the workgroup's tile: row_base + r, or with a row list (loss epilogue, statistics only) entry
+// row_base + r of it; A.N (= no row) past the end of the list or for an entry outside [0, N)
+template <bool CE>
+__device__ __forceinline__ int tile_row(const FusedArgs& A, int row_base, int r) {
+  if constexpr (CE) {
+    if (A.ce_rows) {
+      const int i = row_base + r;
+      const int row = i < A.ce_n_rows ? A.ce_rows[i] : A.N;
+      return (unsigned)row < (unsigned)A.N ? row : A.N;
+    }
+  }
+  return row_base + r;
+}
+
 // Cross-entropy of the finished 32 x Nout tile (Nout <= 128), see FusedArgs::ce_part. The four waves park their 32 x 32
 // blocks in LDS (the aggregate tile is dead by now), then each wave takes 8 rows: a lane holds columns lane and
 // lane + 64, max / first arg-max / sum-exp go through the wave with shuffles. NLLLoss(log_softmax(z))_i = lse_i - z[i, y_i]
@@ -277,15 +315,10 @@ __device__ __forceinline__ void ce_epilogue(const FusedArgs& A, const f32x16& ac
   const bool c0 = lane < A.Nout, c1 = lane + 64 < A.Nout;
   for (int rr = 0; rr < TM / 4; ++rr) {
     const int rl = wave * (TM / 4) + rr;
-    const int row = row_base + rl;
-    if (row >= A.N) break;  // wave-uniform
-    int t = -1;
-    int bits = A.ce_mask ? (int)A.ce_mask[row] : 1;
-    bits = A.ce_groups == 2 ? (bits & 3) : (bits ? 1 : 0);
-    if (bits) {
-      const int64_t ti = A.ce_y[row];
-      if (ti >= 0 && ti < A.Nout) t = (int)ti;
-    }
+    const int row = tile_row<true>(A, row_base, rl);
+    if (row >= A.N) break;  // wave-uniform (a row list's invalid slots are its tail)
+    int t;
+    const int bits = ce_select(A, row, &t);  // the one selection predicate (see ce_select)
     if (t < 0 && !A.ce_scale) continue;  // not selected, nothing to store: wave-uniform
     const float v0 = c0 ? ot[rl * ldq + lane] : -INFINITY;
     const float v1 = c1 ? ot[rl * ldq + lane + 64] : -INFINITY;
@@ -385,7 +418,10 @@ ce_tiles_finish_kernel(const double* __restrict__ part2, int n, double* __restri
 // POS: every gathered row is also accumulated under the second weight vector A.w2 into A.zpos_out (single-head GAT's
 // training forward: the part of the aggregate carried by edges with a positive score, see gat.hip). One more
 // accumulator per lane: 7 waves per SIMD instead of 8.
-template <int G, bool HAS_W, int KC, int NT, bool CE = false, bool DENSE = false, bool BLK = false, bool POS = false>
+// SEL: slots whose column is not selected are not gathered (FusedArgs::col_sel); its own instantiation, so that the
+// plain kernel's scalar registers are what they were.
+template <int G, bool HAS_W, int KC, int NT, bool CE = false, bool DENSE = false, bool BLK = false, bool POS = false,
+          bool SEL = false>
 __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_kernel(const FusedArgs A) {
   constexpr int NG = kWave / G;
   constexpr int U = 4;
@@ -429,10 +465,19 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
     if (lane == 0) lr = atomicAdd(&next_row, 1);
     lr = __builtin_amdgcn_readfirstlane(lr);
     if (lr >= TM) break;
-    const int row = row_base + lr;
+    const int row = tile_row<CE>(A, row_base, lr);
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     float accp[4] = {0.f, 0.f, 0.f, 0.f};  // POS only
-    if (row < A.N) {
+    // a row the loss epilogue does not select (the one predicate, ce_select) is not gathered: its aggregate is 0 — also
+    // in z_out, where the pre-affine map would otherwise put pre_shift * rowsum — and its loss gradient 0 either way
+    bool skip = false;
+    if constexpr (CE && !POS) {
+      if (A.ce_skip && row < A.N) {
+        int t;
+        skip = ce_select(A, row, &t) == 0;  // wave-uniform
+      }
+    }
+    if (row < A.N && !skip) {
       const int start = __builtin_amdgcn_readfirstlane(A.rowptr[row]);
       const int end = __builtin_amdgcn_readfirstlane(A.rowptr[row + 1]);
       if (A.threshold > 0 && end - start > A.threshold) {
@@ -458,6 +503,10 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
             mycol = A.col[base + lane];
             if constexpr (HAS_W) myw = A.w[base + lane];
             if constexpr (POS) mywp = A.w2[base + lane];
+            // a column the loss does not select (the ce_select predicate, restated by ops.ce_selection) has a zero row:
+            // not gathered, the slot adds fmaf(0, 0, acc) = acc + 0 where the full gather adds fmaf(w >= 0, +0, acc) —
+            // same place in the sum, same bits
+            if constexpr (SEL) { if (!A.col_sel[mycol]) mycol = -1; }
           }
           for (int k = 0; k < n; k += NG * U) {
             float v[U][4];
@@ -469,7 +518,7 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
               const int src = __shfl(mycol, idx & 63);
               if constexpr (HAS_W) ww[u] = __shfl(myw, idx & 63);
               if constexpr (POS) wp[u] = __shfl(mywp, idx & 63);
-              const bool ok = active && idx < n;
+              const bool ok = active && idx < n && (!SEL || src >= 0);
 #pragma unroll
               for (int i = 0; i < 4; ++i) v[u][i] = 0.f;
               if (ok) load_vec<4>(v[u], xc + (int64_t)src * A.ldx);
@@ -504,7 +553,7 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
       }
     }
     if (g == 0 && active) {
-      if (A.pre_scale && row < A.N) {
+      if (A.pre_scale && row < A.N && !skip) {
         float ps[4], pt[4];
         load_vec<4>(ps, A.pre_scale + c);
         load_vec<4>(pt, A.pre_shift + c);
@@ -538,7 +587,7 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
       for (int j = 0; j < kRootVecs; ++j) {
         const int idx = threadIdx.x + j * 256;
         const int r = idx / (KC / 4), c4 = (idx - r * (KC / 4)) * 4;
-        const int row = row_base + r;
+        const int row = tile_row<CE>(A, row_base, r);
 #pragma unroll
         for (int i = 0; i < 4; ++i) rootv[j][i] = 0.f;
         if (row < A.N) {
@@ -605,7 +654,7 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
     const int k4 = K >> 2;
     for (int idx = threadIdx.x; idx < TM * k4; idx += 256) {
       const int r = idx / k4, c4 = (idx - r * k4) * 4;
-      const int row = row_base + r;
+      const int row = tile_row<CE>(A, row_base, r);
       float v[4] = {0.f, 0.f, 0.f, 0.f};
       if (row < A.N) {
         load_vec<4>(v, blocked_at(A.xr, BLK ? A.xr_bc : 0, A.xr_bs, A.ldr, row, c4));
@@ -892,7 +941,8 @@ bool launch_dense_stream(const FusedArgs& A, hipStream_t s) {
 
 template <int G, int KC, bool DENSE = false>
 int launch(const FusedArgs& A, hipStream_t s) {
-  const int64_t blocks = cdiv(A.N, TM);
+  const int64_t blocks = A.ce_rows ? cdiv(A.ce_n_rows, TM) : cdiv(A.N, TM);  // a row list: its tiles only
+  if (blocks == 0) return RGBX_OK;  // an empty row list: every tile record is absent, the reduction sums nothing
   // the cross-entropy epilogue re-uses the tile as [TM][Nout + 4]
   const size_t lds = (size_t)TM * ((A.ce_part && A.Nout > A.K ? A.Nout : A.K) + 4) * sizeof(float);
   // NT = 32-column tiles a wave keeps accumulators for (Nout <= 128: 1, <= 256: 2); 0 = any Nout, tile by tile
@@ -909,6 +959,16 @@ int launch(const FusedArgs& A, hipStream_t s) {
       if (A.ce_part) spmm_linear_kernel<G, true, KC, 1, true, false, false, true><<<(int)blocks, 256, lds, s>>>(A);
       else spmm_linear_kernel<G, true, KC, 1, false, false, false, true><<<(int)blocks, 256, lds, s>>>(A);
       RGBX_CHECK_LAUNCH("spmm_linear_kernel (second aggregate)");
+      return RGBX_OK;
+    }
+  }
+  if constexpr (!DENSE && KC > 0) {
+    // column selection: the transposed launch of a last layer (Nout <= 128). Elsewhere col_sel is not honoured and every
+    // slot is gathered — the same result, as a deselected column's row is 0
+    if (A.col_sel && !blk && nt == 1) {
+      if (A.w) spmm_linear_kernel<G, true, KC, 1, false, false, false, false, true><<<(int)blocks, 256, lds, s>>>(A);
+      else spmm_linear_kernel<G, false, KC, 1, false, false, false, false, true><<<(int)blocks, 256, lds, s>>>(A);
+      RGBX_CHECK_LAUNCH("spmm_linear_kernel (column selection)");
       return RGBX_OK;
     }
   }
@@ -999,7 +1059,16 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
       return fail(RGBX_E_ARG, "spmm_linear: mask_groups must be 0, 1 or 2 (got %d)", (int)ce->mask_groups);
     if (ce->mask_groups == 2 && (ce->grad_scale || !ce->mask))
       return fail(RGBX_E_ARG, "spmm_linear: two statistics sets (mask_groups == 2) need a mask and no loss gradient");
+    if (ce->rows || ce->n_rows) {
+      if (!ce->rows || ce->n_rows < 0 || ce->n_rows > N)
+        return fail(RGBX_E_ARG, "spmm_linear: row list of %lld rows for N = %lld", (long long)ce->n_rows, (long long)N);
+      if (ce->grad_scale || dense || L.z_out || L.w_pos)
+        return fail(RGBX_E_ARG, "spmm_linear: a row list needs an aggregating statistics-only launch (no loss gradient, "
+                                "no z_out, no w_pos)");
+    }
   }
+  if (L.col_sel && (dense || ce || L.w_pos || L.out_blk || (L.x_root && L.xr_blk_cols > 0)))
+    return fail(RGBX_E_ARG, "fused_layer: col_sel needs an aggregating launch without ce, w_pos or blocked layouts");
   if ((L.w_pos != nullptr) != (L.z_pos_out != nullptr))
     return fail(RGBX_E_ARG, "fused_layer: w_pos and z_pos_out go together");
   if (L.w_pos) {
@@ -1077,6 +1146,13 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
               ce && ce->mask_groups == 2 ? 2 : 1,
               x_blk ? L.x_blk_cols : 0, L.x_blk_stride, xr_blk ? L.xr_blk_cols : 0, L.xr_blk_stride,
               L.out_blk, L.ob_cols, L.ob_stride, L.w_pos, L.z_pos_out, zlong_pos};
+  A.col_sel = L.col_sel;
+  if (ce) {
+    A.ce_rows = ce->rows;
+    A.ce_n_rows = (int)ce->n_rows;
+    A.ce_skip = ce->skip_unselected ? 1 : 0;
+  }
+  const int64_t tiles = A.ce_rows ? cdiv(A.ce_n_rows, TM) : cdiv(N, TM);  // tile records of the loss epilogue
   const int lanes = (int)(K / 4);
   int rc;
   if (dense) {  // the lane grouping of the gather is irrelevant: one instantiation per unrolled width
@@ -1099,7 +1175,7 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
   else rc = launch<64, 0>(A, s);
   if (rc) return rc;
   if (ce) {
-    if (int rc2 = reduce_ce_tiles(ce->scratch, (int)cdiv(N, TM), ce->stats, ce->mask_groups == 2 ? 6 : 3, s)) return rc2;
+    if (int rc2 = reduce_ce_tiles(ce->scratch, (int)tiles, ce->stats, ce->mask_groups == 2 ? 6 : 3, s)) return rc2;
   }
   if (!L.out_colsums) return RGBX_OK;
   return reduce_tile_stats(stats_part, (int)cdiv(N, TM), (int)(2 * Nout), stats_part2, L.out_colsums, N, s);

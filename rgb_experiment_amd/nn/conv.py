@@ -45,7 +45,8 @@ def _forward_folded(conv, x, edge_index, operands, ce, loops_mode, kind, root):
         if not ops.fused_ce_ok(graph, conv.in_channels, conv.out_channels, root, x, y):
             return None
         _, _, stats = ops.fused_layer(x, wt, csr=graph.fwd, w=w, rs=rs, bias=b, x_root=x if root else None,
-                                      wt_root=wtr if root else None, ce=(y, mask, None), kind=f"{kind}_linear_fwd")
+                                      wt_root=wtr if root else None, ce=(y, mask, None), kind=f"{kind}_linear_fwd",
+                                      select_rows=True)
         return None, stats  # an eval forward is read through its statistics; the mean loss is stats[0] / stats[1]
     out, _, _ = ops.fused_layer(x, wt, csr=graph.fwd, w=w, rs=rs, bias=b, x_root=x if root else None,
                                 wt_root=wtr if root else None, kind=f"{kind}_linear_fwd")

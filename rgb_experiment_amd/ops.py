@@ -472,7 +472,8 @@ def _blocked(t, what):
 
 
 def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_root=None, pre=None, want_out=True,
-                out_blocked=None, want_z=False, want_colsums=False, ce=None, kind="linear", out=None, z=None, w_pos=None):
+                out_blocked=None, want_z=False, want_colsums=False, ce=None, kind="linear", out=None, z=None, w_pos=None,
+                select_rows=False, col_sel=None):
     """One conv layer's arithmetic on rgbx_fused_layer_f32 (no autograd):
         z   = rs * sum_p w_p x[col_p]   over `csr`            (csr given: aggregate)
             = x                                                 (csr None: DENSE mode, the rows are loaded)
@@ -486,8 +487,12 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
     [N, K] tensors to write into (row ranges of bigger ones when a layer is launched piece by piece).
     `w_pos` (second weight vector over the same slots; implies want_z): z_pos = sum_p w_pos_p x[col_p] is stored as well
     and the return value is (out, (z, z_pos), colsums or stats).
+    `select_rows` (one-GPU callers, with `ce`): only the rows the loss selects are gathered — a statistics-only launch
+    runs over the cached list of those rows (selected_rows), a loss-gradient launch skips the others in place (their z
+    rows are 0, their gradient rows 0 as always); see rgbx_ce_epilogue_t.rows / skip_unselected.
+    `col_sel` (uint8 [n_src] or None): slots whose column has a 0 there are not gathered (rgbx_fused_layer_t.col_sel).
     Returns (out, z, colsums or stats)."""
-    _lib.require_device(x, wt, bias, x_root, wt_root, out_blocked)
+    _lib.require_device(x, wt, bias, x_root, wt_root, out_blocked, col_sel)
     lib = _lib.load()
     L = _lib.FusedLayer()
     dense = csr is None
@@ -509,6 +514,13 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
     L.wt = wt.data_ptr()
     if not dense:
         L.rowptr, L.col, L.w, L.rs = _lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w), _lib.ptr(rs)
+        if col_sel is not None:
+            if col_sel.dtype != torch.uint8 or col_sel.numel() < x.size(0):
+                raise RuntimeError(f"fused_layer: col_sel must be uint8 with an entry per input row, got {col_sel.dtype} "
+                                   f"{tuple(col_sel.shape)} for {x.size(0)} rows")
+            col_sel = col_sel.contiguous()
+            keep.append(col_sel)
+            L.col_sel = col_sel.data_ptr()
         split, _scratch = csr.split_arg(K, x.device, hub_rows=2 if w_pos is not None else 1)
         keep.append(_scratch)
         if split is not None:
@@ -551,6 +563,14 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
         ce_scratch = torch.empty(3 * groups * ((N + 31) // 32 + 64), dtype=torch.float64, device=x.device)
         ce_arg = _lib.CeEpilogue(_lib.ptr(y), _lib.ptr(mask), _lib.ptr(grad_scale), _lib.ptr(ce_stats),
                                  _lib.ptr(ce_scratch), groups)
+        if select_rows and not dense and w_pos is None:
+            if grad_scale is not None:
+                ce_arg.skip_unselected = 1
+            elif not want_z and z is None and mask is not None:
+                rows = selected_rows(y, mask, n_out)
+                if rows is not None:  # None: inside a graph capture before the list exists (all tiles, as before)
+                    ce_arg.rows, ce_arg.n_rows = rows.data_ptr(), rows.numel()
+                    keep.append(rows)
         keep += [y, mask, ce_scratch, ce_arg]
         L.ce = ctypes.addressof(ce_arg)
         want_out = grad_scale is not None  # statistics only: the logits are never written
@@ -620,7 +640,7 @@ def blocked_to_rows(src, out=None, bias=None):
 
 
 def spmm_linear_raw(csr, w, rs, x, wt, bias=None, want_z=False, x_root=None, wt_root=None, kind="linear", pre=None,
-                    want_colsums=False, ce=None):
+                    want_colsums=False, ce=None, select_rows=False):
     """out = (rs * sum_p w_p x[col_p]) wt + bias (+ x_root wt_root) on the fused aggregate+transform kernel; `wt` /
     `wt_root` are [K, Nout] row-major. Returns (out, z) with z the stored aggregate [N, K] if `want_z`. `pre` = (scale
     [K], shift [K], rowsum [N]): the gathered matrix (and the root rows) stand for x * scale + shift. `want_colsums`:
@@ -628,9 +648,10 @@ def spmm_linear_raw(csr, w, rs, x, wt, bias=None, want_z=False, x_root=None, wt_
     `ce` = (y, mask, grad_scale): the layer is the model's last and its logits go straight into the masked
     cross-entropy (rgbx_ce_epilogue_t): returns (out, z, stats) with stats [3] float64 = (nll sum, selected rows,
     correct); out = the loss gradient grad_scale * (softmax - onehot) when grad_scale is a device scalar, None (nothing
-    written) when it is None."""
+    written) when it is None. `select_rows`: see fused_layer."""
     out, z, extra = fused_layer(x, wt, csr=csr, w=w, rs=rs, bias=bias, x_root=x_root if wt_root is not None else None,
-                                wt_root=wt_root, pre=pre, want_z=want_z, want_colsums=want_colsums, ce=ce, kind=kind)
+                                wt_root=wt_root, pre=pre, want_z=want_z, want_colsums=want_colsums, ce=ce, kind=kind,
+                                select_rows=select_rows)
     if ce is not None or want_colsums:
         return out, z, extra
     return out, z
@@ -762,24 +783,27 @@ class _PropagateLinear(torch.autograd.Function):
         return gx, None, None, gw, gb, None, gwr, None, None
 
 
-def _propagate_linear_input_grad(g, kind, gy, weight, root_weight):
+def _propagate_linear_input_grad(g, kind, gy, weight, root_weight, ce_sel=None):
     """dx = P^T (dy W) + dy Wr = (P^T dy) W + dy Wr: the fused kernel on the transposed CSR (W as stored is already
     the [K, Nout] operand) when in == out, else GEMMs and the transposed SpMM with the root part as its additive
-    term."""
+    term. `ce_sel` = (y, mask, C): dy is the loss gradient of the masked cross-entropy, zero outside the rows that loss
+    selects; the fused kernel then does not gather those rows (selected_cols; every slot keeps its place in the sum, so
+    the result is the full gather's, bit for bit)."""
+    csr = g.bwd
     wt = {"gcn": lambda: g.w_t, "mean": lambda: g.w_mean_t, "sum": lambda: None}[kind]()
     prefix = getattr(g, "event_prefix", "")
     n_out, n_in = weight.shape
     if n_out <= n_in and _lib.load().rgbx_spmm_linear_supported(n_out, n_in, int(root_weight is not None)):
-        gx, _ = spmm_linear_raw(g.bwd, wt, None, gy, weight.detach().contiguous(), None, False,
-                                gy if root_weight is not None else None,
-                                None if root_weight is None else root_weight.detach().contiguous(),
-                                kind=f"{prefix}{kind}_linear_bwd")
+        gx, _, _ = fused_layer(gy, weight.detach().contiguous(), csr=csr, w=wt,
+                               x_root=gy if root_weight is not None else None,
+                               wt_root=None if root_weight is None else root_weight.detach().contiguous(),
+                               col_sel=None if ce_sel is None else selected_cols(*ce_sel), kind=f"{prefix}{kind}_linear_bwd")
         return gx
     gz = gy @ weight
     gr = gy @ root_weight if root_weight is not None else None
     if gr is None:
-        return spmm_raw(g.bwd, wt, None, gz, kind=f"{prefix}{kind}_bwd")
-    return spmm_raw(g.bwd, wt, None, gz, y=gr, a=1.0, b=1.0, out=gr, kind=f"{prefix}{kind}_bwd")
+        return spmm_raw(csr, wt, None, gz, kind=f"{prefix}{kind}_bwd")
+    return spmm_raw(csr, wt, None, gz, y=gr, a=1.0, b=1.0, out=gr, kind=f"{prefix}{kind}_bwd")
 
 
 class _BNPropagateLinear(torch.autograd.Function):
@@ -869,6 +893,62 @@ def group_masks(mask_a, mask_b):
     return hit[0].get()
 
 
+def ce_selection(y, mask, C):
+    """bool [N]: the rows the masked cross-entropy selects — mask bit(s) set (either of the two of a grouped mask) AND a
+    label in [0, C). The loss epilogue's own predicate (spmm_linear.hip, ce_select), restated for the row list of the
+    statistics-only form (selected_rows) and the column selection of the backward's transposed gather (selected_cols)."""
+    sel = (y >= 0) & (y < C)
+    if mask is not None:
+        sel = sel & mask.bool()
+    return sel
+
+
+def _sel_key(y, mask, C):
+    return (y.data_ptr(), y._version, y.numel(),
+            None if mask is None else (mask.data_ptr(), mask._version, mask.numel()), int(C))
+
+
+_SEL_ROWS = {}
+
+
+def selected_rows(y, mask, C):
+    """int32 device list (ascending) of the rows ce_selection picks: the tiles of a statistics-only loss launch
+    (rgbx_ce_epilogue_t.rows). Built once per (labels, mask, C) — keyed on address, in-place version and size, so an
+    edited mask gets a new list — with the one host read of `nonzero`; None inside a graph capture where the list does
+    not exist yet (the caller then runs every tile)."""
+    key = _sel_key(y, mask, C)
+    hit = _SEL_ROWS.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        rows = ce_selection(y, mask, C).nonzero().reshape(-1).to(torch.int32).contiguous()
+        hit = (_MadeOn(rows), y, mask)  # the tensors stay alive with their addresses
+        _SEL_ROWS[key] = hit
+        while len(_SEL_ROWS) > 16:
+            _SEL_ROWS.pop(next(iter(_SEL_ROWS)))
+    return hit[0].get()
+
+
+_SEL_COLS = {}
+
+
+def selected_cols(y, mask, C):
+    """uint8 device vector of ce_selection: the column selection (rgbx_fused_layer_t.col_sel) of the transposed gather of
+    a loss gradient that is zero on every row the loss does not select. Built once per (labels, mask, C), keyed as
+    selected_rows; None inside a graph capture where it does not exist yet (every slot gathered, same result)."""
+    key = _sel_key(y, mask, C)
+    hit = _SEL_COLS.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        hit = (_MadeOn(ce_selection(y, mask, C).to(torch.uint8).contiguous()), y, mask)
+        _SEL_COLS[key] = hit
+        while len(_SEL_COLS) > 16:
+            _SEL_COLS.pop(next(iter(_SEL_COLS)))
+    return hit[0].get()
+
+
+
 def ce_from_logits(logits, y, mask):
     """(loss, stats) of the masked cross-entropy taken from materialised logits: the unfused route of the *_ce
     entry points. loss = NLLLoss(log_softmax(logits)[mask], y[mask]); stats = [nll sum, selected rows, correct].
@@ -910,8 +990,11 @@ class _PropagateLinearCE(torch.autograd.Function):
             graph.fwd, w, rs, x, weight_t(weight), None if bias is None else bias.detach(),
             want_grad and weight.requires_grad, x if root_weight is not None else None,
             None if root_weight is None else weight_t(root_weight), kind=f"{kind}_linear_fwd", pre=pre,
-            ce=(y, mask, grad_scale))
+            ce=(y, mask, grad_scale), select_rows=True)
         ctx.graph, ctx.kind, ctx.has_bias, ctx.has_bn = graph, kind, bias is not None, bn_weight is not None
+        # the saved dy is the loss gradient: zero outside the selected rows, so the backward's transposed gather may skip
+        # the rows of those slots (selected_cols)
+        ctx.ce_sel = (y, mask, weight.size(0)) if want_grad else None
         if want_grad:
             if ctx.has_bn:
                 ctx.save_for_backward(dlogits, z, weight, root_weight, x, bn_weight, mean, rstd, n, scale, shift)
@@ -955,7 +1038,7 @@ class _PropagateLinearCE(torch.autograd.Function):
         sc = dict(zip((k for k, _ in items), torch._foreach_mul([t for _, t in items], g))) if items else {}
         gw, gb, gwr = sc.get("gw"), sc.get("gb"), sc.get("gwr")
         if need_h:
-            g_h = _propagate_linear_input_grad(graph, kind, gy, sc["w"], sc.get("wr"))
+            g_h = _propagate_linear_input_grad(graph, kind, gy, sc["w"], sc.get("wr"), ce_sel=ctx.ce_sel)
             if ctx.has_bn:
                 gx, g_bnw, g_bnb = B.train_backward(g_h, x, bn_weight, mean, rstd, n, ctx.reduce)
             else:
