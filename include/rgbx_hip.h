@@ -19,6 +19,7 @@
  *                         restated in-repo by models/pta.py:79-84.
  *   rgbx_dagnn_gate_*     Prop.forward's sigmoid-gated mix of the K+1 hops (models/dagnn.py:49-55) and its backward.
  *   rgbx_gat_*            GATConv.forward/message + segment softmax (models/gat.py:28,30) [PyG].
+ *   rgbx_supergat_*       SuperGATConv ('MX' attention, attention loss, negative sampling; models/supergat.py) [PyG].
  *   rgbx_gemm_tn_f32      dW = dY^T X of the nn.Linear / conv.lin layers under loss.backward()
  *                         (itexperiments.py:439; layers at models/gcn.py:18-21, appnp_stack.py:19-20).
  *   rgbx_bn_* / rgbx_affine_cols_f32
@@ -487,6 +488,87 @@ int rgbx_gat_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const fl
                          int64_t ldg, float* g_hfeat, int64_t ldgh, float* g_a_src, float* ds,
                          const float* att2, const float* g_a_dst, int64_t N, int H, int C, float slope,
                          const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* ---- SuperGAT: "MX" attention (per-edge dot product inside the edge-softmax) + link-prediction loss ---------- */
+
+/* For an edge j -> i (p = its slot in the target-grouped CSR) and head h, with hfeat [N, H*C]:
+ *   d_p   = <hfeat[i,h,:], hfeat[j,h,:]>
+ *   s_p   = (<hfeat[j,h,:], att_l[h,:]> + <hfeat[i,h,:], att_r[h,:]>) * sigmoid(d_p)
+ *   alpha = softmax over the in-edges of i of leaky_relu(s_p, slope), as rgbx_gat_aggregate_fwd_f32 forms it
+ *   out[i,h,:] = sum_p alpha_p * kappa_p * hfeat[j,h,:] (+ bias)
+ * (SuperGATConv with attention_type='MX' [PyG], reference models/supergat.py). kappa = 1 in inference mode.
+ *
+ * Randomness. `seed` points to two 32-bit words ON THE DEVICE; NULL selects inference mode. Every random decision is
+ * a hash of (seed, forward CSR slot, head) or (seed, negative slot, re-draw), so that the backward passes recompute
+ * them and no per-edge tensor is stored:
+ *   attention dropout  kappa_p[h] = keep / (1 - p_drop), keep with probability 1 - p_drop per (slot, head);
+ *   positive sample    slot p takes part in the loss with probability pos_ratio (edge_sample_ratio).
+ * rgbx_supergat_draws_u8 writes both decisions out ([E'] and [E', H], 0 / 1) for inspection. */
+
+/* 1 if the attention kernels take H heads of C channels (as GATConv.kernel_channels: any C <= 64, even C <= 128,
+ * C % 4 == 0 up to 256), else 0. Wider heads are padded per head by the caller. */
+int rgbx_supergat_supported(int H, int C);
+
+/* Number of 8-byte (sum, count) records the training forward over N rows with this split writes. */
+int rgbx_supergat_loss_records(int64_t N, const rgbx_row_split_t* split, int64_t* count);
+
+/* Forward over the target-grouped CSR: one gather pass; the target's row stays in registers. Saves m / rden ([N, H],
+ * of the UNDROPPED softmax). `bias` ([H*C], optional) is added in the store. Training mode (seed != NULL) also forms the
+ * positive half of the link-prediction loss in the same pass: for every kept slot the term softplus(-mean_h d_p);
+ * (sum, count) per workgroup go to `loss_records` (n_loss_records >= rgbx_supergat_loss_records, 16-byte aligned) and
+ * are added in record order, in double, into pos_stats[0] = sum and pos_stats[1] = count (reproducible).
+ * `split`: hub rows as in rgbx_gat_aggregate_fwd_f32; split->partial holds n_chunks * (H*C + 2*H) floats. */
+int rgbx_supergat_aggregate_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* hfeat, int64_t ldh,
+                                    const float* att_l, const float* att_r, const float* bias, float* out, int64_t ldo,
+                                    float* m, float* rden, int64_t N, int H, int C, float slope, const uint32_t* seed,
+                                    float p_drop, float pos_ratio, float* loss_records, int64_t n_loss_records,
+                                    double* pos_stats, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward. Per edge and head, with t = <h_j, att_l> + <h_i, att_r>, sg = sigmoid(d):
+ *   g_e = alpha (kappa <gout_i, h_j> - <gout_i, out_i - bias>),  g_s = g_e lrelu'(s),  g_t = g_s sg,
+ *   g_d = g_s t sg (1 - sg)  +  [slot kept as a positive] (sigmoid(mean_h d) - 1) / H * gl[0]
+ * `gl` (device scalar, training mode) = d loss / d att_loss divided by the number of loss terms.
+ * Target side, over the forward CSR: g_hfeat[i,h,:] = sum_p g_d h_j + (sum_p g_t) att_r[h,:] (STORED), g_ar[i,h] = sum_p g_t,
+ * and the record nodeq[i,h] = (<h_i, att_r>, m - log(rden), <gout_i, out_i - bias>, 0) ([N, H, 4], 16-byte aligned).
+ * split->partial holds n_chunks * (H*C + H) floats. */
+int rgbx_supergat_bwd_dst_f32(const int32_t* rowptr, const int32_t* col, const float* hfeat, int64_t ldh,
+                              const float* att_l, const float* att_r, const float* m, const float* rden,
+                              const float* out, int64_t ldo, const float* bias, const float* gout, int64_t ldg,
+                              float* nodeq, float* g_hfeat, int64_t ldgh, float* g_ar, int64_t N, int H, int C,
+                              float slope, const uint32_t* seed, float p_drop, float pos_ratio, const float* gl,
+                              const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i), run AFTER the target side:
+ *   g_hfeat[j,h,:] += sum_p (alpha_p kappa_p gout[i,h,:] + g_d h_i) + (sum_p g_t) att_l[h,:],   g_al[j,h] = sum_p g_t.
+ * `t2f` ([E'], training mode): the forward CSR slot of every transposed slot (the key of its random decisions).
+ * The attention-vector gradients are rgbx_gat_scores_bwd_f32(hfeat, g_al, g_ar, ..., g_hfeat = NULL). */
+int rgbx_supergat_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const float* hfeat,
+                              int64_t ldh, const float* att_l, const float* nodeq, const float* gout, int64_t ldg,
+                              float* g_hfeat, int64_t ldgh, float* g_al, int64_t N, int H, int C, float slope,
+                              const uint32_t* seed, float p_drop, float pos_ratio, const float* gl,
+                              const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* n_neg ordered pairs (u, v), u != v, neither in `keys`: the ascending distinct keys a * N + b of the UNDIRECTED edge
+ * set (rgbx_coalesce_keys_i64 with mirror = 1). Slot k tries up to `redraws` i.i.d. uniform pairs; neg[k] = u,
+ * neg[n_neg + k] = v, valid[k] = 1, or valid[k] = 0 (pair (0, 0)) when every draw was rejected. Duplicates may occur. */
+int rgbx_supergat_sample_negatives(const uint64_t* keys, int64_t n_keys, int64_t N, const uint32_t* seed, int64_t n_neg,
+                                   int redraws, int64_t* neg, uint8_t* valid, rgbx_stream_t stream);
+
+/* Negative half of the loss: for every valid pair (valid NULL = all) the term softplus(<h_u, h_v> / H) over the whole
+ * row; neg_stats[0] = sum, neg_stats[1] = count (double), via at most 8192 (sum, count) records added in record order. */
+int rgbx_supergat_neg_loss_fwd_f32(const float* hfeat, int64_t ldh, const int64_t* neg, const uint8_t* valid,
+                                   int64_t n_neg, int H, int C, float* loss_records, int64_t n_loss_records,
+                                   double* neg_stats, rgbx_stream_t stream);
+
+/* Its backward: g_hfeat[u,:] += g_z h_v and g_hfeat[v,:] += g_z h_u, g_z = sigmoid(z) gl[0] / H. Pairs share rows, so
+ * the rows are updated with float atomics: THIS ONE SUM IS ORDER-DEPENDENT (last-bit differences between runs). */
+int rgbx_supergat_neg_loss_bwd_f32(const float* hfeat, int64_t ldh, const int64_t* neg, const uint8_t* valid,
+                                   int64_t n_neg, int H, int C, const float* gl, float* g_hfeat, int64_t ldgh,
+                                   rgbx_stream_t stream);
+
+/* pos[p] = 1 where slot p is a kept positive, drop[p * H + h] = 1 where (p, h) survives the attention dropout. */
+int rgbx_supergat_draws_u8(const uint32_t* seed, int64_t nnz, int H, float p_drop, float pos_ratio, uint8_t* pos,
+                           uint8_t* drop, rgbx_stream_t stream);
 
 /* ---- dense layers on the MFMA units -------------------------------------------------------- */
 

@@ -178,6 +178,47 @@ class Graph:
         return cache[kind]
 
     @property
+    def undirected_keys(self):
+        """(keys, count): the ascending distinct 64-bit keys a * N + b of the undirected edge set (both directions of every
+        input edge; rgbx_coalesce_keys_i64 with mirror = 1), built once: what the SuperGAT negative sampler searches."""
+        cached = self.__dict__.get("_und_keys")
+        if cached is None:
+            lib = _lib.load()
+            dev = self.fwd.rowptr.device
+            M = 2 * self.E
+            keys = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+            count = 0
+            if M:
+                nbytes = ctypes.c_size_t(0)
+                _lib.check(lib.rgbx_coalesce_workspace_bytes(self.E, self.N, 1, ctypes.byref(nbytes)),
+                           "rgbx_coalesce_workspace_bytes")
+                counts = torch.empty(2, dtype=torch.int64, device=dev)
+                ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+                _lib.check(lib.rgbx_coalesce_keys_i64(_lib.ptr(self._src.contiguous()), _lib.ptr(self._dst.contiguous()),
+                                                      self.E, self.N, 1, _lib.ptr(keys), _lib.ptr(counts), _lib.ptr(ws),
+                                                      ws.numel(), _lib.stream_ptr()), "rgbx_coalesce_keys_i64")
+                count = int(counts[0].item())  # one read-back per graph
+            cached = self._und_keys = (keys, count)
+        return cached
+
+    @property
+    def t2f(self):
+        """int32 [E']: the forward CSR slot of every transposed CSR slot (same edge), from the two slot -> edge-id
+        permutations; the SuperGAT backward keys an edge's random decisions by its forward slot."""
+        cached = self.__dict__.get("_t2f")
+        if cached is None:
+            f, b = self.fwd, self.bwd
+            if f.nnz:
+                inv = torch.empty(int(max(f.perm[:f.nnz].max(), b.perm[:b.nnz].max()).item()) + 1, dtype=torch.int32,
+                                  device=f.perm.device)
+                inv[f.perm[:f.nnz].long()] = torch.arange(f.nnz, dtype=torch.int32, device=inv.device)
+                cached = inv[b.perm[:b.nnz].long()].contiguous()
+            else:
+                cached = b.col
+            self._t2f = cached
+        return cached
+
+    @property
     def w_mean_t(self):
         """Per transposed slot (j -> i): 1/deg(i), the weight of dY[i] in dX[j] for aggr='mean'."""
         if self._w_mean_t is None:

@@ -8,7 +8,8 @@ class InitialParameters:
     default_data_path = os.environ.get("RGB_DATA_ROOT", os.path.join(os.path.dirname(_PKG), "data"))
     default_pics_path = os.path.join(os.path.dirname(_PKG), "pics")
 
-    model_names = ["MLP", "GCN", "GraphSAGE", "GAT", "APPNPStack", "GraphSAGE2", "PTA", "DAGNN", "SGC", "GIN", "GGNN"]
+    model_names = ["MLP", "GCN", "GraphSAGE", "GAT", "APPNPStack", "GraphSAGE2", "PTA", "DAGNN", "SGC", "GIN", "GGNN",
+                   "SuperGAT"]
     # reference initial_params.py:24-35
     default_init_params = [
         {"num_layers": 3, "hidden_unit": 64, "dropout_rate": 0.5},
@@ -22,6 +23,8 @@ class InitialParameters:
         {"K": 2},
         {"num_layers": 2, "hidden_unit": 64, "dropout_rate": 0.5},
         {"num_layers": 2, "hidden_unit": 64, "dropout_rate": 0.5},  # GGNN, reference initial_params.py:28
+        {"hidden_dim": 8, "heads": 8, "dropout_rate": 0.6, "edge_sample_ratio": 0.8,
+         "neg_sample_ratio": 0.5},  # SuperGAT, reference initial_params.py:33
     ]
 
     # reference initial_params.py:42

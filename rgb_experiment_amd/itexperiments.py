@@ -6,7 +6,8 @@ Scope: data loading / mask remake / feature normalisation / 
 lower-cased ``model_name`` / full-batch Adam + NLLLoss loop with early stopping / the PTA branch
 (label propagation + soft-label loss + propagated inference, reference :351-374, :422-462) / metrics
 dict / Correct & Smooth post-processing (reference :514-534). Out of scope and rejected with
-``NotImplementedError``: plots, PCA (reference :536-601) and the SuperGAT / FAGCN zoo members.
+``NotImplementedError``: plots, PCA (reference :536-601) and the FAGCN zoo member. SuperGAT trains on
+``NLL + supergat_graph_lambda * att_loss`` (reference :431-432), on the eager loop.
 
 Deliberate deviations from reference quirks:
   * ``compare_pred_label(need_all_metrics=False)`` returns zeros instead of raising
@@ -33,7 +34,7 @@ from .models import MODELS
 from .rd2pd import RD2PD
 from .utils import get_classification_mask, get_random_mask, get_whole_mask, to_undirected
 
-_OUT_OF_SCOPE = ("supergat", "fagcn")
+_OUT_OF_SCOPE = ("fagcn",)
 
 
 def _macro_prf(label, pred):
@@ -356,6 +357,10 @@ def experiment(model_init_param: dict, *,
     optimizer = torch.optim.Adam(net.parameters(), lr=learning_rate, weight_decay=weight_decay,
                                  capturable=device.type == "cuda")
     want_graph = bool(use_hip_graph) and device.type == "cuda" and not is_pta
+    is_supergat = name == "supergat"
+    if want_graph and is_supergat:
+        say("SuperGAT draws its edge samples every step: running the eager loop (use_hip_graph is ignored)")
+        want_graph = False
     if want_graph and use_hip_graph != "always" and name != "mlp" and data.edge_index.size(1) > HIP_GRAPH_MAX_EDGES:
         say(f"{data.edge_index.size(1)} edges: the epoch is kernel-bound, running the eager loop (use_hip_graph='always' "
             "forces the capture)")
@@ -406,6 +411,8 @@ def experiment(model_init_param: dict, *,
             # same kernels as the captured epoch (models/_stack.masked_ce), so both loops train bit-identically
             from .models._stack import masked_ce
             loss, stats = masked_ce(net, fwd, y, train_mask)
+            if is_supergat:  # reference :431-432
+                loss = loss + supergat_graph_lambda * net.att_loss
             hist["train_acc"].append((stats[2] / stats[1]).item())
         else:
             res = net(**fwd)

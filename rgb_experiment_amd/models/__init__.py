@@ -1,5 +1,5 @@
 """Model registry (reference models/__init__.py:1-13): the hot-path models plus the "next" rows of
-SURVEY §8f that reuse the same kernels (DAGNN, PTA, SGC, GIN) and GGNN. SuperGAT and FAGCN are out of scope."""
+SURVEY §8f that reuse the same kernels (DAGNN, PTA, SGC, GIN), GGNN and SuperGAT. FAGCN is out of scope."""
 from .mlp import MLP
 from .gcn import GCN
 from .graphsage import GraphSAGE
@@ -11,6 +11,7 @@ from .pta import PTA
 from .sgc import SGC
 from .gin import GIN
 from .ggnn import GGNN
+from .supergat import SuperGAT
 
 REGISTRY = {
     "mlp": MLP,
@@ -27,4 +28,4 @@ REGISTRY = {
 
 # Every model experiment() dispatches to by lower-cased model_name: REGISTRY (the set above, pinned as it stands by the
 # host tests) plus the zoo members added after it.
-MODELS = {**REGISTRY, "ggnn": GGNN}
+MODELS = {**REGISTRY, "ggnn": GGNN, "supergat": SuperGAT}

@@ -7,6 +7,7 @@ computing their ``propagate`` in HIP kernels (rgb_experiment_amd.ops).
   GATConv    <- torch_geometric.nn.conv.GATConv   (reference models/gat.py:3,18-21)
   APPNP      <- torch_geometric.nn.conv.APPNP     (reference models/appnp_stack.py:3,22)
   GatedGraphConv <- torch_geometric.nn.GatedGraphConv (reference models/ggnn.py:3,18)
+  SuperGATConv <- torch_geometric.nn.SuperGATConv   (reference models/supergat.py)
 
 Dense X·W^T products go through hipBLASLt (forward, input gradient) and rgbx_gemm_tn_f32 (weight
 gradient, split-K fp32 MFMA); everything indexed by edge_index goes through librgbx_hip.so.
@@ -612,3 +613,76 @@ class GatedGraphConv(nn.Module):
 
     def __repr__(self):
         return f"{self.__class__.__name__}({self.out_channels}, num_layers={self.num_layers})"
+
+
+class SuperGATConv(nn.Module):
+    """SuperGAT's layer with 'MX' attention [PyG SuperGATConv; reference models/supergat.py]: h = x W^T viewed [N,H,C];
+    for an edge j -> i: d = <h_i, h_j>, e = LeakyReLU((<h_j, att_l> + <h_i, att_r>) * sigmoid(d), 0.2); softmax over the
+    in-edges of i (self-loops removed then re-added), dropout on the coefficients, out_i = sum_j alpha_ij h_j; heads
+    concatenated or averaged; + bias. A training forward also forms the self-supervised attention loss — binary
+    cross-entropy of the logits mean_h d over a sample of the edges (label 1) and sampled non-edges (label 0) — read
+    with get_attention_loss(). All of it runs in the rgbx_supergat_* kernels (ops.supergat_attend)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0,
+                 add_self_loops=True, bias=True, attention_type="MX", edge_sample_ratio=1.0, neg_sample_ratio=0.5,
+                 is_undirected=False):
+        super().__init__()
+        if attention_type != "MX":
+            raise NotImplementedError(f"SuperGATConv: attention_type={attention_type!r}; only 'MX' (the reference's) is built")
+        if not add_self_loops:
+            raise NotImplementedError("SuperGATConv: add_self_loops=False is not built (the reference leaves it on)")
+        if not (0.0 <= edge_sample_ratio <= 1.0 and 0.0 <= neg_sample_ratio and 0.0 <= dropout < 1.0):
+            raise ValueError("SuperGATConv: edge_sample_ratio in [0, 1], neg_sample_ratio >= 0, dropout in [0, 1)")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.heads, self.concat, self.negative_slope, self.dropout = heads, concat, negative_slope, dropout
+        self.add_self_loops, self.attention_type = add_self_loops, attention_type
+        self.edge_sample_ratio, self.neg_sample_ratio, self.is_undirected = edge_sample_ratio, neg_sample_ratio, is_undirected
+        self.lin = nn.Linear(in_channels, heads * out_channels, bias=False)
+        self.att_l = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_r = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self._att_loss = None
+        self.last_draw = {}  # seed and negative pairs of the last training forward (ops.supergat_random_choices)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot_(self.lin.weight)
+        glorot_(self.att_l)
+        glorot_(self.att_r)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def get_attention_loss(self):
+        """The attention loss of the last forward (0 after an eval-mode forward)."""
+        if self._att_loss is None:
+            raise RuntimeError("SuperGATConv.get_attention_loss(): no forward has run yet")
+        return self._att_loss
+
+    def forward(self, x, edge_index, neg_edge_index=None):
+        H, C = self.heads, self.out_channels
+        Cp = GATConv.kernel_channels(C)
+        graph = get_graph(edge_index, x.size(0), LOOPS_REMOVE_ADD)
+        in_kernel = self.bias is not None and (self.concat or H == 1)  # the bias rides in the aggregation kernel's store
+        weight, att_l, att_r, bias = self.lin.weight, self.att_l, self.att_r, self.bias
+        if Cp != C:  # pad every head with zero weight rows / attention entries: no score, logit or kept column changes
+            pad = torch.nn.functional.pad
+            weight = pad(weight.view(H, C, -1), (0, 0, 0, Cp - C)).reshape(H * Cp, -1)
+            att_l, att_r = pad(att_l, (0, Cp - C)), pad(att_r, (0, Cp - C))
+            if in_kernel:
+                bias = pad(bias.view(H, C), (0, Cp - C)).reshape(-1)
+        h = ops.linear(x, weight)
+        self.last_draw = {}
+        out, self._att_loss = ops.supergat_attend(
+            h, att_l, att_r, graph, H, Cp, self.negative_slope, bias=bias if in_kernel else None, training=self.training,
+            p_drop=self.dropout, pos_ratio=self.edge_sample_ratio, neg_ratio=self.neg_sample_ratio,
+            neg_edge_index=neg_edge_index, record=self.last_draw)
+        if Cp != C:
+            out = out.view(-1, H, Cp)[:, :, :C].reshape(-1, H * C)
+        if not self.concat and H > 1:
+            out = out.view(-1, H, C).mean(dim=1)
+        if self.bias is not None and not in_kernel:
+            out = out + self.bias
+        return out

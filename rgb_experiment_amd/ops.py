@@ -1791,6 +1791,202 @@ def gat_attend_linear(x, weight, att_src, att_dst, graph, slope=0.2, bias=None, 
     return _GATAttendLinear.apply(x, weight, att_src, att_dst, bias, graph, slope, y, mask, want_grad)
 
 
+SUPERGAT_REDRAWS = 8  # candidate pairs a negative slot may draw before it is dropped from the loss
+
+
+def _supergat_split(csr, H, C, scalars, dev):
+    split, scratch = csr.split_arg(H * C + scalars * H, dev)
+    return (None if split is None else ctypes.byref(split)), split, scratch
+
+
+def supergat_sample_negatives(graph, seed, n_neg):
+    """(neg int64 [2, n_neg], valid uint8 [n_neg]): ordered non-edges drawn on the device (no host read)."""
+    dev = seed.device
+    neg = torch.empty((2, max(n_neg, 1)), dtype=torch.int64, device=dev)[:, :n_neg].contiguous()
+    valid = torch.empty(n_neg, dtype=torch.uint8, device=dev)
+    keys, n_keys = graph.undirected_keys
+    _lib.check(_lib.load().rgbx_supergat_sample_negatives(_lib.ptr(keys), n_keys, graph.N, _lib.ptr(seed), n_neg,
+                                                          SUPERGAT_REDRAWS, _lib.ptr(neg), _lib.ptr(valid),
+                                                          _lib.stream_ptr()), "rgbx_supergat_sample_negatives")
+    return neg, valid
+
+
+def supergat_random_choices(record, graph, H):
+    """The exact random choices of the training forward that filled `record` (SuperGATConv keeps the record of its last
+    forward): {'pos': bool [E'] in forward CSR slot order, 'drop': bool [E', H] (True = kept), 'neg': int64 [2, n_neg],
+    'valid': bool [n_neg], 'src' / 'dst': int64 [E'] endpoints of every forward CSR slot}."""
+    csr = graph.fwd
+    dev = csr.rowptr.device
+    nnz = csr.nnz
+    pos = torch.empty(nnz, dtype=torch.uint8, device=dev)
+    drop = torch.empty((nnz, H), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().rgbx_supergat_draws_u8(_lib.ptr(record["seed"]), nnz, H, float(record["p_drop"]),
+                                                  float(record["pos_ratio"]), _lib.ptr(pos), _lib.ptr(drop),
+                                                  _lib.stream_ptr()), "rgbx_supergat_draws_u8")
+    deg = (csr.rowptr[1:] - csr.rowptr[:-1]).long()
+    dst = torch.repeat_interleave(torch.arange(csr.N, device=dev), deg)
+    valid = record["valid"]
+    return {"pos": pos.bool(), "drop": drop.bool(), "neg": record["neg"],
+            "valid": torch.ones(record["neg"].size(1), dtype=torch.bool, device=dev) if valid is None else valid.bool(),
+            "src": csr.col[:nnz].long(), "dst": dst}
+
+
+class _SuperGATAttend(torch.autograd.Function):
+    """One SuperGATConv ('MX') attention block as a single autograd node: fused score + edge-softmax + aggregation
+    (+ attention dropout + the positive half of the link-prediction loss in training mode), the negative sampler and
+    the negative half of the loss; backward = target-side pass, source-side pass, negative scatter, attention-vector
+    sums. Returns (out [N, H*C], att_loss scalar)."""
+
+    @staticmethod
+    def forward(ctx, hfeat, att_l, att_r, graph, H, C, slope, bias, train, p_drop, pos_ratio, neg_ratio, neg_edge_index,
+                record):
+        _lib.require_device(hfeat, att_l, att_r, bias, neg_edge_index)
+        lib = _lib.load()
+        hfeat = hfeat.contiguous()
+        b = None if bias is None else bias.detach().reshape(H * C).contiguous()
+        al = att_l.detach().reshape(H, C).contiguous()
+        ar = att_r.detach().reshape(H, C).contiguous()
+        csr, N, dev = graph.fwd, graph.fwd.N, hfeat.device
+        if hfeat.size(0) != N:
+            raise RuntimeError(f"supergat_attend: {hfeat.size(0)} feature rows for a graph of {N} nodes")
+        out = torch.empty((N, H * C), dtype=torch.float32, device=dev)
+        m = torch.empty((N, H), dtype=torch.float32, device=dev)
+        rden = torch.empty_like(m)
+        ph, ldh = _lib.mat(hfeat, "hfeat")
+        po, ldo = _lib.mat(out, "out")
+        split_ref, split, _scratch = _supergat_split(csr, H, C, 2, dev)
+        seed = records = pos_stats = None
+        n_rec = 0
+        if train:
+            # two 32-bit words from torch's device generator (torch.manual_seed makes the run repeatable); they stay
+            # on the device: every kernel reads them there
+            seed = torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32, device=dev)
+            cnt = ctypes.c_int64(0)
+            _lib.check(lib.rgbx_supergat_loss_records(N, split_ref, ctypes.byref(cnt)), "rgbx_supergat_loss_records")
+            n_rec = max(cnt.value, 8192)
+            records = torch.empty((n_rec, 2), dtype=torch.float32, device=dev)
+            pos_stats = torch.empty(2, dtype=torch.float64, device=dev)
+        with _Timed("supergat_fwd"):
+            _lib.check(
+                lib.rgbx_supergat_aggregate_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), ph, ldh, _lib.ptr(al),
+                                                    _lib.ptr(ar), _lib.ptr(b), po, ldo, _lib.ptr(m), _lib.ptr(rden), N, H,
+                                                    C, float(slope), _lib.ptr(seed), float(p_drop), float(pos_ratio),
+                                                    _lib.ptr(records), n_rec, _lib.ptr(pos_stats), split_ref,
+                                                    _lib.stream_ptr()), "rgbx_supergat_aggregate_fwd_f32")
+        ctx.train = train
+        ctx.graph, ctx.H, ctx.C, ctx.slope = graph, H, C, slope
+        ctx.att_shapes = (att_l.shape, att_r.shape)
+        ctx.bias_shape = None if bias is None else bias.shape
+        ctx.rng = (float(p_drop), float(pos_ratio))
+        if not train:
+            ctx.save_for_backward(hfeat, al, ar, b, m, rden, out)
+            loss = torch.zeros((), dtype=torch.float32, device=dev)
+            ctx.mark_non_differentiable(loss)
+            return out, loss
+        if neg_edge_index is None:
+            n_neg = int(neg_ratio * pos_ratio * csr.nnz)
+            neg, valid = supergat_sample_negatives(graph, seed, n_neg)
+        else:
+            neg, valid = neg_edge_index.contiguous(), None
+            n_neg = neg.size(1)
+        neg_stats = torch.empty(2, dtype=torch.float64, device=dev)
+        with _Timed("supergat_neg_fwd"):
+            _lib.check(lib.rgbx_supergat_neg_loss_fwd_f32(ph, ldh, _lib.ptr(neg), _lib.ptr(valid), n_neg, H, C,
+                                                          _lib.ptr(records), n_rec, _lib.ptr(neg_stats),
+                                                          _lib.stream_ptr()), "rgbx_supergat_neg_loss_fwd_f32")
+        terms = (pos_stats[1] + neg_stats[1]).clamp(min=1.0)
+        loss = ((pos_stats[0] + neg_stats[0]) / terms).to(torch.float32)
+        if record is not None:
+            record.update(seed=seed, neg=neg, valid=valid, p_drop=float(p_drop), pos_ratio=float(pos_ratio),
+                          pos_stats=pos_stats, neg_stats=neg_stats)
+        ctx.save_for_backward(hfeat, al, ar, b, m, rden, out, seed, neg, valid, terms)
+        return out, loss
+
+    @staticmethod
+    def backward(ctx, gout, g_loss):
+        train = ctx.train
+        if train:
+            hfeat, al, ar, b, m, rden, out, seed, neg, valid, terms = ctx.saved_tensors
+        else:
+            hfeat, al, ar, b, m, rden, out = ctx.saved_tensors
+            seed = neg = valid = None
+        g, H, C, slope = ctx.graph, ctx.H, ctx.C, ctx.slope
+        p_drop, pos_ratio = ctx.rng
+        lib = _lib.load()
+        N, dev = g.fwd.N, hfeat.device
+        gout = torch.zeros_like(out) if gout is None else gout.contiguous()
+        gl = None
+        if train:
+            gl = (torch.zeros((), device=dev) if g_loss is None else g_loss.to(torch.float64) / terms).to(
+                torch.float32).reshape(1).contiguous()
+        nodeq = torch.empty((N, H, 4), dtype=torch.float32, device=dev)
+        g_h = torch.empty_like(hfeat)
+        g_ar = torch.empty((N, H), dtype=torch.float32, device=dev)
+        g_al = torch.empty_like(g_ar)
+        ph, ldh = _lib.mat(hfeat, "hfeat")
+        po, ldo = _lib.mat(out, "out")
+        pg, ldg = _lib.mat(gout, "gout")
+        pgh, ldgh = _lib.mat(g_h, "g_hfeat")
+        split_ref, split, _scratch = _supergat_split(g.fwd, H, C, 1, dev)
+        with _Timed("supergat_bwd_dst"):
+            _lib.check(
+                lib.rgbx_supergat_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), ph, ldh, _lib.ptr(al),
+                                              _lib.ptr(ar), _lib.ptr(m), _lib.ptr(rden), po, ldo, _lib.ptr(b), pg, ldg,
+                                              _lib.ptr(nodeq), pgh, ldgh, _lib.ptr(g_ar), N, H, C, float(slope),
+                                              _lib.ptr(seed), p_drop, pos_ratio, _lib.ptr(gl), split_ref,
+                                              _lib.stream_ptr()), "rgbx_supergat_bwd_dst_f32")
+        split_ref, split, _scratch2 = _supergat_split(g.bwd, H, C, 1, dev)
+        with _Timed("supergat_bwd_src"):
+            _lib.check(
+                lib.rgbx_supergat_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
+                                              _lib.ptr(g.t2f) if train else None, ph, ldh, _lib.ptr(al), _lib.ptr(nodeq),
+                                              pg, ldg, pgh, ldgh, _lib.ptr(g_al), N, H, C, float(slope), _lib.ptr(seed),
+                                              p_drop, pos_ratio, _lib.ptr(gl), split_ref, _lib.stream_ptr()),
+                "rgbx_supergat_bwd_src_f32")
+        if train and neg.size(1):
+            with _Timed("supergat_neg_bwd"):
+                _lib.check(lib.rgbx_supergat_neg_loss_bwd_f32(ph, ldh, _lib.ptr(neg), _lib.ptr(valid), neg.size(1), H, C,
+                                                              _lib.ptr(gl), pgh, ldgh, _lib.stream_ptr()),
+                           "rgbx_supergat_neg_loss_bwd_f32")
+        n_scr = ctypes.c_int64(0)
+        _lib.check(lib.rgbx_gat_scores_bwd_scratch_floats(N, H, C, ctypes.byref(n_scr)),
+                   "rgbx_gat_scores_bwd_scratch_floats")
+        scratch = torch.empty(n_scr.value, dtype=torch.float32, device=dev)
+        g_att_l = torch.empty((H, C), dtype=torch.float32, device=dev)
+        g_att_r = torch.empty_like(g_att_l)
+        with _Timed("supergat_att_bwd"):  # g_att_l = sum_j g_al[j] h_j, g_att_r = sum_i g_ar[i] h_i, in workgroup order
+            _lib.check(
+                lib.rgbx_gat_scores_bwd_f32(ph, ldh, _lib.ptr(g_al), _lib.ptr(g_ar), N, _lib.ptr(al), _lib.ptr(ar), None,
+                                            0, _lib.ptr(g_att_l), _lib.ptr(g_att_r), _lib.ptr(scratch), n_scr.value, N, H,
+                                            C, _lib.stream_ptr()), "rgbx_gat_scores_bwd_f32")
+        g_b = gout.sum(0).reshape(ctx.bias_shape) if b is not None and ctx.needs_input_grad[7] else None
+        return (g_h, g_att_l.reshape(ctx.att_shapes[0]), g_att_r.reshape(ctx.att_shapes[1]), None, None, None, None, g_b,
+                None, None, None, None, None, None)
+
+
+def supergat_supported(H, C):
+    return bool(_lib.load().rgbx_supergat_supported(H, C))
+
+
+def supergat_attend(h, att_l, att_r, graph, H, C, slope=0.2, bias=None, training=False, p_drop=0.0, pos_ratio=1.0,
+                    neg_ratio=0.5, neg_edge_index=None, record=None):
+    """(out, att_loss) of one SuperGATConv with 'MX' attention on h = x W^T [N, H*C]. In training mode the layer draws
+    its attention dropout, its positive sample and (unless `neg_edge_index` int64 [2, n] is given) its negative pairs
+    from a seed taken from torch's device generator; `record` (a dict) receives that seed and the pairs, for
+    supergat_random_choices. att_loss is 0 outside training mode."""
+    if _is_dist(graph):
+        raise RuntimeError("SuperGATConv has no node-partitioned form: run it on one GPU")
+    if not supergat_supported(H, C):
+        raise RuntimeError(f"supergat_attend: {H} heads of {C} channels; pad the head width (SuperGATConv does)")
+    if neg_edge_index is not None and training:
+        if neg_edge_index.dtype != torch.int64 or neg_edge_index.dim() != 2 or neg_edge_index.size(0) != 2:
+            raise RuntimeError("neg_edge_index must be int64 [2, n]")
+        if neg_edge_index.numel() and (int(neg_edge_index.min()) < 0 or int(neg_edge_index.max()) >= graph.N):
+            raise RuntimeError(f"neg_edge_index values outside [0, {graph.N})")
+    return _SuperGATAttend.apply(h, att_l, att_r, graph, H, C, slope, bias, bool(training), p_drop, pos_ratio, neg_ratio,
+                                 neg_edge_index, record)
+
+
 def _scores_in_kernel(C):
     """Forming <h_j, att_src> from the gathered row costs log2(lanes per head) cross-lane adds per
     neighbour and saves the a_src[j] cache-line request. Measured at |V|=2M, |E|=60M: 4 lanes per head
