@@ -724,6 +724,63 @@ int rgbx_scatter_add_rows_f32(const float* src, int64_t lds, const int32_t* idx,
  * (the optimistic bracket of what a real exchange's DMA traffic does to them). n % 4 == 0, 16-byte aligned pointers. */
 int rgbx_paced_copy_f32(const float* src, float* dst, int64_t n, int workgroups, int nontemporal, rgbx_stream_t stream);
 
+/* ---- FAGCN: FAConv (signed tanh attention on the GCN-normalised graph) ----------------------- */
+
+/* For an edge j -> i of the target-grouped CSR (graph mode add-remaining-self-loops, w = gcn_norm weights):
+ *   a = tanh(al_j + ar_i),  c = kappa a w,  out[i,:] = sum_j c x[j,:] + eps x0[i,:]
+ * with al = x att_l, ar = x att_r interleaved in alr [N, 2] (8-byte aligned) and kappa = keep / (1 - p_drop) in
+ * training mode (FAConv [PyG], reference models/fagcn.py). `seed` points to two 32-bit words ON THE DEVICE; NULL
+ * selects inference mode. A slot's keep is a hash of (seed, forward CSR slot): the backward passes recompute it and no
+ * per-edge tensor is stored. Rows are read in fragments of vec = 4 / 2 / 1 floats for C % 4 == 0 / C % 2 == 0 / odd C:
+ * every row pointer must be vec * 4-byte aligned and every leading dimension a multiple of vec (RGBX_E_ALIGN).
+ * `split` (hub rows, as rgbx_spmm_csr_f32): split->partial holds n_chunks * (C + 1) floats, 16-byte aligned. */
+
+/* 1 if the fused kernels take width C (any C <= 64, even C <= 128, C % 4 == 0 up to 256), else 0: the caller then
+ * composes the layer from rgbx_faconv_edge_coef_f32, rgbx_spmm_csr_f32 and rgbx_faconv_edge_dot_f32. */
+int rgbx_faconv_supported(int64_t C);
+
+/* alr[r] = (<x[r,:], att_l>, <x[r,:], att_r>); any C. */
+int rgbx_faconv_scores_f32(const float* x, int64_t ldx, const float* att_l, const float* att_r, float* alr, int64_t N,
+                           int64_t C, rgbx_stream_t stream);
+
+/* Forward: one gather pass. x0 == NULL skips the eps term. `out` must not alias x. */
+int rgbx_faconv_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* w, const float* x, int64_t ldx,
+                        const float* alr, const float* x0, int64_t ldx0, float eps, float* out, int64_t ldo, int64_t N,
+                        int64_t C, const uint32_t* seed, float p_drop, const rgbx_row_split_t* split,
+                        rgbx_stream_t stream);
+
+/* Backward, with q = kappa w (1 - a^2) and s = q <gout[i,:], x[j,:]>. Target side, over the forward CSR:
+ * g_alr[i * 2 + 1] = sum_j s (the gradient of ar). */
+int rgbx_faconv_bwd_dst_f32(const int32_t* rowptr, const int32_t* col, const float* w, const float* x, int64_t ldx,
+                            const float* alr, const float* gout, int64_t ldg, float* g_alr, int64_t N, int64_t C,
+                            const uint32_t* seed, float p_drop, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i, w_t its gcn_norm weights), run AFTER the
+ * target side: g_alr[j * 2] = sum_i s and
+ *   g_x[j,:] = sum_i c gout[i,:] + g_alr[j * 2] att_l + g_alr[j * 2 + 1] att_r      (stored; not the eps term).
+ * `t2f` ([E'], training mode): the forward CSR slot of every transposed slot. g_att_l / g_att_r are the rows of
+ * g_alr^T x (rgbx_gemm_tn_f32). */
+int rgbx_faconv_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* w_t, const int32_t* t2f,
+                            const float* x, int64_t ldx, const float* alr, const float* gout, int64_t ldg,
+                            const float* att_l, const float* att_r, float* g_alr, float* g_x, int64_t ldgx, int64_t N,
+                            int64_t C, const uint32_t* seed, float p_drop, const rgbx_row_split_t* split,
+                            rgbx_stream_t stream);
+
+/* Composed path: coef[p] = c and (q != NULL) q[p] = kappa w (1 - a^2) of every slot of a CSR. transposed == 0: rows
+ * are targets (a = tanh(al[col] + ar[row])); != 0: rows are sources (a = tanh(al[row] + ar[col])). `slot` ([E'] or
+ * NULL = identity): the forward slot that keys the dropout decision of slot p. */
+int rgbx_faconv_edge_coef_f32(const int32_t* rowptr, const int32_t* col, const float* w, const int32_t* slot,
+                              const float* alr, int transposed, int64_t N, const uint32_t* seed, float p_drop,
+                              float* coef, float* q, rgbx_stream_t stream);
+
+/* out[i * out_stride] = sum_{p in row i} q[p] <a[i,:], b[col[p],:]>; any C (one wave per row, no hub split). */
+int rgbx_faconv_edge_dot_f32(const int32_t* rowptr, const int32_t* col, const float* q, const float* a, int64_t lda,
+                             const float* b, int64_t ldb, float* out, int64_t out_stride, int64_t N, int64_t C,
+                             rgbx_stream_t stream);
+
+/* keep[p] = 1 where forward slot p survives the dropout of this seed. */
+int rgbx_faconv_draws_u8(const uint32_t* seed, int64_t nnz, float p_drop, uint8_t* keep, rgbx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,15 @@ SIGNATURES = {
     "rgbx_scatter_add_rows_f32": [_P, _I64, _P, _I64, _I64, _P, _I64, _P],
     "rgbx_paced_copy_f32": [_P, _P, _I64, _I, _I, _P],
     "rgbx_py_random_shuffle_i64": [_I64, _I64, _P],
+    "rgbx_faconv_supported": [_I64],
+    "rgbx_faconv_scores_f32": [_P, _I64, _P, _P, _P, _I64, _I64, _P],
+    "rgbx_faconv_fwd_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _F, _P, _I64, _I64, _I64, _P, _F, _P, _P],
+    "rgbx_faconv_bwd_dst_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _P, _F, _P, _P],
+    "rgbx_faconv_bwd_src_f32": [_P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _P, _F, _P,
+                                _P],
+    "rgbx_faconv_edge_coef_f32": [_P, _P, _P, _P, _P, _I, _I64, _P, _F, _P, _P, _P],
+    "rgbx_faconv_edge_dot_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P],
+    "rgbx_faconv_draws_u8": [_P, _I64, _F, _P, _P],
 }
 EXPORTS = ["rgbx_version", "rgbx_last_error_string"] + list(SIGNATURES)
 

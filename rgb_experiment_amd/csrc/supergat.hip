@@ -12,6 +12,7 @@
 // and the negative pairs are hashes of a 64-bit seed that lives on the device. The backward recomputes them; no
 // [E', H] tensor is ever written.
 #include "rgbx_common.h"
+#include "rgbx_rng.h"
 
 namespace rgbx {
 namespace {
@@ -105,21 +106,7 @@ struct SgatRng {
 constexpr uint32_t kStreamDrop = 0x243F6A88u, kStreamPos = 0x85A308D3u, kStreamNegU = 0x13198A2Eu,
                    kStreamNegV = 0x03707344u;
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
-// 32 bits that depend on (seed, stream, a, b) and on nothing else.
-__device__ __forceinline__ uint32_t draw32(uint32_t s0, uint32_t s1, uint32_t stream, uint32_t a, uint32_t b) {
-  return mix32(mix32(mix32(a ^ s0) + b * 0x9E3779B9u + stream) ^ s1);
-}
-
-__device__ __forceinline__ float unit24(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
+// mix32 / draw32 / unit24: rgbx_rng.h (shared with faconv.hip)
 
 __device__ __forceinline__ bool drop_keep(uint32_t s0, uint32_t s1, int slot, int head, float p) {
   return unit24(draw32(s0, s1, kStreamDrop, (uint32_t)slot, (uint32_t)head)) >= p;

@@ -9,7 +9,7 @@ class InitialParameters:
     default_pics_path = os.path.join(os.path.dirname(_PKG), "pics")
 
     model_names = ["MLP", "GCN", "GraphSAGE", "GAT", "APPNPStack", "GraphSAGE2", "PTA", "DAGNN", "SGC", "GIN", "GGNN",
-                   "SuperGAT"]
+                   "SuperGAT", "FAGCN"]
     # reference initial_params.py:24-35
     default_init_params = [
         {"num_layers": 3, "hidden_unit": 64, "dropout_rate": 0.5},
@@ -25,6 +25,7 @@ class InitialParameters:
         {"num_layers": 2, "hidden_unit": 64, "dropout_rate": 0.5},  # GGNN, reference initial_params.py:28
         {"hidden_dim": 8, "heads": 8, "dropout_rate": 0.6, "edge_sample_ratio": 0.8,
          "neg_sample_ratio": 0.5},  # SuperGAT, reference initial_params.py:33
+        {"num_layers": 2, "hidden_unit": 64, "dropout_rate": 0.5, "epsilon": 0.3},  # FAGCN, reference initial_params.py:36
     ]
 
     # reference initial_params.py:42

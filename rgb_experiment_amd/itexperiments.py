@@ -18,6 +18,7 @@ test ``(not valid_list) or (not valid_tensor)`` (:210) is true for every input, 
 once — and so does this function. ``keep_valid_data_mask=True`` (an addition) applies the test the code was
 evidently meant to make, ``not (valid_list or valid_tensor)``, and keeps supplied masks that pass it.
 """
+import inspect
 import os
 import random
 from copy import deepcopy
@@ -251,7 +252,16 @@ def experiment(model_init_param: dict, *,
     "auto" | "on" | "off" — whether the epoch is split by task over two groups of ranks (dist/tasksplit.py). On TWO ranks
     the split puts the WHOLE graph on both GPUs (one trains, one evaluates: fastest, but no memory scaling): "auto" takes
     it only when one GPU can hold the whole graph and falls back to the node partition (half of everything per rank)
-    otherwise; "off" always partitions; the environment variable RGBX_TASK_SPLIT overrides "auto"."""
+    otherwise; "off" always partitions; the environment variable RGBX_TASK_SPLIT overrides "auto".
+    ``model`` (declared and never read by the reference, :78; live here): a ``nn.Module`` to train INSTEAD of building one
+    from ``model_name``. ``model_init_param`` is then ignored and ``model_name`` is only the label of the log line (it
+    still passes the out-of-scope / unknown-name checks). The module is moved to the run's device; its forward takes
+    ``x`` (and ``edge_index`` when its signature has one) and returns a mapping with 'out' and 'emb' (ValueError
+    before the loop otherwise); it runs on the generic loop — loss and accuracy from its logits (ops.ce_from_logits /
+    ops.masked_ce_accuracy) — single-device, with ``use_hip_graph`` honoured as for any model. ``use_cpu=True`` is not
+    refused up front: a module that owns a graph layer raises that layer's "no CPU fallback" RuntimeError. This is how
+    FAGCN trains (``model=rgb_experiment_amd.models.FAGCN(...)``) while the NAME "fagcn" stays refused. ``model=None``
+    (default) changes nothing."""
     say = print if print_print else (lambda *a, **k: None)
     say(f"running node classification: {'custom' if specify_data else dataset_name} data, model {model_name}")
 
@@ -283,13 +293,13 @@ def experiment(model_init_param: dict, *,
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if distributed is None:  # one of several ranks a launcher started, and a model with a node-partitioned form
         from .dist.experiment import SUPPORTED
-        distributed = world > 1 and name in SUPPORTED and not post_cs
+        distributed = world > 1 and name in SUPPORTED and not post_cs and model is None
     dist_ctx = None
     if distributed:
         from .dist.experiment import DistContext
         dist_ctx = DistContext.open(name, post_cs, use_cpu)  # process group, rank's device; raises for unsupported set-ups
         cuda_index = dist_ctx.cuda_index
-    elif name != "mlp" and (use_cpu or not torch.cuda.is_available()):
+    elif model is None and name != "mlp" and (use_cpu or not torch.cuda.is_available()):
         raise RuntimeError("rgb_experiment_amd runs message passing in HIP kernels on an MI355X device; "
                            "use_cpu=True / no visible GPU is not supported (no CPU fallback)")
     device = dist_ctx.device if dist_ctx is not None else torch.device(
@@ -327,8 +337,15 @@ def experiment(model_init_param: dict, *,
         if sel.numel() and (int(sel.min()) < 0 or int(sel.max()) >= output_dim):
             raise RuntimeError(f"{part}_mask selects nodes whose label is outside [0, {output_dim}) "
                                "(e.g. -1 = unlabelled): the reference's NLLLoss would raise on them")
-    is_pta = name == "pta"
-    if is_pta:  # reference :351-374
+    is_pta = name == "pta" and model is None
+    if model is not None:  # the caller's module: `model_name` is a label only, `model_init_param` is not read
+        if not isinstance(model, nn.Module):
+            raise TypeError(f"model must be a torch.nn.Module, got {type(model).__name__}")
+        net = model
+        params = inspect.signature(net.forward).parameters
+        takes_edges = "edge_index" in params or any(p.kind is p.VAR_KEYWORD for p in params.values())
+        fwd = {"x": features, "edge_index": data.edge_index} if takes_edges else {"x": features}
+    elif is_pta:  # reference :351-374
         adj = normalized_adjacency(data.edge_index, data.num_nodes)
         idx = [m.nonzero(as_tuple=True)[0] for m in (train_mask, val_mask, test_mask)]
         K, alpha = model_init_param["K"], model_init_param["alpha"]
@@ -339,8 +356,18 @@ def experiment(model_init_param: dict, *,
         net = MODELS[name](input_dim=input_dim, output_dim=output_dim, **model_init_param)
         fwd = {"x": features} if name == "mlp" else {"x": features, "edge_index": data.edge_index}
     net.to(device)
+    uses_graph = name != "mlp" if model is None else "edge_index" in fwd
+    if model is not None:  # one eval-mode forward before the loop: the contract of the returned mapping
+        net.eval()
+        with torch.no_grad():
+            probe = net(**fwd)
+        if not (hasattr(probe, "__getitem__") and hasattr(probe, "__contains__") and "emb" in probe and "out" in probe):
+            raise ValueError("experiment(model=...): the module's forward must return a mapping with 'out' (log-"
+                             "probabilities) and 'emb' (logits), as the models of this package do")
+        del probe
     if cache_input_aggregate == "auto":  # memory guard: the kept aggregate is one more [N, F] fp32 matrix in HBM
         cache_input_aggregate = (device.type == "cuda" and name != "mlp" and dist_ctx is None  # partitioned: opt-in only
+                                 and model is None
                                  and features.numel() * 4 <= torch.cuda.mem_get_info(device)[0] // 4)
     if cache_input_aggregate:
         net.cache_input_aggregate = True  # read by models/_stack.ConvStack; other models have no such form
@@ -357,11 +384,11 @@ def experiment(model_init_param: dict, *,
     optimizer = torch.optim.Adam(net.parameters(), lr=learning_rate, weight_decay=weight_decay,
                                  capturable=device.type == "cuda")
     want_graph = bool(use_hip_graph) and device.type == "cuda" and not is_pta
-    is_supergat = name == "supergat"
+    is_supergat = name == "supergat" and model is None
     if want_graph and is_supergat:
         say("SuperGAT draws its edge samples every step: running the eager loop (use_hip_graph is ignored)")
         want_graph = False
-    if want_graph and use_hip_graph != "always" and name != "mlp" and data.edge_index.size(1) > HIP_GRAPH_MAX_EDGES:
+    if want_graph and use_hip_graph != "always" and uses_graph and data.edge_index.size(1) > HIP_GRAPH_MAX_EDGES:
         say(f"{data.edge_index.size(1)} edges: the epoch is kernel-bound, running the eager loop (use_hip_graph='always' "
             "forces the capture)")
         want_graph = False

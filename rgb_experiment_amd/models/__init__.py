@@ -1,5 +1,8 @@
 """Model registry (reference models/__init__.py:1-13): the hot-path models plus the "next" rows of
-SURVEY §8f that reuse the same kernels (DAGNN, PTA, SGC, GIN), GGNN and SuperGAT. FAGCN is out of scope."""
+SURVEY §8f that reuse the same kernels (DAGNN, PTA, SGC, GIN), GGNN and SuperGAT. FAGCN is exported as a class and
+trained through ``experiment(..., model=FAGCN(...))``: two host tests pin that the NAME "fagcn" is refused, so it is in
+neither REGISTRY nor MODELS (entering it there, and dropping it from itexperiments._OUT_OF_SCOPE, is the one-line change
+left for when those tests may move)."""
 from .mlp import MLP
 from .gcn import GCN
 from .graphsage import GraphSAGE
@@ -12,6 +15,7 @@ from .sgc import SGC
 from .gin import GIN
 from .ggnn import GGNN
 from .supergat import SuperGAT
+from .fagcn import FAGCN
 
 REGISTRY = {
     "mlp": MLP,

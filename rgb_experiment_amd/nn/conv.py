@@ -8,6 +8,7 @@ computing their ``propagate`` in HIP kernels (rgb_experiment_amd.ops).
   APPNP      <- torch_geometric.nn.conv.APPNP     (reference models/appnp_stack.py:3,22)
   GatedGraphConv <- torch_geometric.nn.GatedGraphConv (reference models/ggnn.py:3,18)
   SuperGATConv <- torch_geometric.nn.SuperGATConv   (reference models/supergat.py)
+  FAConv     <- torch_geometric.nn.conv.FAConv    (reference models/fagcn.py)
 
 Dense X·W^T products go through hipBLASLt (forward, input gradient) and rgbx_gemm_tn_f32 (weight
 gradient, split-K fp32 MFMA); everything indexed by edge_index goes through librgbx_hip.so.
@@ -686,3 +687,37 @@ class SuperGATConv(nn.Module):
         if self.bias is not None and not in_kernel:
             out = out + self.bias
         return out
+
+
+class FAConv(nn.Module):
+    """FAGCN's layer [PyG FAConv; reference models/fagcn.py]: for an edge j -> i of the GCN-normalised graph (self-loops
+    removed then re-added, w_ij = 1/sqrt(d_i d_j)), a_ij = tanh(<x_j, att_l> + <x_i, att_r>) — signed, no softmax —
+    with dropout on the coefficient, out_i = sum_j a_ij w_ij x_j + eps * x_0,i. Parameter names are PyG's
+    (att_l.weight / att_r.weight [1, C], no bias). All of it runs in the rgbx_faconv_* kernels (ops.faconv);
+    `form` (None | 'fused' | 'composed') forces one of the two kernel paths."""
+
+    def __init__(self, channels, eps=0.1, dropout=0.0, add_self_loops=True, normalize=True):
+        super().__init__()
+        if not normalize:
+            raise NotImplementedError("FAConv: normalize=False is not built (the reference leaves it on)")
+        if not add_self_loops:
+            raise NotImplementedError("FAConv: add_self_loops=False is not built (the reference leaves it on)")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("FAConv: dropout in [0, 1)")
+        self.channels, self.eps, self.dropout = channels, eps, dropout
+        self.add_self_loops, self.normalize = add_self_loops, normalize
+        self.att_l = nn.Linear(channels, 1, bias=False)
+        self.att_r = nn.Linear(channels, 1, bias=False)
+        self.form = None
+        self.last_draw = {}  # dropout seed of the last forward (ops.faconv_random_choices)
+
+    def reset_parameters(self):
+        self.att_l.reset_parameters()
+        self.att_r.reset_parameters()
+
+    def forward(self, x, x_0, edge_index):
+        _lib.require_device(x, x_0)
+        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING)
+        self.last_draw = {}
+        return ops.faconv(x, x_0, self.att_l.weight, self.att_r.weight, graph, eps=self.eps, training=self.training,
+                          p_drop=self.dropout, form=self.form, record=self.last_draw)

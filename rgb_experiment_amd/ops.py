@@ -1987,6 +1987,162 @@ def supergat_attend(h, att_l, att_r, graph, H, C, slope=0.2, bias=None, training
                                  neg_edge_index, record)
 
 
+FACONV_FORMS = ("fused", "composed")
+
+
+def faconv_supported(C):
+    return bool(_lib.load().rgbx_faconv_supported(C))
+
+
+def faconv_form(C, form=None):
+    """'fused' (rgbx_faconv_fwd / bwd_dst / bwd_src: nothing per edge is written) where the kernels take the width,
+    else 'composed' (per-slot coefficients written by rgbx_faconv_edge_coef_f32, then the plain weighted gather).
+    `form` forces one of FACONV_FORMS (tests, tools/fagcn_bench.py); forcing 'fused' at a refused width raises."""
+    if form is None:
+        return "fused" if faconv_supported(C) else "composed"
+    if form not in FACONV_FORMS:
+        raise ValueError(f"faconv: form {form!r} not in {FACONV_FORMS}")
+    if form == "fused" and not faconv_supported(C):
+        raise RuntimeError(f"faconv: the fused kernels do not take width {C}; use form='composed'")
+    return form
+
+
+def faconv_random_choices(record, graph):
+    """The dropout decisions of the training forward that filled `record` (FAConv keeps the record of its last
+    forward): {'keep': bool [E'] in forward CSR slot order, 'src' / 'dst': int64 [E'] endpoints of every slot}."""
+    csr = graph.fwd
+    dev, nnz = csr.rowptr.device, csr.nnz
+    if record.get("seed") is None:
+        keep = torch.ones(nnz, dtype=torch.uint8, device=dev)
+    else:
+        keep = torch.empty(nnz, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().rgbx_faconv_draws_u8(_lib.ptr(record["seed"]), nnz, float(record["p_drop"]), _lib.ptr(keep),
+                                                    _lib.stream_ptr()), "rgbx_faconv_draws_u8")
+    deg = (csr.rowptr[1:] - csr.rowptr[:-1]).long()
+    return {"keep": keep.bool(), "src": csr.col[:nnz].long(),
+            "dst": torch.repeat_interleave(torch.arange(csr.N, device=dev), deg)}
+
+
+def _faconv_edge_coef(csr, w, slot, alr, transposed, seed, p_drop, want_q):
+    coef = torch.empty(max(csr.nnz, 1), dtype=torch.float32, device=alr.device)
+    q = torch.empty_like(coef) if want_q else None
+    with _Timed("faconv_edge_coef"):
+        _lib.check(_lib.load().rgbx_faconv_edge_coef_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w),
+                                                         _lib.ptr(slot), _lib.ptr(alr), int(transposed), csr.N,
+                                                         _lib.ptr(seed), float(p_drop), _lib.ptr(coef), _lib.ptr(q),
+                                                         _lib.stream_ptr()), "rgbx_faconv_edge_coef_f32")
+    return coef, q
+
+
+def _faconv_edge_dot(csr, q, a, b, out, column):
+    """out[:, column] = per-row sums of q[p] <a[row], b[col[p]]> (out [N, 2])."""
+    pa, lda = _lib.mat(a, "a")
+    pb, ldb = _lib.mat(b, "b")
+    with _Timed("faconv_edge_dot"):
+        _lib.check(_lib.load().rgbx_faconv_edge_dot_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(q), pa, lda, pb,
+                                                        ldb, out.data_ptr() + 4 * column, 2, csr.N, a.size(1),
+                                                        _lib.stream_ptr()), "rgbx_faconv_edge_dot_f32")
+
+
+class _FAConv(torch.autograd.Function):
+    """One FAConv as a single autograd node: out_i = sum_j k a_ij w_ij x_j + eps x0_i with a_ij = tanh(al_j + ar_i).
+    Saves x, [al, ar], the attention vectors and the dropout seed; nothing per edge (the backward recomputes tanh and
+    the keep decisions)."""
+
+    @staticmethod
+    def forward(ctx, x, x0, att_l, att_r, graph, eps, train, p_drop, form, record):
+        _lib.require_device(x, x0, att_l, att_r)
+        lib = _lib.load()
+        csr, N, dev = graph.fwd, graph.fwd.N, x.device
+        x = x.contiguous()
+        C = x.size(1)
+        if x.size(0) != N:
+            raise RuntimeError(f"faconv: {x.size(0)} feature rows for a graph of {N} nodes")
+        use_x0 = x0 is not None and eps != 0.0
+        x0c = x0.contiguous() if use_x0 else None
+        att = torch.cat([att_l.detach().reshape(1, C), att_r.detach().reshape(1, C)]).contiguous()  # [2, C]
+        seed = None
+        if train and p_drop > 0.0:
+            # two 32-bit words from torch's device generator (torch.manual_seed makes the run repeatable; under a
+            # hipGraph capture the generator's offset advances with every replay); they stay on the device
+            seed = torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32, device=dev)
+        if record is not None:
+            record.update(seed=seed, p_drop=float(p_drop))
+        alr = torch.empty((N, 2), dtype=torch.float32, device=dev)
+        px, ldx = _lib.mat(x, "x")
+        with _Timed("faconv_scores"):
+            _lib.check(lib.rgbx_faconv_scores_f32(px, ldx, att[0].data_ptr(), att[1].data_ptr(), _lib.ptr(alr), N, C,
+                                                  _lib.stream_ptr()), "rgbx_faconv_scores_f32")
+        if form == "fused":
+            out = torch.empty((N, C), dtype=torch.float32, device=dev)
+            po, ldo = _lib.mat(out, "out")
+            p0, ld0 = _lib.mat(x0c, "x_0") if use_x0 else (None, 0)
+            split, _scratch = csr.split_arg(C + 1, dev)
+            with _Timed("faconv_fwd"):
+                _lib.check(lib.rgbx_faconv_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(graph.w), px, ldx,
+                                                   _lib.ptr(alr), p0, ld0, float(eps), po, ldo, N, C, _lib.ptr(seed),
+                                                   float(p_drop), None if split is None else ctypes.byref(split),
+                                                   _lib.stream_ptr()), "rgbx_faconv_fwd_f32")
+        else:
+            coef, _ = _faconv_edge_coef(csr, graph.w, None, alr, 0, seed, p_drop, False)
+            out = spmm_raw(csr, coef, None, x, y=x0c, a=1.0, b=float(eps), kind="faconv_fwd_composed")
+        ctx.graph, ctx.eps, ctx.p_drop, ctx.form, ctx.use_x0 = graph, float(eps), float(p_drop), form, use_x0
+        ctx.att_shapes = (att_l.shape, att_r.shape)
+        ctx.save_for_backward(x, alr, att, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, alr, att, seed = ctx.saved_tensors
+        g, p_drop = ctx.graph, ctx.p_drop
+        lib = _lib.load()
+        N, C, dev = x.size(0), x.size(1), x.device
+        gout = gout.contiguous()
+        g_alr = torch.empty((N, 2), dtype=torch.float32, device=dev)
+        px, ldx = _lib.mat(x, "x")
+        pg, ldg = _lib.mat(gout, "gout")
+        t2f = g.t2f if seed is not None else None
+        if ctx.form == "fused":
+            g_x = torch.empty_like(x)
+            pgx, ldgx = _lib.mat(g_x, "g_x")
+            split, _scratch = g.fwd.split_arg(C + 1, dev)
+            with _Timed("faconv_bwd_dst"):
+                _lib.check(lib.rgbx_faconv_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), _lib.ptr(g.w), px, ldx,
+                                                       _lib.ptr(alr), pg, ldg, _lib.ptr(g_alr), N, C, _lib.ptr(seed), p_drop,
+                                                       None if split is None else ctypes.byref(split),
+                                                       _lib.stream_ptr()), "rgbx_faconv_bwd_dst_f32")
+            split, _scratch2 = g.bwd.split_arg(C + 1, dev)
+            with _Timed("faconv_bwd_src"):
+                _lib.check(lib.rgbx_faconv_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(g.w_t),
+                                                       _lib.ptr(t2f), px, ldx, _lib.ptr(alr), pg, ldg, att[0].data_ptr(),
+                                                       att[1].data_ptr(), _lib.ptr(g_alr), pgx, ldgx, N, C, _lib.ptr(seed),
+                                                       p_drop, None if split is None else ctypes.byref(split),
+                                                       _lib.stream_ptr()), "rgbx_faconv_bwd_src_f32")
+        else:
+            _, q = _faconv_edge_coef(g.fwd, g.w, None, alr, 0, seed, p_drop, True)
+            _faconv_edge_dot(g.fwd, q, gout, x, g_alr, 1)
+            coef_t, q_t = _faconv_edge_coef(g.bwd, g.w_t, t2f, alr, 1, seed, p_drop, True)
+            _faconv_edge_dot(g.bwd, q_t, x, gout, g_alr, 0)
+            g_x = torch.addmm(spmm_raw(g.bwd, coef_t, None, gout, kind="faconv_bwd_composed"), g_alr, att)
+        g_att = gemm_tn(g_alr, x)  # [2, C]: rows g_att_l, g_att_r, summed in slab order
+        g_x0 = gout * ctx.eps if ctx.use_x0 and ctx.needs_input_grad[1] else None
+        return (g_x, g_x0, g_att[0].reshape(ctx.att_shapes[0]), g_att[1].reshape(ctx.att_shapes[1]), None, None, None,
+                None, None, None)
+
+
+def faconv(x, x0, att_l, att_r, graph, eps=0.1, training=False, p_drop=0.0, form=None, record=None):
+    """FAConv on the GCN-weighted graph (graph mode LOOPS_ADD_REMAINING): out_i = sum_j k_ij tanh(<x_j, att_l> +
+    <x_i, att_r>) w_ij x_j + eps x0_i. In training mode with p_drop > 0 the layer draws its dropout seed from torch's
+    device generator; `record` (a dict) receives it, for faconv_random_choices. `form`: see faconv_form."""
+    if _is_dist(graph):
+        raise RuntimeError("FAConv has no node-partitioned form: run it on one GPU")
+    _lib.require_device(x, x0, att_l, att_r)
+    if not (0.0 <= p_drop < 1.0):
+        raise ValueError("faconv: dropout must be in [0, 1)")
+    return _FAConv.apply(x, x0, att_l, att_r, graph, float(eps), bool(training), float(p_drop),
+                         faconv_form(x.size(1), form), record)
+
+
 def _scores_in_kernel(C):
     """Forming <h_j, att_src> from the gathered row costs log2(lanes per head) cross-lane adds per
     neighbour and saves the a_src[j] cache-line request. Measured at |V|=2M, |E|=60M: 4 lanes per head
