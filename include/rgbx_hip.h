@@ -12,6 +12,10 @@
  *                         models/appnp_stack.py:29), restated in-repo by models/dagnn.py:20-24.
  *   rgbx_gcn_norm_f32     gcn_norm, models/dagnn.py:12-31 (degree over the target index,
  *                         deg^-1/2 with inf -> 0, w = dis[src] * dis[tgt]).
+ *   rgbx_loop_weights_f32 / rgbx_edge_slot_weights_f32 / rgbx_weighted_deg_inv_sqrt_f32 / rgbx_gcn_norm_weighted_f32 /
+ *   rgbx_edge_dot_f32 / rgbx_gcn_norm_bwd_f32
+ *                         the same gcn_norm with its edge_weight argument given (models/dagnn.py:12-31), and its
+ *                         gradient in the weights.
  *   rgbx_inv_degree_f32   the 1/max(count,1) of aggr='mean' (models/graphsage.py:39,58) [PyG].
  *   rgbx_spmm_csr_f32     MessagePassing.propagate with aggr='add' / 'mean' and message
  *                         norm * x_j (models/dagnn.py:34-36,46,57-59; models/graphsage.py:58).
@@ -109,6 +113,46 @@ int rgbx_gcn_norm_f32(const int32_t* rowptr, const int32_t* col, int64_t N, cons
 /* inv[i] = 1 / max(rowptr[i+1]-rowptr[i], 1) — the divisor of aggr='mean'. */
 int rgbx_inv_degree_f32(const int32_t* rowptr, int64_t N, float* inv, rgbx_stream_t stream);
 
+/* ---- weighted graphs: gcn_norm(edge_index, edge_weight, ...) of models/dagnn.py:12-31 with the weight present ------- */
+
+/* Weight of the self-loop every node gets from the rewrite (models/dagnn.py:20-24 -> add_remaining_self_loops, fill 1):
+ *   RGBX_LOOPS_ADD_REMAINING: loop_w[i] = ew[e] of node i's input self-loop e, `fill` if it has none; of several input
+ *     self-loops the one with the HIGHEST edge id supplies the weight (an integer atomic max over edge ids, then a read: the
+ *     same answer in every run). loop_src[i] = that edge id, -1 where the loop was filled in.
+ *   RGBX_LOOPS_REMOVE_ADD: loop_w[i] = fill, loop_src[i] = -1 for every node.
+ * src / dst = edge_index[0] / edge_index[1] (int64 [E]); loop_w f32 [N], loop_src int32 [N].
+ * RGBX_LOOPS_KEEP adds no loops: RGBX_E_ARG. */
+int rgbx_loop_weights_f32(const int64_t* src, const int64_t* dst, const float* ew, int64_t E, int64_t N, int loops_mode,
+                          float fill, float* loop_w, int32_t* loop_src, rgbx_stream_t stream);
+
+/* ew_slot[p] = perm[p] < E ? ew[perm[p]] : loop_w[perm[p] - E] for the nnz slots of a CSR from rgbx_csr_build (forward
+ * or transposed; loop_w may be NULL when nnz <= E, i.e. RGBX_LOOPS_KEEP). */
+int rgbx_edge_slot_weights_f32(const int32_t* perm, int64_t nnz, const float* ew, int64_t E, const float* loop_w,
+                               float* ew_slot, rgbx_stream_t stream);
+
+/* deg[i] = sum of ew_slot over row i of the FORWARD CSR (rows of any length; fixed summation order: bitwise reproducible),
+ * dis[i] = deg[i]^-1/2 with inf -> 0 (models/dagnn.py:25-30). Not clamped: deg = 0 gives 0, a negative sum gives NaN. */
+int rgbx_weighted_deg_inv_sqrt_f32(const int32_t* rowptr, const float* ew_slot, int64_t N, float* dis,
+                                   rgbx_stream_t stream);
+
+/* w[p] = dis[col[p]] * ew_slot[p] * dis[i] for every slot p of row i (models/dagnn.py:31); either CSR with its own
+ * ew_slot, `dis` from the forward one. Unit weights give rgbx_gcn_norm_f32's bits. */
+int rgbx_gcn_norm_weighted_f32(const int32_t* rowptr, const int32_t* col, const float* ew_slot, int64_t N,
+                               const float* dis, float* w, rgbx_stream_t stream);
+
+/* Backward of the weighted normalisation (models/dagnn.py:12-31 differentiated in edge_weight). g = dL/dw per FORWARD
+ * slot, ew_slot the forward slot weights, dis from rgbx_weighted_deg_inv_sqrt_f32. With w_p = dis[j] ew_p dis[i]:
+ *   dL/dew_p = g_p dis[j] dis[i] + ddeg[i],  ddeg[k] = -1/2 deg[k]^-3/2 ddis[k],
+ *   ddis[k]  = sum_{p: tgt = k} g_p ew_p dis[src] + sum_{p: src = k} g_p ew_p dis[tgt]
+ * (first sum over forward row k, second over transposed row k through t2f[q] = forward slot of transposed slot q; both
+ * row-wise in a fixed order, no float atomics). dew [E] receives dL/dew of every input edge: a slot's gradient goes to
+ * edge perm[p]; that of an added loop E + i goes to loop_src[i] (the input self-loop that supplied its weight), nowhere
+ * when loop_src[i] < 0 or loop_src == NULL; input self-loops that the rewrite dropped get 0. ddeg: f32 [N] scratch. */
+int rgbx_gcn_norm_bwd_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm, const int32_t* rowptr_t,
+                          const int32_t* col_t, const int32_t* t2f, const int32_t* loop_src, const float* g,
+                          const float* ew_slot, const float* dis, int64_t N, int64_t E, float* ddeg, float* dew,
+                          rgbx_stream_t stream);
+
 /* ---- aggregation ------------------------------------------------------------------------- */
 
 /* Optional plan for rows with very many slots (hub nodes). Rows with more than `threshold` slots are
@@ -138,6 +182,16 @@ int rgbx_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* w,
                       const float* x, int64_t ldx, const float* y, int64_t ldy, const float* bias,
                       float* out, int64_t ldo, int64_t N, int64_t d, float a, float b,
                       const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* g[p] = sum_c a[i,c] * b[col[p],c] for every slot p of row i: dL/dw of the aggregation out = sum_p w[p] x[col[p],:]
+ * (message norm * x_j, models/dagnn.py:57-59, norm from models/dagnn.py:12-31) with a = dL/dout and b = x. One wave per
+ * row, the gather's lane layout; every g[p] is written once with plain stores. d % 4 == 0, 4 <= d <= 256
+ * (rgbx_edge_dot_supported; other widths: zero-pad, or cut into column blocks and add); a, b 16-byte aligned with leading
+ * dimensions % 4 == 0. `split`: rows above split->threshold are cut into the plan's chunks, one wave each (needs
+ * chunk_begin / chunk_end / chunk_row; `partial` is not used). */
+int rgbx_edge_dot_supported(int64_t d);
+int rgbx_edge_dot_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t lda, const float* b, int64_t ldb,
+                      float* g, int64_t N, int64_t d, const rgbx_row_split_t* split, rgbx_stream_t stream);
 
 /* rgbx_spmm_csr_f32 with an epilogue over the finished output rows, for layers that transform BEFORE they aggregate
  * (in > out — every default configuration of the reference, initial_params.py:25-29: F -> 64 -> C with C = 7, 6, 3, 40 ...),

@@ -56,6 +56,13 @@ SIGNATURES = {
     "rgbx_deg_inv_sqrt_f32": [_P, _I64, _P, _P],
     "rgbx_gcn_norm_f32": [_P, _P, _I64, _P, _P, _P],
     "rgbx_inv_degree_f32": [_P, _I64, _P, _P],
+    "rgbx_loop_weights_f32": [_P, _P, _P, _I64, _I64, _I, _F, _P, _P, _P],
+    "rgbx_edge_slot_weights_f32": [_P, _I64, _P, _I64, _P, _P, _P],
+    "rgbx_weighted_deg_inv_sqrt_f32": [_P, _P, _I64, _P, _P],
+    "rgbx_gcn_norm_weighted_f32": [_P, _P, _P, _I64, _P, _P, _P],
+    "rgbx_edge_dot_supported": [_I64],
+    "rgbx_edge_dot_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P],
+    "rgbx_gcn_norm_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P],
     "rgbx_spmm_csr_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P],
     "rgbx_spmm_csr_epilogue_supported": [_I64],
     "rgbx_spmm_csr_epilogue_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P],

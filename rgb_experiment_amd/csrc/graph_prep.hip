@@ -89,6 +89,129 @@ gcn_norm_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, int
   }
 }
 
+// ---- weighted graphs: gcn_norm(edge_index, edge_weight) of models/dagnn.py:12-31 with the weight present ----------
+
+__global__ void __launch_bounds__(256) fill_i32_kernel(int* __restrict__ v, int64_t n, int value) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    v[i] = value;
+}
+
+// The input self-loop that supplies node i's loop weight: the one with the HIGHEST edge id (the CPU assignment
+// loop_w[row[~keep]] = edge_weight[~keep] of add_remaining_self_loops leaves the last one standing). An integer max
+// has one answer whatever the order of the threads.
+__global__ void __launch_bounds__(256)
+loop_source_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int64_t E,
+                   int* __restrict__ loop_src) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = dst[e];
+    if (src[e] == t) atomicMax(loop_src + t, (int)e);
+  }
+}
+
+__global__ void __launch_bounds__(256)
+loop_weight_kernel(const int* __restrict__ loop_src, const float* __restrict__ ew, int N, float fill,
+                   float* __restrict__ loop_w) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
+    const int e = loop_src[i];
+    loop_w[i] = e >= 0 ? ew[e] : fill;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+slot_weight_kernel(const int* __restrict__ perm, int64_t nnz, const float* __restrict__ ew, int64_t E,
+                   const float* __restrict__ loop_w, float* __restrict__ ew_slot) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += (int64_t)gridDim.x * blockDim.x) {
+    const int id = perm[p];
+    ew_slot[p] = id < E ? ew[id] : loop_w[id - E];
+  }
+}
+
+// Fixed-order sum of v over the wave: lane l adds its strided elements in slot order, then a butterfly.
+__device__ __forceinline__ float wave_sum_fixed(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// One wave per row (any length: a hub row is one long strided loop, this runs once per graph):
+// deg = sum of the row's slot weights, dis = deg^-1/2 with inf -> 0 (dagnn.py:25-30). Not clamped: a negative sum gives NaN.
+__global__ void __launch_bounds__(256)
+weighted_deg_inv_sqrt_kernel(const int* __restrict__ rowptr, const float* __restrict__ ew_slot, int N,
+                             float* __restrict__ dis) {
+  const int lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < N; row += gridDim.x * wpb) {
+    const int s = rowptr[row], e = rowptr[row + 1];
+    float acc = 0.f;
+    for (int p = s + lane; p < e; p += 64) acc += ew_slot[p];
+    const float deg = wave_sum_fixed(acc);
+    if (lane == 0) dis[row] = deg == 0.f ? 0.f : 1.0f / sqrtf(deg);
+  }
+}
+
+// w = (dis[src] * ew) * dis[tgt], dagnn.py:31.
+__global__ void __launch_bounds__(256)
+gcn_norm_weighted_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                         const float* __restrict__ ew_slot, int N, const float* __restrict__ dis,
+                         float* __restrict__ w) {
+  const int lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < N; row += gridDim.x * wpb) {
+    const int s = rowptr[row], e = rowptr[row + 1];
+    const float di = dis[row];
+    for (int p = s + lane; p < e; p += 64) w[p] = dis[col[p]] * ew_slot[p] * di;
+  }
+}
+
+// Backward of the normalisation, first half: with w_p = dis[j] ew_p dis[i] and g = dL/dw,
+//   ddis[k] = sum_{p: tgt = k} g_p ew_p dis[src_p] + sum_{p: src = k} g_p ew_p dis[tgt_p]
+// (first sum over the forward row k, second over the transposed row k, whose slots name their forward slot in t2f),
+//   ddeg[k] = -1/2 deg[k]^-3/2 ddis[k] = -1/2 dis[k]^3 ddis[k]   (dis = 0 where inf was masked: no gradient there).
+// One wave per row, both sums in a fixed order.
+__global__ void __launch_bounds__(256)
+gcn_norm_bwd_deg_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                        const int* __restrict__ rowptr_t, const int* __restrict__ col_t,
+                        const int* __restrict__ t2f, const float* __restrict__ g,
+                        const float* __restrict__ ew_slot, const float* __restrict__ dis, int N,
+                        float* __restrict__ ddeg) {
+  const int lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < N; row += gridDim.x * wpb) {
+    float acc = 0.f;
+    for (int p = rowptr[row] + lane; p < rowptr[row + 1]; p += 64) acc = fmaf(g[p] * ew_slot[p], dis[col[p]], acc);
+    float acc_t = 0.f;
+    for (int q = rowptr_t[row] + lane; q < rowptr_t[row + 1]; q += 64) {
+      const int p = t2f[q];
+      acc_t = fmaf(g[p] * ew_slot[p], dis[col_t[q]], acc_t);
+    }
+    const float ddis = wave_sum_fixed(acc) + wave_sum_fixed(acc_t);
+    const float di = dis[row];
+    if (lane == 0) ddeg[row] = -0.5f * di * di * di * ddis;
+  }
+}
+
+// Second half: dL/dew of slot p of row i = g_p dis[j] dis[i] + ddeg[i] (deg[i] sums the row's slot weights), sent to the
+// input edge behind the slot: perm[p] < E is that edge; an added loop E + i goes to the input self-loop that supplied its
+// weight (loop_src[i]), or nowhere when the loop was filled in. Every edge is written at most once (dew is zeroed first:
+// removed self-loops that lost, or were dropped, take no part in the output).
+__global__ void __launch_bounds__(256)
+gcn_norm_bwd_edge_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                         const int* __restrict__ perm, const int* __restrict__ loop_src,
+                         const float* __restrict__ g, const float* __restrict__ dis,
+                         const float* __restrict__ ddeg, int N, int64_t E, float* __restrict__ dew) {
+  const int lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < N; row += gridDim.x * wpb) {
+    const int s = rowptr[row], e = rowptr[row + 1];
+    const float di = dis[row], dd = ddeg[row];
+    for (int p = s + lane; p < e; p += 64) {
+      int id = perm[p];
+      if (id >= E) id = loop_src ? loop_src[id - E] : -1;
+      if (id >= 0) dew[id] = fmaf(g[p] * dis[col[p]], di, dd);
+    }
+  }
+}
+
 int sort_bits(int64_t N) {
   int b = 1;
   while (((int64_t)1 << b) <= N) ++b;  // keys lie in [0, N]
@@ -188,5 +311,76 @@ extern "C" int rgbx_gcn_norm_f32(const int32_t* rowptr, const int32_t* col, int6
   if (N == 0) return RGBX_OK;
   gcn_norm_kernel<<<grid_for(N, 4), 256, 0, (hipStream_t)stream>>>(rowptr, col, (int)N, dis, w);
   RGBX_CHECK_LAUNCH("gcn_norm_kernel");
+  return RGBX_OK;
+}
+
+extern "C" int rgbx_loop_weights_f32(const int64_t* src, const int64_t* dst, const float* ew, int64_t E,
+                                     int64_t N, int loops_mode, float fill, float* loop_w,
+                                     int32_t* loop_src, rgbx_stream_t stream) {
+  if (E < 0 || N < 0 || (E > 0 && (!src || !dst || !ew)) || (N > 0 && (!loop_w || !loop_src)))
+    return fail(RGBX_E_ARG, "loop_weights: null pointer or negative size");
+  if (loops_mode != RGBX_LOOPS_ADD_REMAINING && loops_mode != RGBX_LOOPS_REMOVE_ADD)
+    return fail(RGBX_E_ARG, "loop_weights: loops_mode %d adds no loops", loops_mode);
+  if (E >= INT32_MAX || N >= INT32_MAX) return fail(RGBX_E_RANGE, "loop_weights: E or N exceeds int32");
+  if (N == 0) return RGBX_OK;
+  hipStream_t s = (hipStream_t)stream;
+  fill_i32_kernel<<<grid_for(N), 256, 0, s>>>(loop_src, N, -1);
+  RGBX_CHECK_LAUNCH("fill_i32_kernel");
+  if (loops_mode == RGBX_LOOPS_ADD_REMAINING && E > 0) {
+    loop_source_kernel<<<grid_for(E), 256, 0, s>>>(src, dst, E, loop_src);
+    RGBX_CHECK_LAUNCH("loop_source_kernel");
+  }
+  loop_weight_kernel<<<grid_for(N), 256, 0, s>>>(loop_src, ew, (int)N, fill, loop_w);
+  RGBX_CHECK_LAUNCH("loop_weight_kernel");
+  return RGBX_OK;
+}
+
+extern "C" int rgbx_edge_slot_weights_f32(const int32_t* perm, int64_t nnz, const float* ew, int64_t E,
+                                          const float* loop_w, float* ew_slot, rgbx_stream_t stream) {
+  if (nnz < 0 || E < 0 || (nnz > 0 && (!perm || !ew_slot)) || (E > 0 && !ew))
+    return fail(RGBX_E_ARG, "edge_slot_weights: null pointer or negative size");
+  if (nnz > E && !loop_w) return fail(RGBX_E_ARG, "edge_slot_weights: nnz > E needs loop weights");
+  if (nnz == 0) return RGBX_OK;
+  slot_weight_kernel<<<grid_for(nnz), 256, 0, (hipStream_t)stream>>>(perm, nnz, ew, E, loop_w, ew_slot);
+  RGBX_CHECK_LAUNCH("slot_weight_kernel");
+  return RGBX_OK;
+}
+
+extern "C" int rgbx_weighted_deg_inv_sqrt_f32(const int32_t* rowptr, const float* ew_slot, int64_t N, float* dis,
+                                              rgbx_stream_t stream) {
+  if (N < 0 || !rowptr || !ew_slot || (N > 0 && !dis)) return fail(RGBX_E_ARG, "weighted_deg_inv_sqrt: bad argument");
+  if (N >= INT32_MAX) return fail(RGBX_E_RANGE, "weighted_deg_inv_sqrt: N exceeds int32");
+  if (N == 0) return RGBX_OK;
+  weighted_deg_inv_sqrt_kernel<<<grid_for(N, 4), 256, 0, (hipStream_t)stream>>>(rowptr, ew_slot, (int)N, dis);
+  RGBX_CHECK_LAUNCH("weighted_deg_inv_sqrt_kernel");
+  return RGBX_OK;
+}
+
+extern "C" int rgbx_gcn_norm_weighted_f32(const int32_t* rowptr, const int32_t* col, const float* ew_slot,
+                                          int64_t N, const float* dis, float* w, rgbx_stream_t stream) {
+  if (N < 0 || !rowptr || !col || !ew_slot || !dis || !w) return fail(RGBX_E_ARG, "gcn_norm_weighted: bad argument");
+  if (N >= INT32_MAX) return fail(RGBX_E_RANGE, "gcn_norm_weighted: N exceeds int32");
+  if (N == 0) return RGBX_OK;
+  gcn_norm_weighted_kernel<<<grid_for(N, 4), 256, 0, (hipStream_t)stream>>>(rowptr, col, ew_slot, (int)N, dis, w);
+  RGBX_CHECK_LAUNCH("gcn_norm_weighted_kernel");
+  return RGBX_OK;
+}
+
+extern "C" int rgbx_gcn_norm_bwd_f32(const int32_t* rowptr, const int32_t* col, const int32_t* perm,
+                                     const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f,
+                                     const int32_t* loop_src, const float* g, const float* ew_slot,
+                                     const float* dis, int64_t N, int64_t E, float* ddeg, float* dew,
+                                     rgbx_stream_t stream) {
+  if (N < 0 || E < 0) return fail(RGBX_E_ARG, "gcn_norm_bwd: negative size");
+  if (!rowptr || !col || !perm || !rowptr_t || !col_t || !t2f || !g || !ew_slot || !dis || !ddeg || (E > 0 && !dew))
+    return fail(RGBX_E_ARG, "gcn_norm_bwd: null pointer");
+  if (N >= INT32_MAX || E >= INT32_MAX) return fail(RGBX_E_RANGE, "gcn_norm_bwd: N or E exceeds int32");
+  hipStream_t s = (hipStream_t)stream;
+  if (E > 0) RGBX_HIP(hipMemsetAsync(dew, 0, sizeof(float) * (size_t)E, s));
+  if (N == 0) return RGBX_OK;
+  gcn_norm_bwd_deg_kernel<<<grid_for(N, 4), 256, 0, s>>>(rowptr, col, rowptr_t, col_t, t2f, g, ew_slot, dis, (int)N, ddeg);
+  RGBX_CHECK_LAUNCH("gcn_norm_bwd_deg_kernel");
+  gcn_norm_bwd_edge_kernel<<<grid_for(N, 4), 256, 0, s>>>(rowptr, col, perm, loop_src, g, dis, ddeg, (int)N, E, dew);
+  RGBX_CHECK_LAUNCH("gcn_norm_bwd_edge_kernel");
   return RGBX_OK;
 }

@@ -12,6 +12,12 @@ HBM layout per graph (E' = edges after the rewrite):
   dis     f32   [N]     deg^-1/2 over the target index           (GCN / APPNP)
   w       f32   [E']    dis[src]*dis[tgt] per forward slot; w_t the same per transposed slot
   inv_deg f32   [N]     1/max(deg,1) (mean);  w_mean_t f32 [E'] = inv_deg[tgt] per transposed slot
+
+Weighted graphs (``get_graph(..., edge_weight=ew)``, the ``edge_weight`` argument of gcn_norm at models/dagnn.py:12-31)
+share the unweighted entry's CSR arrays and add
+  loop_w  f32   [N]     weight of every added self-loop;  loop_src int32 [N] the input self-loop it came from, or -1
+  ew_slot f32   [E']    the input weight per forward slot (ew_slot_t per transposed slot)
+with dis = (sum of ew_slot over the row)^-1/2 and w = dis[src] * ew * dis[tgt].
 """
 import ctypes
 from collections import OrderedDict
@@ -226,6 +232,115 @@ class Graph:
         return self._w_mean_t
 
 
+def check_edge_weight(edge_weight, edge_index):
+    """The contract of an `edge_weight` argument, checked before any launch: float32 [E] on edge_index's device."""
+    if not isinstance(edge_weight, torch.Tensor):
+        raise ValueError(f"edge_weight must be a tensor, got {type(edge_weight).__name__}")
+    if edge_weight.dtype != torch.float32:
+        raise ValueError(f"edge_weight must be float32, got {edge_weight.dtype}")
+    if edge_weight.dim() != 1 or edge_index.dim() != 2 or edge_weight.numel() != edge_index.size(1):
+        raise ValueError(f"edge_weight must have shape [E] = [{edge_index.size(-1)}], got {tuple(edge_weight.shape)}")
+    if edge_weight.device != edge_index.device:
+        raise ValueError(f"edge_weight is on '{edge_weight.device}', edge_index on '{edge_index.device}'")
+
+
+class WeightedGraph(Graph):
+    """A Graph with per-edge weights: gcn_norm(edge_index, edge_weight) of models/dagnn.py:12-31. The CSR arrays (and the
+    sort behind them) are the unweighted entry's; `dis`, `w`, `w_t` and rowsum('gcn') are the weighted ones. The mean
+    aggregation has no weighted form (PyG's SAGEConv takes no edge_weight): `inv_deg` / `w_mean_t` raise."""
+
+    def __init__(self, base, edge_weight):
+        check_edge_weight(edge_weight, base._keepalive)
+        _lib.require_device(edge_weight)
+        ew = edge_weight.detach().contiguous()
+        if ew.numel() and not bool(torch.isfinite(ew).all().item()):
+            raise ValueError("edge_weight holds non-finite values")
+        self.base = base
+        self.N, self.E, self.loops_mode = base.N, base.E, base.loops_mode
+        self._src, self._dst = base._src, base._dst
+        self.fwd = base.fwd
+        self.ew = ew
+        self._dis = self._w = self._w_t = None
+        self._loops = self._ew_slot = self._ew_slot_t = None
+
+    bwd = property(lambda self: self.base.bwd)
+    t2f = property(lambda self: self.base.t2f)
+    undirected_keys = property(lambda self: self.base.undirected_keys)
+
+    @property
+    def loops(self):
+        """(loop_w f32 [N], loop_src int32 [N]) of the added self-loops, or (None, None) for LOOPS_KEEP."""
+        if self._loops is None:
+            if self.loops_mode == LOOPS_KEEP:
+                self._loops = (None, None)
+            else:
+                loop_w = self._f32(self.N)
+                loop_src = torch.empty(max(self.N, 1), dtype=torch.int32, device=loop_w.device)
+                _lib.check(_lib.load().rgbx_loop_weights_f32(
+                    _lib.ptr(self._src.contiguous()), _lib.ptr(self._dst.contiguous()), _lib.ptr(self.ew), self.E, self.N,
+                    self.loops_mode, 1.0, _lib.ptr(loop_w), _lib.ptr(loop_src), _lib.stream_ptr()), "rgbx_loop_weights_f32")
+                self._loops = (loop_w, loop_src)
+        return self._loops
+
+    def _slot_weights(self, csr):
+        out = self._f32(csr.nnz)
+        _lib.check(_lib.load().rgbx_edge_slot_weights_f32(_lib.ptr(csr.perm), csr.nnz, _lib.ptr(self.ew), self.E,
+                                                          _lib.ptr(self.loops[0]), _lib.ptr(out), _lib.stream_ptr()),
+                   "rgbx_edge_slot_weights_f32")
+        return out
+
+    @property
+    def ew_slot(self):
+        if self._ew_slot is None:
+            self._ew_slot = self._slot_weights(self.fwd)
+        return self._ew_slot
+
+    @property
+    def ew_slot_t(self):
+        if self._ew_slot_t is None:
+            self._ew_slot_t = self._slot_weights(self.bwd)
+        return self._ew_slot_t
+
+    @property
+    def dis(self):
+        if self._dis is None:
+            self._dis = self._f32(self.N)
+            _lib.check(_lib.load().rgbx_weighted_deg_inv_sqrt_f32(_lib.ptr(self.fwd.rowptr), _lib.ptr(self.ew_slot), self.N,
+                                                                  _lib.ptr(self._dis), _lib.stream_ptr()),
+                       "rgbx_weighted_deg_inv_sqrt_f32")
+        return self._dis
+
+    def _norm_weighted(self, csr, ew_slot):
+        w = self._f32(csr.nnz)
+        _lib.check(_lib.load().rgbx_gcn_norm_weighted_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(ew_slot), self.N,
+                                                          _lib.ptr(self.dis), _lib.ptr(w), _lib.stream_ptr()),
+                   "rgbx_gcn_norm_weighted_f32")
+        return w
+
+    @property
+    def w(self):
+        if self._w is None:
+            self._w = self._norm_weighted(self.fwd, self.ew_slot)
+        return self._w
+
+    @property
+    def w_t(self):
+        if self._w_t is None:
+            self._w_t = self._norm_weighted(self.bwd, self.ew_slot_t)
+        return self._w_t
+
+    @property
+    def inv_deg(self):
+        raise RuntimeError("a weighted graph has no mean aggregation: SAGEConv takes no edge_weight [PyG]")
+
+    w_mean_t = inv_deg
+
+    def rowsum(self, kind):
+        if kind != "gcn":
+            raise RuntimeError("a weighted graph has no mean aggregation: SAGEConv takes no edge_weight [PyG]")
+        return Graph.rowsum(self, kind)
+
+
 _CACHE = OrderedDict()
 _CACHE_MAX = 16
 _PINNED = {}
@@ -243,8 +358,13 @@ def register_graph(edge_index, num_nodes, loops_mode, graph):
     _PINNED[_key(edge_index, num_nodes, loops_mode)] = graph
 
 
-def get_graph(edge_index, num_nodes, loops_mode):
-    """Cached Graph for this edge_index tensor (identity + in-place version), N and rewrite mode."""
+def get_graph(edge_index, num_nodes, loops_mode, edge_weight=None):
+    """Cached Graph for this edge_index tensor (identity + in-place version), N and rewrite mode. With `edge_weight`
+    (float32 [E], same device, finite; else ValueError before any launch) a WeightedGraph over the same CSR arrays, cached
+    under the weight tensor's identity, shape and version as well; a weight that requires grad is prepared anew on every
+    call (its values move with every optimizer step) and not cached."""
+    if edge_weight is not None:
+        return _get_weighted(edge_index, num_nodes, loops_mode, edge_weight)
     key = _key(edge_index, num_nodes, loops_mode)
     g = _PINNED.get(key)
     if g is not None:
@@ -258,6 +378,27 @@ def get_graph(edge_index, num_nodes, loops_mode):
             _CACHE.popitem(last=False)
     else:
         _CACHE.move_to_end(key)
+    return g
+
+
+def _get_weighted(edge_index, num_nodes, loops_mode, edge_weight):
+    check_edge_weight(edge_weight, edge_index)
+    key = _key(edge_index, num_nodes, loops_mode) + (edge_weight.data_ptr(), tuple(edge_weight.shape),
+                                                     edge_weight._version)
+    g = None if edge_weight.requires_grad else _CACHE.get(key)
+    if g is not None:
+        _CACHE.move_to_end(key)
+        return g
+    base = get_graph(edge_index, num_nodes, loops_mode)
+    if getattr(base, "is_distributed", False):
+        raise NotImplementedError("edge weights on a partitioned graph are not implemented")
+    g = WeightedGraph(base, edge_weight)
+    g._keepalive = edge_index
+    if not edge_weight.requires_grad:
+        g._keepalive_weight = edge_weight  # the key holds its data_ptr
+        _CACHE[key] = g
+        while len(_CACHE) > _CACHE_MAX:
+            _CACHE.popitem(last=False)
     return g
 
 

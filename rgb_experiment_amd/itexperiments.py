@@ -177,6 +177,8 @@ def label_propagation(adj, labels, idx, K, alpha, device=None):
     return y
 
 
+_EDGE_WEIGHT_MODELS = ("gcn", "appnpstack", "sgc")  # experiment(use_edge_weight=True)
+
 # use_hip_graph=True captures the epoch only up to this many edges: beyond it the aggregation kernels, not launch
 # latency, set the epoch time, and a replayed graph was measured slower
 HIP_GRAPH_MAX_EDGES = 20_000_000
@@ -226,7 +228,8 @@ def experiment(model_init_param: dict, *,
                share_eval_forward: bool = True,
                cache_input_aggregate="auto",
                distributed=None,
-               task_split: str = "auto"):
+               task_split: str = "auto",
+               use_edge_weight: bool = False):
     """Train + evaluate one model on one graph; returns {'ACC', 'precision_score', 'recall_score',
     'f1_macro', 'f1_micro'} (reference :603-605). ``return_model=True`` (an addition) also returns
     the trained module and the per-epoch curves under 'model' / 'history'. ``use_hip_graph=True`` (an
@@ -261,7 +264,12 @@ def experiment(model_init_param: dict, *,
     ops.masked_ce_accuracy) — single-device, with ``use_hip_graph`` honoured as for any model. ``use_cpu=True`` is not
     refused up front: a module that owns a graph layer raises that layer's "no CPU fallback" RuntimeError. This is how
     FAGCN trains (``model=rgb_experiment_amd.models.FAGCN(...)``) while the NAME "fagcn" stays refused. ``model=None``
-    (default) changes nothing."""
+    (default) changes nothing. ``use_edge_weight=True`` (an addition, off by default): ``data.edge_weight`` (float [E])
+    goes to the device with the data and into the forward arguments as ``edge_weight`` — gcn_norm's parameter
+    (models/dagnn.py:12-31) — for the four routes that take weights: ``gcn``, ``appnpstack``, ``sgc`` and ``post_cs``
+    (any other model_name: ValueError). Not with ``to_undirected_graph`` (the reference's to_undirected call carries no
+    weights: ValueError) and not on the partitioned route (NotImplementedError). With the flag off a ``Data`` that
+    happens to carry an ``edge_weight`` attribute behaves exactly as one without."""
     say = print if print_print else (lambda *a, **k: None)
     say(f"running node classification: {'custom' if specify_data else dataset_name} data, model {model_name}")
 
@@ -275,6 +283,13 @@ def experiment(model_init_param: dict, *,
         raise NotImplementedError("print_pics / vis_feat are reporting features outside the hot-path scope")
     if post_cs and name == "pta":
         raise ValueError("post_cs cannot be combined with PTA (reference :517)")
+    if use_edge_weight:
+        if name not in _EDGE_WEIGHT_MODELS or model is not None:
+            raise ValueError(f"use_edge_weight=True: model_name={model_name!r} takes no edge weights; the routes that do "
+                             "are gcn, appnpstack, sgc and post_cs (on one of those three models)")
+        if to_undirected_graph:
+            raise ValueError("use_edge_weight=True cannot be combined with to_undirected_graph=True: the reference's "
+                             "to_undirected call (:235-238) carries no weights")
 
     # ---- data (reference :179-229) ----------------------------------------------------------
     if not specify_data:
@@ -295,6 +310,8 @@ def experiment(model_init_param: dict, *,
         from .dist.experiment import SUPPORTED
         distributed = world > 1 and name in SUPPORTED and not post_cs and model is None
     dist_ctx = None
+    if distributed and use_edge_weight:
+        raise NotImplementedError("use_edge_weight=True is not implemented on the partitioned (distributed) route")
     if distributed:
         from .dist.experiment import DistContext
         dist_ctx = DistContext.open(name, post_cs, use_cpu)  # process group, rank's device; raises for unsupported set-ups
@@ -307,6 +324,15 @@ def experiment(model_init_param: dict, *,
     data = data.to(device)
     if to_undirected_graph:  # reference :235-238 (there on the CPU, before .to(device)); here on the run's device: the
         data.edge_index = to_undirected(data.edge_index, num_nodes=data.num_nodes)  # HIP radix sort + unique on a GPU
+    edge_weight = None
+    if use_edge_weight:
+        edge_weight = getattr(data, "edge_weight", None)
+        if not torch.is_tensor(edge_weight) or not edge_weight.is_floating_point():
+            raise ValueError("use_edge_weight=True needs data.edge_weight: a float tensor of shape [E]")
+        if edge_weight.dim() != 1 or edge_weight.numel() != data.edge_index.size(1):
+            raise ValueError(f"data.edge_weight must have shape [E] = [{data.edge_index.size(1)}], got "
+                             f"{tuple(edge_weight.shape)}")
+        edge_weight = edge_weight.detach().to(torch.float32).contiguous()
     features = data.x
     if normalize_feature in ("row", "col", "all"):
         features = _normalize_features(features, normalize_feature, normalize_feature_method)
@@ -355,6 +381,8 @@ def experiment(model_init_param: dict, *,
     else:
         net = MODELS[name](input_dim=input_dim, output_dim=output_dim, **model_init_param)
         fwd = {"x": features} if name == "mlp" else {"x": features, "edge_index": data.edge_index}
+        if edge_weight is not None:
+            fwd["edge_weight"] = edge_weight
     net.to(device)
     uses_graph = name != "mlp" if model is None else "edge_index" in fwd
     if model is not None:  # one eval-mode forward before the loop: the contract of the returned mapping
@@ -545,8 +573,9 @@ def experiment(model_init_param: dict, *,
             raise RuntimeError("post_cs runs its propagation in HIP kernels; a GPU is required (no CPU fallback)")
         post = CorrectAndSmooth(**(cs_param or InitialParameters.default_cs_param))
         y_soft = final["test_op"].exp()
-        y_soft = post.correct(y_soft, y[train_mask], train_mask, data.edge_index)
-        y_soft = post.smooth(y_soft, y[train_mask], train_mask, data.edge_index)
+        cs_weight = {} if edge_weight is None else {"edge_weight": edge_weight}
+        y_soft = post.correct(y_soft, y[train_mask], train_mask, data.edge_index, **cs_weight)
+        y_soft = post.smooth(y_soft, y[train_mask], train_mask, data.edge_index, **cs_weight)
         pred = y_soft.max(dim=1)[1][test_mask]
         cs = compare_pred_label(pred, y[test_mask], need_all_metrics)
         final.update(cs)

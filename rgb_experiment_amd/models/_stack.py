@@ -88,38 +88,48 @@ class ConvStack(nn.Module):
         self.convs = nn.ModuleList(make_conv(i, widths[i], widths[i + 1]) for i in range(num_layers))
         self.bns = nn.ModuleList(BatchNorm1d(bn_width) for _ in range(num_layers - 1))
 
-    def forward(self, x, edge_index):
-        return model_output(self._run(x, edge_index))
+    def forward(self, x, edge_index, edge_weight=None):
+        """`edge_weight` (float32 [E]): passed to every conv; only stacks of GCNConv take one (ValueError otherwise). A
+        weight that requires grad makes every layer take its plain transform-first route (nn.GCNConv): the cached input
+        aggregate and the fused forms are skipped, the collapsed eval forward (no_grad) stays."""
+        return model_output(self._run(x, edge_index, edge_weight=edge_weight))
 
-    def masked_ce(self, x, edge_index, y, mask):
+    def masked_ce(self, x, edge_index, y, mask, edge_weight=None):
         """(loss, stats) = NLLLoss(log_softmax(logits)[mask], y[mask]) and [nll sum, selected rows, correct] of this
         model's logits — what the training loop and the metrics need of a forward (itexperiments.py:429,434,624-626) —
         with the last conv taking the loss into its kernel where it can: the logits are then never written
         (ops.propagate_linear_ce). Otherwise the same numbers from the materialised logits. Under no_grad in eval mode
         the loss itself may be None (nobody reads it there): it is stats[0] / stats[1]."""
-        return self._run(x, edge_index, ce=(y, mask))
+        return self._run(x, edge_index, ce=(y, mask), edge_weight=edge_weight)
 
-    def masked_ce_pair(self, x, edge_index, y, mask_a, mask_b):
+    def masked_ce_pair(self, x, edge_index, y, mask_a, mask_b, edge_weight=None):
         """[2, 3] statistics ([nll sum, selected rows, correct] under mask_a and under mask_b) of ONE eval forward: the val
         and the test metrics of an epoch, for which the reference runs two identical eval forwards
         (itexperiments.py:464-473). Where the last conv takes the loss into its kernel both sets come out of that one
         launch (rgbx_ce_epilogue_t.mask_groups = 2) and the logits are never written; otherwise from the logits."""
-        return self._run(x, edge_index, ce=(y, (mask_a, mask_b)))[1]
+        return self._run(x, edge_index, ce=(y, (mask_a, mask_b)), edge_weight=edge_weight)[1]
 
-    def _run(self, x, edge_index, ce=None):
+    def _run(self, x, edge_index, ce=None, edge_weight=None):
         """x = bns[i](convs[i](x)) ... convs[-1](x) (models/gcn.py:25-31). A BatchNorm is never a pass of its own
         where a neighbouring conv can absorb it: under no_grad its eval-mode affine map goes into the PRECEDING conv's
         weights; in a training forward it is handed to the FOLLOWING conv (forward_after_bn), whose fused kernel
         applies it to the aggregate of the raw rows."""
         from .. import ops
         last = self.num_layers - 1
+        ew = {}  # the keyword goes to the convs only when it is given: every other call is exactly the unweighted one
+        if edge_weight is not None:
+            if any(type(c).__name__ != "GCNConv" for c in self.convs):
+                raise ValueError(f"{type(self).__name__}: edge_weight is taken by stacks of GCNConv only")
+            ew["edge_weight"] = edge_weight
+        learned = edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled()
         pending = None  # a BatchNorm whose output has not been formed yet
         if self.training and torch.is_grad_enabled():
             self._train_forwards = getattr(self, "_train_forwards", 0) + 1  # statistics and weights are about to move
         folded = self._eval_operands() if (not torch.is_grad_enabled() and not self.training and x.is_cuda) else None
-        agg0 = self._input_aggregate(x, edge_index) if getattr(self, "cache_input_aggregate", False) else None
+        agg0 = (self._input_aggregate(x, edge_index, edge_weight)
+                if getattr(self, "cache_input_aggregate", False) and not learned else None)
         if folded is not None and agg0 is None and getattr(self, "collapse_eval", True):
-            out = self._run_collapsed(x, edge_index, ce)
+            out = self._run_collapsed(x, edge_index, ce, edge_weight)
             if out is not None:
                 return out
         for i, conv in enumerate(self.convs):
@@ -137,13 +147,13 @@ class ConvStack(nn.Module):
                     continue
             if folded is not None and pending is None and folded[i] is not None:
                 # eval forward from prepared operands: one fused launch per layer, no weight arithmetic
-                res = conv.forward_folded(x, edge_index, folded[i], ce=ce if i == last else None)
+                res = conv.forward_folded(x, edge_index, folded[i], ce=ce if i == last else None, **ew)
                 if res is not None:
                     x = res
                     continue
             # a training-mode BatchNorm follows a conv that can hand it its column sums (taken from the fused kernel's
             # MFMA tiles): no statistics pass over the conv's output
-            extra = {}
+            extra = dict(ew)
             if (bn is not None and bn.training and torch.is_grad_enabled() and getattr(conv, "emits_colsums", False)
                     and hasattr(bn, "begin_training_step")):
                 extra["want_colsums"] = True
@@ -162,7 +172,7 @@ class ConvStack(nn.Module):
                 fold = getattr(bn, "eval_affine", None)
                 affine = fold() if fold is not None else None
             if affine is not None:  # eval forward: BatchNorm's affine map folded into the conv's weights
-                x = conv(x, edge_index, post_affine=affine)
+                x = conv(x, edge_index, post_affine=affine, **ew)
             else:
                 x, pending = conv(x, edge_index, **extra), bn
         if ce is not None and not isinstance(x, tuple):  # a last conv without the loss epilogue (GATConv)
@@ -243,7 +253,7 @@ def _collapsed_operands(self):
     return out
 
 
-def _run_collapsed(self, x, edge_index, ce):
+def _run_collapsed(self, x, edge_index, ce, edge_weight=None):
     """The eval forward (no_grad) through _collapsed_operands: one product at (blocks x) the class width, one row gather per
     layer with the lower-order block as its additive operand, the masked cross-entropy (one or two masks) taken in the last
     gather. None where the collapsed form does not apply."""
@@ -253,7 +263,7 @@ def _run_collapsed(self, x, edge_index, ce):
     if operands is None:
         return None
     weight, have, shifts, C, Cp, kind, loops_mode = operands
-    graph = get_graph(edge_index, x.size(0), loops_mode)
+    graph = get_graph(edge_index, x.size(0), loops_mode, edge_weight)
     if getattr(graph, "is_distributed", False) or not ops.rows_epilogue_ok(graph, Cp, x, None if ce is None else ce[0]):
         return None
     z = ops.linear(x, weight)  # [N, blocks * C']: over the non-zeros of bag-of-words features (ops.prepare_features)
@@ -302,7 +312,7 @@ def _eval_operands(self):
 ConvStack._eval_operands = _eval_operands
 
 
-def _input_aggregate(self, x, edge_index):
+def _input_aggregate(self, x, edge_index, edge_weight=None):
     """The first conv's aggregate P x of the input features, kept across forwards and epochs (opt-in:
     `model.cache_input_aggregate = True`, experiment(cache_input_aggregate=True)). The reference recomputes it in every
     forward (models/gcn.py:27 inside the loop of itexperiments.py:417-473); with static features and a static graph it
@@ -312,15 +322,24 @@ def _input_aggregate(self, x, edge_index):
     if x.requires_grad or not x.is_cuda:
         return None
     key = (x.data_ptr(), x._version, tuple(x.shape), edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape))
+    if edge_weight is not None:
+        key += (edge_weight.data_ptr(), edge_weight._version, tuple(edge_weight.shape))
     cached = getattr(self, "_agg0", None)
     if cached is None or cached[0] != key:
         make = getattr(self.convs[0], "aggregate_input", None)
-        cached = (key, make(x, edge_index) if make is not None else None, x, edge_index)  # the tensors stay alive
+        args = (x, edge_index) if edge_weight is None else (x, edge_index, edge_weight)
+        cached = (key, make(*args) if make is not None else None, x, edge_index, edge_weight)  # the tensors stay alive
         self._agg0 = cached
     return cached[1]
 
 
 ConvStack._input_aggregate = _input_aggregate
+
+
+def _weighted_call(fn, fwd):
+    """Forward arguments {x, edge_index, edge_weight} for a masked_ce form that takes the weight."""
+    import inspect
+    return set(fwd) == {"x", "edge_index", "edge_weight"} and "edge_weight" in inspect.signature(fn).parameters
 
 
 def masked_ce_pair(model, fwd, y, mask_a, mask_b):
@@ -330,6 +349,8 @@ def masked_ce_pair(model, fwd, y, mask_a, mask_b):
     fn = getattr(model, "masked_ce_pair", None)
     if fn is not None and set(fwd) == {"x", "edge_index"} and fwd["x"].is_cuda:
         return fn(fwd["x"], fwd["edge_index"], y, mask_a, mask_b)
+    if fn is not None and fwd["x"].is_cuda and _weighted_call(fn, fwd):
+        return fn(fwd["x"], fwd["edge_index"], y, mask_a, mask_b, edge_weight=fwd["edge_weight"])
     emb = model(**fwd)["emb"]
     return torch.stack([ops.masked_ce_accuracy(emb, y, mask_a), ops.masked_ce_accuracy(emb, y, mask_b)])
 
@@ -341,4 +362,6 @@ def masked_ce(model, fwd, y, mask):
     fn = getattr(model, "masked_ce", None)
     if fn is not None and set(fwd) == {"x", "edge_index"} and fwd["x"].is_cuda:
         return fn(fwd["x"], fwd["edge_index"], y, mask)
+    if fn is not None and fwd["x"].is_cuda and _weighted_call(fn, fwd):
+        return fn(fwd["x"], fwd["edge_index"], y, mask, edge_weight=fwd["edge_weight"])
     return ops.ce_from_logits(model(**fwd)["emb"], y, mask)

@@ -10,5 +10,6 @@ class SGC(nn.Module):
         super().__init__()
         self.conv1 = SGConv(input_dim, output_dim, K=K, cached=cached, add_self_loops=add_self_loops)
 
-    def forward(self, x, edge_index):
-        return model_output(self.conv1(x, edge_index))
+    def forward(self, x, edge_index, edge_weight=None):
+        """`edge_weight`: see nn.SGConv (with cached=True the first call's weights are the ones kept)."""
+        return model_output(self.conv1(x, edge_index, edge_weight))

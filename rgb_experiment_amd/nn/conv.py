@@ -30,12 +30,18 @@ def glorot_(t):
     return t
 
 
-def _forward_folded(conv, x, edge_index, operands, ce, loops_mode, kind, root):
+def _no_weight_grad(edge_weight, who):
+    if edge_weight is not None and edge_weight.requires_grad:
+        raise ValueError(f"{who}: edge_weight must not require grad (the gradient in the edge weights is implemented for "
+                         "GCNConv only)")
+
+
+def _forward_folded(conv, x, edge_index, operands, ce, loops_mode, kind, root, edge_weight=None):
     """Eval forward of a GCN / SAGE layer from prepared operands (W'^T, b', Wr'^T): ONE rgbx_fused_layer_f32 launch, no
     autograd node, no weight arithmetic on the way. Returns None when the fused kernel does not apply."""
     if operands is None or torch.is_grad_enabled() or not x.is_cuda:
         return None
-    graph = get_graph(edge_index, x.size(0), loops_mode)
+    graph = get_graph(edge_index, x.size(0), loops_mode, edge_weight)
     if getattr(graph, "is_distributed", False) or not ops.fused_linear_ok(graph, conv.in_channels, conv.out_channels,
                                                                           root=root, x=x):
         return None
@@ -55,9 +61,11 @@ def _forward_folded(conv, x, edge_index, operands, ce, loops_mode, kind, root):
     return out
 
 
-def _aggregate_input(x, edge_index, loops_mode, kind):
+def _aggregate_input(x, edge_index, loops_mode, kind, edge_weight=None):
     """P x of the static input features (no autograd), or None where the cached-aggregate route does not apply."""
-    graph = get_graph(edge_index, x.size(0), loops_mode)
+    if edge_weight is not None and edge_weight.requires_grad:
+        return None  # the aggregate depends on weights that are being learned
+    graph = get_graph(edge_index, x.size(0), loops_mode, edge_weight)
     if getattr(graph, "is_distributed", False) or not x.is_cuda or x.requires_grad:
         return None
     with torch.no_grad():
@@ -75,7 +83,13 @@ def _folded_from_aggregate(z, x, operands, root):
 class GCNConv(nn.Module):
     """out = A_hat (x W^T) + b, A_hat = D^-1/2 (A ∪ I) D^-1/2 with in-degree over the target index
     (gcn_norm restated at reference models/dagnn.py:12-31; message norm*x_j at dagnn.py:57-59).
-    Parameters: ``lin.weight`` [out, in] (glorot, no bias), ``bias`` [out] (zeros)."""
+    Parameters: ``lin.weight`` [out, in] (glorot, no bias), ``bias`` [out] (zeros).
+
+    ``edge_weight`` (float32 [E], PyG's third argument) enters the normalisation as in gcn_norm(edge_index, edge_weight)
+    (dagnn.py:12-31): an existing self-loop keeps its weight, added ones get 1, the degree is the weighted in-degree.
+    Constant weights take every route of the unweighted layer on the weighted graph's per-slot weights. A weight that
+    REQUIRES GRAD takes the transform-first route propagate(lin(x)) through ops.propagate_gcn_edge_weight, whose backward
+    also returns dL/d edge_weight; the fused aggregate + transform kernels and the loss-in-kernel forms are skipped then."""
 
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # forward(..., want_colsums=True): the output may carry its column sums (ops.COLSUMS)
@@ -94,7 +108,7 @@ class GCNConv(nn.Module):
     accepts_ce = True         # forward(..., ce=(y, mask)): the model's last layer may take the loss into its kernel
     accepts_ce_pair = True    # ... and mask may be (mask_a, mask_b): (None, [2, 3] statistics) of one eval forward
 
-    def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None):
+    def forward(self, x, edge_index, edge_weight=None, post_affine=None, want_colsums=False, ce=None):
         """`post_affine` = (scale, shift) of an eval-mode BatchNorm that follows this layer (no_grad only): a
         per-column affine map of a linear layer's output is the same layer with rows of W and b rescaled, so the
         normalisation costs two [out]-sized vector ops instead of a pass over [N, out].
@@ -104,37 +118,45 @@ class GCNConv(nn.Module):
         not the logits: returns (loss, stats [nll sum, selected rows, correct]); where the fused kernel runs the loss
         is taken from the output tiles and the logits are never written (ops.propagate_linear_ce)."""
         if ce is not None:
-            return self._ce(x, edge_index, ce, None, None)
+            return self._ce(x, edge_index, ce, None, None, edge_weight)
         weight, bias = self.lin.weight, self.bias
         if post_affine is not None:
             scale, shift = post_affine
             weight, bias = weight * scale[:, None], bias * scale + shift
-        return self._conv(x, edge_index, weight, bias, want_colsums)
+        return self._conv(x, edge_index, weight, bias, want_colsums, edge_weight)
 
     def eval_operands(self, bn=None):
         """(W'^T, b', None) of this layer for an eval forward, the eval-mode BatchNorm `bn` behind it folded in."""
         return ops.fold_bn_linear(self.lin.weight, self.bias, bn=bn)
 
     # opt-in cache of the static input features' aggregate (models/_stack.ConvStack.cache_input_aggregate)
-    def aggregate_input(self, x, edge_index):
+    def aggregate_input(self, x, edge_index, edge_weight=None):
         if self.in_channels > self.out_channels or not ops.aggregate_linear_ok(self.in_channels, self.out_channels):
             return None
-        return _aggregate_input(x, edge_index, LOOPS_ADD_REMAINING, "gcn")
+        return _aggregate_input(x, edge_index, LOOPS_ADD_REMAINING, "gcn", edge_weight)
 
     def forward_from_aggregate(self, z, x, want_colsums=False, folded=None):
         if folded is not None:
             return _folded_from_aggregate(z, x, folded, False)
         return ops.aggregate_linear(z, self.lin.weight, self.bias, want_colsums=want_colsums)
 
-    def forward_folded(self, x, edge_index, operands, ce=None):
+    def forward_folded(self, x, edge_index, operands, ce=None, edge_weight=None):
         """Eval forward (no_grad) from prepared operands (eval_operands; models/_stack.ConvStack keeps them per
         parameter state): one fused launch. `ce` = (y, mask): returns (None, stats). None when this layer / graph does
         not take the fused kernel (the caller then runs the ordinary forward)."""
-        return _forward_folded(self, x, edge_index, operands, ce, LOOPS_ADD_REMAINING, "gcn", False)
+        return _forward_folded(self, x, edge_index, operands, ce, LOOPS_ADD_REMAINING, "gcn", False, edge_weight)
 
-    def _ce(self, x, edge_index, ce, bn, colsums):
+    @staticmethod
+    def _learned(edge_weight):
+        return edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled()
+
+    def _ce(self, x, edge_index, ce, bn, colsums, edge_weight=None):
         y, mask = ce
-        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING)
+        if self._learned(edge_weight):  # the loss-in-kernel forms have no gradient in the edge weights
+            if bn is not None:
+                x = bn(x, colsums=colsums)
+            return ops.ce_from_logits(self.forward(x, edge_index, edge_weight), y, mask)
+        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING, edge_weight)
         hand_over = bn is not None and bn.folds_into_next_layer(x)
         if ops.fused_ce_ok(graph, self.in_channels, self.out_channels, False, x, y) and (bn is None or hand_over):
             return ops.propagate_linear_ce(x, graph, "gcn", self.lin.weight, self.bias, None, y, mask, bn=bn,
@@ -146,23 +168,28 @@ class GCNConv(nn.Module):
             # transform first (the reference's shapes: hidden 64 -> C = 7, initial_params.py:25), then aggregate the
             # [N, 8] rows with the loss taken in the gather kernel: no logits, no log-softmax / NLL / arg-max passes
             return ops.propagate_rows_ce(ops.linear(x, weight), graph, "gcn", n, self.out_channels, y, mask, bias=bias)
-        return ops.ce_from_logits(self.forward(x, edge_index), y, mask)
+        return ops.ce_from_logits(self.forward(x, edge_index, edge_weight), y, mask)
 
-    def forward_after_bn(self, x, edge_index, bn, colsums=None, want_colsums=False, ce=None):
+    def forward_after_bn(self, x, edge_index, bn, colsums=None, want_colsums=False, ce=None, edge_weight=None):
         """self(bn(x), edge_index) for the BatchNorm1d in front of this layer. In a training forward on one GPU the
         normalised matrix is not written: the fused kernel gathers the raw rows and applies BatchNorm's affine map to
         the aggregate (ops.bn_propagate_linear). `colsums`: the column sums of x if its producer took them."""
         if ce is not None:
-            return self._ce(x, edge_index, ce, bn, colsums)
-        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING)
+            return self._ce(x, edge_index, ce, bn, colsums, edge_weight)
+        if self._learned(edge_weight):
+            return self.forward(bn(x, colsums=colsums), edge_index, edge_weight, want_colsums=want_colsums)
+        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING, edge_weight)
         if (bn.folds_into_next_layer(x) and not getattr(graph, "is_distributed", False)
                 and ops.fused_linear_ok(graph, self.in_channels, self.out_channels, x=x)):
             return ops.bn_propagate_linear(x, bn, graph, "gcn", self.lin.weight, self.bias, colsums=colsums,
                                            want_colsums=want_colsums)
-        return self.forward(bn(x, colsums=colsums), edge_index, want_colsums=want_colsums)
+        return self.forward(bn(x, colsums=colsums), edge_index, edge_weight, want_colsums=want_colsums)
 
-    def _conv(self, x, edge_index, weight, bias, want_colsums=False):
-        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING)
+    def _conv(self, x, edge_index, weight, bias, want_colsums=False, edge_weight=None):
+        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING, edge_weight)
+        if self._learned(edge_weight):
+            # transform first, then the gather whose backward also differentiates the normalisation in the weights
+            return ops.propagate_gcn_edge_weight(ops.linear(x, weight), edge_weight, graph, bias=bias)
         if ops.fused_linear_ok(graph, self.in_channels, self.out_channels, x=x):
             # A_hat (x W^T) + b = (A_hat x) W^T + b in one kernel: the aggregate stays in LDS and the GEMM
             # runs on the MFMA units underneath the gather (ops._PropagateLinear)
@@ -492,21 +519,25 @@ class GATConv(nn.Module):
 
 class APPNP(nn.Module):
     """z^0 = x; z^{k+1} = (1-alpha) A_hat z^k + alpha x, K times (in-repo twin of the recurrence:
-    reference models/pta.py:79-84); gcn_norm computed once per graph."""
+    reference models/pta.py:79-84); gcn_norm computed once per graph. `edge_weight` (float32 [E], constant: a weight that
+    requires grad raises ValueError) enters gcn_norm as in GCNConv."""
 
     def __init__(self, K, alpha):
         super().__init__()
         self.K, self.alpha = K, alpha
 
-    def forward(self, x, edge_index):
-        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING)
+    def forward(self, x, edge_index, edge_weight=None):
+        _no_weight_grad(edge_weight, "APPNP")
+        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING, edge_weight)
         return ops.appnp_propagate(x, graph, self.K, self.alpha)
 
 
 class SGConv(nn.Module):
     """x' = lin(A_hat^K x) with gcn_norm (self-loops added unless add_self_loops=False) and the
     propagated features cached after the first call when cached=True [PyG SGConv, as built at reference
-    models/sgc.py:9-10]. The K propagates run as one rgbx_appnp_f32 call with alpha = 0."""
+    models/sgc.py:9-10]. The K propagates run as one rgbx_appnp_f32 call with alpha = 0. `edge_weight` (float32 [E],
+    constant: a weight that requires grad raises ValueError) enters gcn_norm as in GCNConv; with cached=True the kept
+    propagate is that of the FIRST call's weights, as in PyG — later calls ignore their edge_weight."""
 
     def __init__(self, in_channels, out_channels, K=1, cached=False, add_self_loops=True, bias=True):
         super().__init__()
@@ -515,11 +546,12 @@ class SGConv(nn.Module):
         self.lin = nn.Linear(in_channels, out_channels, bias=bias)
         self._cached_x = None
 
-    def forward(self, x, edge_index):
+    def forward(self, x, edge_index, edge_weight=None):
+        _no_weight_grad(edge_weight, "SGConv")
         h = self._cached_x
         if h is None:
             mode = LOOPS_ADD_REMAINING if self.add_self_loops else LOOPS_KEEP
-            graph = get_graph(edge_index, x.size(0), mode)
+            graph = get_graph(edge_index, x.size(0), mode, edge_weight)
             if not self.cached and self.in_channels > self.out_channels:
                 # nothing is kept between calls, so A_hat^K (x W^T) = (A_hat^K x) W^T runs the K gathers at the
                 # OUTPUT width (F = 1433 -> C = 7 on Cora: 1/180 of the bytes)

@@ -2,7 +2,8 @@
 torch_geometric.nn.CorrectAndSmooth / LabelPropagation [PyG, un-vendored]). Both stages are K
 repetitions of `out <- alpha * A_hat out + (1 - alpha) * y0` followed by a clamp, with
 A_hat = D^-1/2 A D^-1/2 WITHOUT added self-loops; each repetition is one rgbx_spmm_csr_f32 launch
-with the residual fused into the store (a = alpha, y = (1-alpha) y0, b = 1)."""
+with the residual fused into the store (a = alpha, y = (1-alpha) y0, b = 1). `edge_weight` (float32 [E], PyG's keyword
+position; constant) enters the normalisation: A_hat = D^-1/2 A_w D^-1/2 with the weighted in-degree."""
 import torch
 import torch.nn.functional as F
 
@@ -15,9 +16,11 @@ class LabelPropagation:
         self.num_layers, self.alpha = num_layers, alpha
 
     @torch.no_grad()
-    def __call__(self, y, edge_index, post_step=None):
+    def __call__(self, y, edge_index, edge_weight=None, post_step=None):
+        if edge_weight is not None and edge_weight.requires_grad:
+            raise ValueError("LabelPropagation: edge_weight must not require grad")
         post_step = post_step or (lambda t: t.clamp_(0.0, 1.0))
-        graph = get_graph(edge_index, y.size(0), LOOPS_KEEP)
+        graph = get_graph(edge_index, y.size(0), LOOPS_KEEP, edge_weight)
         out = y.contiguous()
         res = ((1 - self.alpha) * out).contiguous()
         for _ in range(self.num_layers):
@@ -42,7 +45,7 @@ class CorrectAndSmooth:
         return y_true
 
     @torch.no_grad()
-    def correct(self, y_soft, y_true, mask, edge_index):
+    def correct(self, y_soft, y_true, mask, edge_index, edge_weight=None):
         """Spread the training residual: error = onehot - y_soft on `mask`, 0 elsewhere; propagate it
         (clamped to [-1, 1]); with autoscale, scale every row so its L1 norm equals the mean training
         residual norm (rows that would scale by inf or > 1000 keep scale 1)."""
@@ -52,7 +55,7 @@ class CorrectAndSmooth:
         error = torch.zeros_like(y_soft)
         error[mask] = y_true - y_soft[mask]
         if self.autoscale:
-            smoothed = self.prop1(error, edge_index, post_step=lambda t: t.clamp_(-1.0, 1.0))
+            smoothed = self.prop1(error, edge_index, edge_weight, post_step=lambda t: t.clamp_(-1.0, 1.0))
             sigma = error[mask].abs().sum() / numel
             scale = sigma / smoothed.abs().sum(dim=1, keepdim=True)
             scale[scale.isinf() | (scale > 1000)] = 1.0
@@ -62,11 +65,11 @@ class CorrectAndSmooth:
             t[mask] = error[mask]
             return t
 
-        return y_soft + self.scale * self.prop1(error, edge_index, post_step=fix_input)
+        return y_soft + self.scale * self.prop1(error, edge_index, edge_weight, post_step=fix_input)
 
     @torch.no_grad()
-    def smooth(self, y_soft, y_true, mask, edge_index):
+    def smooth(self, y_soft, y_true, mask, edge_index, edge_weight=None):
         """Clamp the training rows to their labels and propagate (clamped to [0, 1])."""
         y_soft = y_soft.clone()
         y_soft[mask] = self._onehot(y_true, y_soft)
-        return self.prop2(y_soft, edge_index)
+        return self.prop2(y_soft, edge_index, edge_weight)

@@ -185,6 +185,78 @@ def propagate_gcn(x, graph, bias=None):
     return out if xp is x else out[:, :d]
 
 
+def edge_dot_raw(csr, a, b, kind="edge_dot"):
+    """g[p] = <a[i], b[col[p]]> for every slot p of row i of `csr` (rgbx_edge_dot_f32; no autograd): dL/dw of a weighted
+    aggregation with a = dL/dout and b = the gathered matrix. Widths that are no multiple of 4 run zero-padded; widths
+    above 256 in column blocks of 256 whose dots are added."""
+    _lib.require_device(a, b)
+    if a.size(1) % 4:
+        pad = 4 - a.size(1) % 4
+        a, b = torch.nn.functional.pad(a, (0, pad)), torch.nn.functional.pad(b, (0, pad))
+    vec_ok = lambda t: t.stride(-1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+    a, b = (a if vec_ok(a) else a.contiguous()), (b if vec_ok(b) else b.contiguous())
+    d = a.size(1)
+    g = torch.empty(max(csr.nnz, 1), dtype=torch.float32, device=a.device)
+    total = None
+    lib = _lib.load()
+    for c0 in range(0, d, 256):
+        c1 = min(c0 + 256, d)
+        pa, lda = _lib.mat(a[:, c0:c1], "a")
+        pb, ldb = _lib.mat(b[:, c0:c1], "b")
+        split, _scratch = (None, None) if csr.split is None else csr.split_arg(1, a.device)
+        with _Timed(kind, f"rows+d{c1 - c0}" if _EVENT_SINK is not None else None):
+            _lib.check(lib.rgbx_edge_dot_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pa, lda, pb, ldb, _lib.ptr(g), csr.N,
+                                             c1 - c0, None if split is None else ctypes.byref(split), _lib.stream_ptr()),
+                       "rgbx_edge_dot_f32")
+        if c1 < d or total is not None:
+            total = g.clone() if total is None else total.add_(g)
+    return g if total is None else total
+
+
+def gcn_norm_bwd(graph, g_slot):
+    """dL/d edge_weight [E] of a graph.WeightedGraph from dL/dw per forward slot (rgbx_gcn_norm_bwd_f32)."""
+    f, b = graph.fwd, graph.bwd
+    dev = f.rowptr.device
+    dew = torch.empty(max(graph.E, 1), dtype=torch.float32, device=dev)
+    ddeg = torch.empty(max(graph.N, 1), dtype=torch.float32, device=dev)
+    with _Timed("gcn_norm_bwd"):
+        _lib.check(_lib.load().rgbx_gcn_norm_bwd_f32(
+            _lib.ptr(f.rowptr), _lib.ptr(f.col), _lib.ptr(f.perm), _lib.ptr(b.rowptr), _lib.ptr(b.col), _lib.ptr(graph.t2f),
+            _lib.ptr(graph.loops[1]), _lib.ptr(g_slot), _lib.ptr(graph.ew_slot), _lib.ptr(graph.dis), graph.N, graph.E,
+            _lib.ptr(ddeg), _lib.ptr(dew), _lib.stream_ptr()), "rgbx_gcn_norm_bwd_f32")
+    return dew[:graph.E]
+
+
+class _PropagateGCNEdgeWeight(torch.autograd.Function):
+    """A_hat(ew) h with the gradient in the edge weights as well (gcn_norm with edge_weight, dagnn.py:12-31; message
+    dagnn.py:57-59). Forward = the row gather, dh = the transposed gather, d ew = the per-slot dots <dY[i], h[col[p]]>
+    (rgbx_edge_dot_f32) pushed through the normalisation's backward (rgbx_gcn_norm_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, h, edge_weight, graph, bias):
+        ctx.graph, ctx.has_bias = graph, bias is not None
+        ctx.save_for_backward(h)
+        b = None if bias is None else bias.detach().contiguous()
+        return spmm_raw(graph.fwd, graph.w, None, h, kind="gcn_fwd", bias=b)
+
+    @staticmethod
+    def backward(ctx, gy):
+        g = ctx.graph
+        (h,) = ctx.saved_tensors
+        gy = gy.contiguous()
+        gh = spmm_raw(g.bwd, g.w_t, None, gy, kind="gcn_bwd") if ctx.needs_input_grad[0] else None
+        gew = gcn_norm_bwd(g, edge_dot_raw(g.fwd, gy, h)) if ctx.needs_input_grad[1] else None
+        gb = gy.sum(0) if ctx.has_bias and ctx.needs_input_grad[3] else None
+        return gh, gew, None, gb
+
+
+def propagate_gcn_edge_weight(h, edge_weight, graph, bias=None):
+    """A_hat(edge_weight) h (+ bias) for an edge_weight that requires grad; `graph` = get_graph(..., edge_weight)."""
+    hp, d = _pad4(h)
+    out = _PropagateGCNEdgeWeight.apply(hp, edge_weight, graph, _pad4_vec(bias, hp.size(1)))
+    return out if hp is h else out[:, :d]
+
+
 def propagate_mean(x, graph):
     if _is_dist(graph):
         return graph.propagate(x, "mean")
