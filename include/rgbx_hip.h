@@ -19,6 +19,9 @@
  *   rgbx_inv_degree_f32   the 1/max(count,1) of aggr='mean' (models/graphsage.py:39,58) [PyG].
  *   rgbx_spmm_csr_f32     MessagePassing.propagate with aggr='add' / 'mean' and message
  *                         norm * x_j (models/dagnn.py:34-36,46,57-59; models/graphsage.py:58).
+ *   rgbx_spmm_csr_extremum_f32 / rgbx_extremum_bwd_f32
+ *                         the same propagate with aggr='max' / 'min' (the keyword models/graphsage.py:38-40 leaves to
+ *                         the caller) and its backward.
  *   rgbx_appnp_f32        APPNP.forward's K-step recurrence (models/appnp_stack.py:29),
  *                         restated in-repo by models/pta.py:79-84.
  *   rgbx_dagnn_gate_*     Prop.forward's sigmoid-gated mix of the K+1 hops (models/dagnn.py:49-55) and its backward.
@@ -192,6 +195,35 @@ int rgbx_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* w,
 int rgbx_edge_dot_supported(int64_t d);
 int rgbx_edge_dot_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t lda, const float* b, int64_t ldb,
                       float* g, int64_t N, int64_t d, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Max / min neighbourhood aggregation: MessagePassing.propagate with aggr='max' | 'min', the choice my_SAGEConv leaves to
+ * its caller (models/graphsage.py:38-40: kwargs.setdefault('aggr', 'mean'); message x_j at :58) and SAGEConv(aggr=...)
+ * takes as well (models/graphsage2.py:20-23) [PyG].
+ *   out[i,c] = max (min) over the slots p of row i of x[col[p], c];   arg[i,c] = the slot p that supplied it
+ * A row without slots gets out = 0 and arg = -1 (PyG: nodes without in-edges aggregate 0). Ties: the LOWEST slot wins
+ * (strict > / < while walking the slots in order — torch_scatter's CPU scatter_max in edge order, the CSR build being a
+ * stable sort). INPUTS ARE FINITE: there is no NaN policy (a NaN never wins a strict comparison; an infinity of the losing
+ * sign in every slot leaves arg = -1). An extremum involves no rounding: values and arg are exact and the same in every run.
+ * arg: int32 [N, d] (leading dimension d), or NULL = the inference form, which stores nothing extra. d % 4 == 0,
+ * 4 <= d <= 256 (rgbx_spmm_csr_extremum_supported; other widths: pad, or cut into column blocks); x, out, arg 16-byte
+ * aligned, leading dimensions % 4 == 0. `split`: rows above split->threshold are cut into the plan's chunks, one wave each,
+ * and the chunk results are merged in chunk order under the same strict comparison — the split changes neither values nor
+ * arg. split->partial must then hold 2 * n_chunks * d 4-byte words (chunk values, then chunk slots), 16-byte aligned. */
+enum { RGBX_EXTREMUM_MAX = 0, RGBX_EXTREMUM_MIN = 1 };
+int rgbx_spmm_csr_extremum_supported(int64_t d);
+int rgbx_spmm_csr_extremum_f32(const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx, float* out,
+                               int64_t ldo, int32_t* arg, int64_t N, int64_t d, int mode, const rgbx_row_split_t* split,
+                               rgbx_stream_t stream);
+
+/* Source-side backward of rgbx_spmm_csr_extremum_f32 over the TRANSPOSED CSR (rows = sources, col_t = targets) with
+ * t2f[q] = the forward slot of transposed slot q:
+ *   gx[j,c] = sum over the slots q of transposed row j, i = col_t[q], of gout[i,c] * [arg[i,c] == t2f[q]]
+ * Matching the slot, not the source id, keeps duplicate edges j -> i from counting twice. Row-wise sums in a fixed order,
+ * no float atomics: bitwise reproducible. N = rows of the transposed CSR (gx [N, ldgx]); gout / arg are indexed by col_t.
+ * Widths and alignment as the forward; `split` (of the transposed CSR): partial [n_chunks, d], added in chunk order. */
+int rgbx_extremum_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const float* gout, int64_t ldg,
+                          const int32_t* arg, float* gx, int64_t ldgx, int64_t N, int64_t d, const rgbx_row_split_t* split,
+                          rgbx_stream_t stream);
 
 /* rgbx_spmm_csr_f32 with an epilogue over the finished output rows, for layers that transform BEFORE they aggregate
  * (in > out — every default configuration of the reference, initial_params.py:25-29: F -> 64 -> C with C = 7, 6, 3, 40 ...),

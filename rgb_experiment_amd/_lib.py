@@ -64,6 +64,9 @@ SIGNATURES = {
     "rgbx_edge_dot_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P],
     "rgbx_gcn_norm_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P],
     "rgbx_spmm_csr_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P],
+    "rgbx_spmm_csr_extremum_supported": [_I64],
+    "rgbx_spmm_csr_extremum_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
+    "rgbx_extremum_bwd_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P],
     "rgbx_spmm_csr_epilogue_supported": [_I64],
     "rgbx_spmm_csr_epilogue_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P],
     "rgbx_spmm_csr_short_rows_supported": [_I64],

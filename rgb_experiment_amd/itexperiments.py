@@ -312,6 +312,9 @@ def experiment(model_init_param: dict, *,
     dist_ctx = None
     if distributed and use_edge_weight:
         raise NotImplementedError("use_edge_weight=True is not implemented on the partitioned (distributed) route")
+    if distributed and model is None and (model_init_param or {}).get("aggr", "mean") != "mean":
+        raise NotImplementedError(f"aggr={model_init_param['aggr']!r} is not implemented on the partitioned (distributed) "
+                                  "route: its exchange carries sums")
     if distributed:
         from .dist.experiment import DistContext
         dist_ctx = DistContext.open(name, post_cs, use_cpu)  # process group, rank's device; raises for unsupported set-ups

@@ -184,9 +184,12 @@ def _layer_maps(conv):
     """(W_l [out, in], W_r [out, in] or None, b [out], aggregation kind, self-loop rewrite) of a conv layer that is
     `A(x) W_l^T + x W_r^T + b` with a row-wise aggregation A, or None: GCNConv (A = A_hat, no root term), my_SAGEConv (mean
     over N(i) and i itself — its b_l sits inside the mean, whose rows sum to 1: models/graphsage.py:49-62), SAGEConv (mean over
-    N(i), lin_l's bias outside it [PyG])."""
+    N(i), lin_l's bias outside it [PyG]). A SAGE layer with aggr other than 'mean' has no such form: a max is not a
+    polynomial in an operator, and the sum's rows do not add up to 1."""
     from ..graph import LOOPS_ADD_REMAINING, LOOPS_KEEP, LOOPS_REMOVE_ADD
     name = type(conv).__name__
+    if getattr(conv, "aggr", "mean") != "mean":
+        return None
     if name == "GCNConv":
         return conv.lin.weight, None, conv.bias, "gcn", LOOPS_ADD_REMAINING
     if name == "MySAGEConv" and conv.add_self_loops:

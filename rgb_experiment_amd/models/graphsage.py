@@ -6,6 +6,9 @@ my_SAGEConv = MySAGEConv  # the reference's class name
 
 
 class GraphSAGE(ConvStack):
-    def __init__(self, num_layers, hidden_unit, input_dim, output_dim, dropout_rate):
+    """`aggr` ('mean' | 'max' | 'min' | 'add' | 'sum') goes to every conv: the keyword my_SAGEConv leaves to its caller
+    (models/graphsage.py:38-40). It reaches this constructor through experiment()'s model_init_param."""
+
+    def __init__(self, num_layers, hidden_unit, input_dim, output_dim, dropout_rate, aggr="mean"):
         widths = [input_dim] + [hidden_unit] * (num_layers - 1) + [output_dim]
-        super().__init__(num_layers, dropout_rate, widths, lambda i, a, b: MySAGEConv(a, b), hidden_unit)
+        super().__init__(num_layers, dropout_rate, widths, lambda i, a, b: MySAGEConv(a, b, aggr=aggr), hidden_unit)

@@ -4,6 +4,8 @@ from ._stack import ConvStack
 
 
 class GraphSAGE2(ConvStack):
-    def __init__(self, num_layers, hidden_unit, input_dim, output_dim, dropout_rate):
+    """`aggr` ('mean' | 'max' | 'min' | 'add' | 'sum') goes to every conv (PyG SAGEConv's keyword)."""
+
+    def __init__(self, num_layers, hidden_unit, input_dim, output_dim, dropout_rate, aggr="mean"):
         widths = [input_dim] + [hidden_unit] * (num_layers - 1) + [output_dim]
-        super().__init__(num_layers, dropout_rate, widths, lambda i, a, b: SAGEConv(a, b), hidden_unit)
+        super().__init__(num_layers, dropout_rate, widths, lambda i, a, b: SAGEConv(a, b, aggr=aggr), hidden_unit)

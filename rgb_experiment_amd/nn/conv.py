@@ -36,6 +36,39 @@ def _no_weight_grad(edge_weight, who):
                          "GCNConv only)")
 
 
+AGGRS = {"mean": "mean", "max": "max", "min": "min", "add": "add", "sum": "add"}  # accepted keyword -> canonical name
+
+
+def _set_aggr(conv, aggr):
+    """The `aggr` keyword of the SAGE layers (reference models/graphsage.py:38-40: kwargs.setdefault('aggr', 'mean'), the
+    caller may choose; PyG's SAGEConv takes the same keyword). 'mean' leaves the layer exactly as it is. The others run
+    composed (ops.propagate_max / propagate_min / propagate_sum between the dense products): the loss-in-kernel, folded,
+    cached-aggregate and fused aggregate + transform forms are all forms of a weighted row SUM with rows that sum to 1, so
+    this instance switches them off."""
+    if aggr not in AGGRS:
+        raise ValueError(f"{type(conv).__name__}: aggr must be one of {sorted(AGGRS)}, got {aggr!r}")
+    conv.aggr = AGGRS[aggr]
+    if conv.aggr != "mean":
+        conv.accepts_ce = conv.accepts_ce_pair = conv.folds_post_affine = conv.emits_colsums = False
+
+
+def _aggregate(x, graph, aggr):
+    """The non-mean neighbourhood reductions of the SAGE layers over `graph` (single GPU)."""
+    if getattr(graph, "is_distributed", False):
+        raise NotImplementedError(f"aggr='{aggr}' is not implemented on the partitioned (distributed) route")
+    if aggr == "add":
+        return ops.propagate_sum(x, graph)
+    return ops.propagate_max(x, graph) if aggr == "max" else ops.propagate_min(x, graph)
+
+
+def _finish_composed(out, post_affine, ce):
+    """What a caller of the composed forward may still have asked of the layer (the conv stack asks neither of an instance
+    that reports no such form): an eval BatchNorm's affine map on the output, the masked cross-entropy from the logits."""
+    if post_affine is not None:
+        out = out * post_affine[0] + post_affine[1]
+    return out if ce is None else ops.ce_from_logits(out, ce[0], ce[1])
+
+
 def _forward_folded(conv, x, edge_index, operands, ce, loops_mode, kind, root, edge_weight=None):
     """Eval forward of a GCN / SAGE layer from prepared operands (W'^T, b', Wr'^T): ONE rgbx_fused_layer_f32 launch, no
     autograd node, no weight arithmetic on the way. Returns None when the fused kernel does not apply."""
@@ -209,14 +242,19 @@ class GCNConv(nn.Module):
 
 class SAGEConv(nn.Module):
     """out = lin_l(mean_{j in N(i)} x_j) + lin_r(x_i); no self-loops; nodes without in-edges
-    aggregate 0 [PyG SAGEConv defaults: aggr='mean', root_weight=True, lin_l bias, lin_r no bias]."""
+    aggregate 0 [PyG SAGEConv defaults: aggr='mean', root_weight=True, lin_l bias, lin_r no bias].
+
+    ``aggr`` in {'mean', 'max', 'min', 'add'} ('sum' = 'add'): PyG's keyword. Other than 'mean' the layer runs in PyG's
+    order on separate kernels — aggregate the raw x (ops.propagate_max / propagate_min / propagate_sum), then
+    lin_l(agg) + lin_r(x) — and reports none of the fused forms (see _set_aggr)."""
 
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # see GCNConv
 
-    def __init__(self, in_channels, out_channels):
+    def __init__(self, in_channels, out_channels, aggr="mean"):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
+        _set_aggr(self, aggr)
         self.lin_l = nn.Linear(in_channels, out_channels, bias=True)
         self.lin_r = nn.Linear(in_channels, out_channels, bias=False)
 
@@ -224,12 +262,21 @@ class SAGEConv(nn.Module):
     accepts_ce_pair = True
 
     def eval_operands(self, bn=None):
+        if self.aggr != "mean":
+            return None
         return ops.fold_bn_linear(self.lin_l.weight, self.lin_l.bias, root_weight=self.lin_r.weight, bn=bn)
 
     def aggregate_input(self, x, edge_index):
-        if self.in_channels > self.out_channels or not ops.aggregate_linear_ok(self.in_channels, self.out_channels, True):
+        if (self.aggr != "mean" or self.in_channels > self.out_channels
+                or not ops.aggregate_linear_ok(self.in_channels, self.out_channels, True)):
             return None
         return _aggregate_input(x, edge_index, LOOPS_KEEP, "mean")
+
+    def _forward_composed(self, x, edge_index):
+        """aggr != 'mean': PyG's order — the reduction over the raw rows, then both Linears."""
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        agg = _aggregate(x, graph, self.aggr)
+        return ops.linear(agg, self.lin_l.weight, self.lin_l.bias) + ops.linear(x, self.lin_r.weight)
 
     def forward_from_aggregate(self, z, x, want_colsums=False, folded=None):
         if folded is not None:
@@ -238,6 +285,8 @@ class SAGEConv(nn.Module):
 
     def forward_folded(self, x, edge_index, operands, ce=None):
         """See GCNConv.forward_folded."""
+        if self.aggr != "mean":
+            return None
         return _forward_folded(self, x, edge_index, operands, ce, LOOPS_KEEP, "mean", True)
 
     def _ce(self, x, edge_index, ce, bn, colsums):
@@ -266,6 +315,8 @@ class SAGEConv(nn.Module):
 
     def forward_after_bn(self, x, edge_index, bn, colsums=None, want_colsums=False, ce=None):
         """See GCNConv.forward_after_bn; the root term lin_r(bn(x)_i) gets the affine map as its rows are loaded."""
+        if self.aggr != "mean":
+            return _finish_composed(self._forward_composed(bn(x, colsums=colsums), edge_index), None, ce)
         if ce is not None:
             return self._ce(x, edge_index, ce, bn, colsums)
         graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
@@ -276,6 +327,8 @@ class SAGEConv(nn.Module):
         return self.forward(bn(x, colsums=colsums), edge_index, want_colsums=want_colsums)
 
     def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None):
+        if self.aggr != "mean":
+            return _finish_composed(self._forward_composed(x, edge_index), post_affine, ce)
         if ce is not None:
             return self._ce(x, edge_index, ce, None, None)
         w_l, b_l, w_r = self.lin_l.weight, self.lin_l.bias, self.lin_r.weight
@@ -303,29 +356,43 @@ class SAGEConv(nn.Module):
 
 class MySAGEConv(nn.Module):
     """reference models/graphsage.py:36-62: x_l = lin_l(x), x_r = lin_r(x) (both with bias),
-    remove_self_loops + add_self_loops, mean over N(i) ∪ {i} of x_l, then += x_r."""
+    remove_self_loops + add_self_loops, mean over N(i) ∪ {i} of x_l, then += x_r.
+
+    ``aggr`` in {'mean', 'max', 'min', 'add'} ('sum' = 'add'): the keyword the reference leaves to the caller
+    (graphsage.py:38-40). Other than 'mean' the layer runs in the reference's order on separate kernels — [lin_l(x),
+    lin_r(x)] in one product, the reduction over the left half (ops.propagate_max / propagate_min / propagate_sum),
+    += x_r — and reports none of the fused forms (see _set_aggr)."""
 
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # see GCNConv
 
-    def __init__(self, in_channels, out_channels, add_self_loops=True):
+    def __init__(self, in_channels, out_channels, add_self_loops=True, aggr="mean"):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.add_self_loops = add_self_loops
+        _set_aggr(self, aggr)
         self.lin_l = nn.Linear(in_channels, out_channels)
         self.lin_r = nn.Linear(in_channels, out_channels)
 
     accepts_ce = True         # see GCNConv
     accepts_ce_pair = True
 
+    def _forward_composed(self, x, edge_index):
+        """aggr != 'mean': the reference's order (graphsage.py:49-60) — transform, reduce x_l over N(i) (and i itself
+        with add_self_loops), += x_r."""
+        graph = get_graph(edge_index, x.size(0), LOOPS_REMOVE_ADD if self.add_self_loops else LOOPS_KEEP)
+        h, n = self._transform_both(x, self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, self.lin_r.bias)
+        out = _aggregate(h[:, :n], graph, self.aggr) + h[:, n:]
+        return out if n == self.out_channels else out[:, :self.out_channels]
+
     def eval_operands(self, bn=None):
-        if not self.add_self_loops:
+        if not self.add_self_loops or self.aggr != "mean":
             return None
         return ops.fold_bn_linear(self.lin_l.weight, self.lin_l.bias, self.lin_r.bias, root_weight=self.lin_r.weight,
                                   bn=bn)
 
     def aggregate_input(self, x, edge_index):
-        if (not self.add_self_loops or self.in_channels > self.out_channels
+        if (not self.add_self_loops or self.aggr != "mean" or self.in_channels > self.out_channels
                 or not ops.aggregate_linear_ok(self.in_channels, self.out_channels, True)):
             return None
         return _aggregate_input(x, edge_index, LOOPS_REMOVE_ADD, "mean")
@@ -339,6 +406,8 @@ class MySAGEConv(nn.Module):
     def forward_folded(self, x, edge_index, operands, ce=None):
         """See GCNConv.forward_folded (mean over N(i) + {i}: the weights of a row sum to 1, so both biases and the
         BatchNorm shift ride in the kernel's bias)."""
+        if self.aggr != "mean":
+            return None
         return _forward_folded(self, x, edge_index, operands, ce, LOOPS_REMOVE_ADD, "mean", True)
 
     def _ce(self, x, edge_index, ce, bn, colsums):
@@ -370,6 +439,8 @@ class MySAGEConv(nn.Module):
 
     def forward_after_bn(self, x, edge_index, bn, colsums=None, want_colsums=False, ce=None):
         """See GCNConv.forward_after_bn."""
+        if self.aggr != "mean":
+            return _finish_composed(self._forward_composed(bn(x, colsums=colsums), edge_index), None, ce)
         if ce is not None:
             return self._ce(x, edge_index, ce, bn, colsums)
         if self.add_self_loops:
@@ -382,6 +453,8 @@ class MySAGEConv(nn.Module):
         return self.forward(bn(x, colsums=colsums), edge_index, want_colsums=want_colsums)
 
     def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None):
+        if self.aggr != "mean":
+            return _finish_composed(self._forward_composed(x, edge_index), post_affine, ce)
         if ce is not None:
             return self._ce(x, edge_index, ce, None, None)
         w_l, b_l, w_r, b_r = self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, self.lin_r.bias

@@ -273,6 +273,115 @@ def propagate_sum(x, graph):
     return out if xp is x else out[:, :d]
 
 
+# ---- max / min over the neighbourhood (aggr='max' | 'min') --------------------------------------------------------------
+
+EXTREMUM_MODES = {"max": 0, "min": 1}  # RGBX_EXTREMUM_MAX / RGBX_EXTREMUM_MIN
+
+
+def _vec4_rows(t):
+    """`t` as a matrix the 16-byte row kernels can read: unit column stride, row stride % 4 == 0, 16-byte aligned."""
+    ok = t.stride(-1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.size(1) and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+def spmm_extremum_raw(csr, x, mode, want_arg, kind=None):
+    """(out [N, d], arg int32 [N, d] or None): out[i, c] = max / min over the slots p of row i of x[col[p], c], arg the
+    slot that supplied it (lowest slot on ties; rows without slots: 0 / -1). No autograd; rgbx_spmm_csr_extremum_f32.
+    `x` has a width that is a multiple of 4 (callers pad, cf. _pad4); widths above 256 run in column blocks of 256 (an
+    extremum is taken per column). `want_arg=False` is the inference form: no arg is allocated or written."""
+    if mode not in EXTREMUM_MODES:
+        raise ValueError(f"mode must be 'max' or 'min', got {mode!r}")
+    _lib.require_device(x)
+    x = _vec4_rows(x)
+    N, d = csr.N, x.size(1)
+    if d % 4:
+        raise RuntimeError(f"spmm_extremum_raw: width {d} is no multiple of 4 (pad the rows)")
+    out = torch.empty((N, d), dtype=torch.float32, device=x.device)
+    arg = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_arg else None
+    lib = _lib.load()
+    for c0 in range(0, d, 256):
+        c1 = min(c0 + 256, d)
+        w = c1 - c0
+        px, ldx = _lib.mat(x[:, c0:c1], "x")
+        po, ldo = _lib.mat(out[:, c0:c1], "out")
+        # one column block's arg rows are [N, w] with leading dimension w: a block of a wider matrix gets its own buffer
+        blk = arg if (arg is None or w == d) else torch.empty((N, w), dtype=torch.int32, device=x.device)
+        split, _scratch = csr.split_arg(2 * w, x.device)  # chunk values + chunk slots
+        with _Timed(kind or f"{mode}_fwd", f"rows+d{w}" + ("+arg" if want_arg else "") if _EVENT_SINK is not None else None):
+            _lib.check(lib.rgbx_spmm_csr_extremum_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), px, ldx, po, ldo,
+                                                      _lib.ptr(blk), N, w, EXTREMUM_MODES[mode],
+                                                      None if split is None else ctypes.byref(split), _lib.stream_ptr()),
+                       "rgbx_spmm_csr_extremum_f32")
+        if blk is not arg:
+            arg[:, c0:c1] = blk
+    return out, arg
+
+
+def extremum_bwd_raw(graph, gout, arg, kind="extremum_bwd"):
+    """gx[j, c] = sum over the out-edges q of j (target i) of gout[i, c] * [arg[i, c] == forward slot of q], over the
+    transposed CSR (rgbx_extremum_bwd_f32; fixed summation order, no atomics). No autograd."""
+    _lib.require_device(gout, arg)
+    csr, t2f = graph.bwd, graph.t2f
+    gout = _vec4_rows(gout)
+    d = gout.size(1)
+    gx = torch.empty((csr.N, d), dtype=torch.float32, device=gout.device)
+    lib = _lib.load()
+    for c0 in range(0, d, 256):
+        c1 = min(c0 + 256, d)
+        w = c1 - c0
+        pg, ldg = _lib.mat(gout[:, c0:c1], "gout")
+        px, ldgx = _lib.mat(gx[:, c0:c1], "gx")
+        blk = arg if w == d else arg[:, c0:c1].contiguous()
+        split, _scratch = csr.split_arg(w, gout.device)
+        with _Timed(kind, f"rows+d{w}" if _EVENT_SINK is not None else None):
+            _lib.check(lib.rgbx_extremum_bwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(t2f), pg, ldg,
+                                                 _lib.ptr(blk), px, ldgx, csr.N, w,
+                                                 None if split is None else ctypes.byref(split), _lib.stream_ptr()),
+                       "rgbx_extremum_bwd_f32")
+    return gx
+
+
+class _PropagateExtremum(torch.autograd.Function):
+    """max / min over incoming edges (aggr='max' | 'min'; graphsage.py:38-40 leaves the aggregator to the caller). The
+    forward keeps the winning slot of every (row, column) only when a gradient will be asked for; the backward routes
+    gout through those slots over the transposed CSR."""
+
+    @staticmethod
+    def forward(ctx, x, graph, mode, want):
+        ctx.graph = graph
+        out, arg = spmm_extremum_raw(graph.fwd, x, mode, want)
+        if want:
+            graph.t2f  # built here, outside the backward (its construction reads sizes back to the host)
+            ctx.save_for_backward(arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        (arg,) = ctx.saved_tensors
+        return extremum_bwd_raw(ctx.graph, gy, arg), None, None, None
+
+
+def _propagate_extremum(x, graph, mode):
+    if _is_dist(graph):
+        raise NotImplementedError(f"aggr='{mode}' is not implemented on the partitioned (distributed) route")
+    _lib.require_device(x)
+    xp, d = _pad4(x)
+    # decided here: inside a Function's forward the grad mode is always off and cannot tell no_grad from training
+    want = torch.is_grad_enabled() and xp.requires_grad
+    out = _PropagateExtremum.apply(xp, graph, mode, want)
+    return out if xp is x else out[:, :d]
+
+
+def propagate_max(x, graph):
+    """out[i] = max_{j in N(i)} x[j] per column over `graph` (0 where i has no in-edge)."""
+    return _propagate_extremum(x, graph, "max")
+
+
+def propagate_min(x, graph):
+    """out[i] = min_{j in N(i)} x[j] per column over `graph` (0 where i has no in-edge)."""
+    return _propagate_extremum(x, graph, "min")
+
+
 # ---- propagate of an already transformed matrix, with the passes that follow it taken in the same kernel --------------
 
 def pad_rows4(weight, *vectors):
