@@ -27,6 +27,7 @@
  *   rgbx_dagnn_gate_*     Prop.forward's sigmoid-gated mix of the K+1 hops (models/dagnn.py:49-55) and its backward.
  *   rgbx_gat_*            GATConv.forward/message + segment softmax (models/gat.py:28,30) [PyG].
  *   rgbx_supergat_*       SuperGATConv ('MX' attention, attention loss, negative sampling; models/supergat.py) [PyG].
+ *   rgbx_gatv2_*          GATv2Conv (dynamic attention) [PyG]; not in the reference's zoo, shaped like models/gat.py.
  *   rgbx_gemm_tn_f32      dW = dY^T X of the nn.Linear / conv.lin layers under loss.backward()
  *                         (itexperiments.py:439; layers at models/gcn.py:18-21, appnp_stack.py:19-20).
  *   rgbx_bn_* / rgbx_affine_cols_f32
@@ -655,6 +656,64 @@ int rgbx_supergat_neg_loss_bwd_f32(const float* hfeat, int64_t ldh, const int64_
 /* pos[p] = 1 where slot p is a kept positive, drop[p * H + h] = 1 where (p, h) survives the attention dropout. */
 int rgbx_supergat_draws_u8(const uint32_t* seed, int64_t nnz, int H, float p_drop, float pos_ratio, uint8_t* pos,
                            uint8_t* drop, rgbx_stream_t stream);
+
+/* ---- GATv2: dynamic attention (the non-linearity in front of the attention vector) ---------------------------- */
+
+/* For an edge j -> i (p = its slot in the target-grouped CSR) and head h, with xl, xr [N, H*C] and att [H*C]:
+ *   s_p[c] = xl[j,h,c] + xr[i,h,c]
+ *   e_p    = sum_c att[h,c] * leaky_relu(s_p[c], slope)
+ *   alpha  = softmax over the in-edges of i of e_p, as rgbx_gat_aggregate_fwd_f32 forms it
+ *   out[i,h,:] = sum_p alpha_p * kappa_p * xl[j,h,:] (+ bias)
+ * (GATv2Conv.forward / edge_update / message [PyG]; Brody et al. 2022. The reference's zoo has no GATv2: the layer
+ * sits where models/gat.py puts GATConv.) The score is no sum of per-node scalars, so every gathered xl row is scored
+ * against the target's xr row in registers; the same row is the message.
+ *
+ * Attention dropout. `seed` points to two 32-bit words ON THE DEVICE; NULL = no dropout (kappa = 1). Otherwise
+ * kappa_p[h] = keep / (1 - p_drop) with keep a hash of (seed, forward CSR slot, head), true with probability
+ * 1 - p_drop; the backward passes recompute it and every score, so nothing per edge is stored.
+ * rgbx_gatv2_draws_u8 writes the keep bits out for inspection. No entry point uses float atomics: two runs are
+ * bit-identical. */
+
+/* 1 if the kernels take H heads of C channels (as GATConv.kernel_channels: any C <= 64, even C <= 128, C % 4 == 0 up
+ * to 256), else 0. Other widths are padded per head by the caller. */
+int rgbx_gatv2_supported(int H, int C);
+
+/* Forward over the target-grouped CSR: one gather pass with an online softmax. m / rden ([N, H], of the UNDROPPED
+ * softmax) are saved for the backward; both NULL = inference form (and then seed must be NULL). `bias` ([H*C],
+ * optional) is added in the store. `split`: hub rows as in rgbx_gat_aggregate_fwd_f32; split->partial holds
+ * n_chunks * (H*C + 2*H) floats. Float pointers that are not 4-byte aligned: RGBX_E_ALIGN. */
+int rgbx_gatv2_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* xl, int64_t ldl, const float* xr,
+                       int64_t ldr, const float* att, const float* bias, float* out, int64_t ldo, float* m, float* rden,
+                       int64_t N, int H, int C, float slope, const uint32_t* seed, float p_drop,
+                       const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Floats of the `att_partial` workspace of rgbx_gatv2_bwd_dst_f32: one [H*C] record per workgroup. */
+int rgbx_gatv2_att_partial_floats(int64_t N, int H, int C, const rgbx_row_split_t* split, int64_t* count);
+
+/* Backward. Per edge and head, with D_i = <gout_i, out_i - bias>:
+ *   de = alpha (kappa <gout_i, xl_j> - D_i),   ds[c] = de att[h,c] lrelu'(s[c])
+ * Target side, over the forward CSR: g_xr[i,h,:] = sum_p ds, g_att[h,c] = sum over all edges of de lrelu(s[c]) (per
+ * workgroup records in att_partial, added in record order), and the record nodeq[i,h] = (m - log(rden), D_i)
+ * ([N, H, 2], 8-byte aligned) of the source side. split->partial holds n_chunks * H*C floats. */
+int rgbx_gatv2_bwd_dst_f32(const int32_t* rowptr, const int32_t* col, const float* xl, int64_t ldl, const float* xr,
+                           int64_t ldr, const float* att, const float* m, const float* rden, const float* out,
+                           int64_t ldo, const float* bias, const float* gout, int64_t ldg, float* nodeq, float* g_xr,
+                           int64_t ldgr, float* g_att, float* att_partial, int64_t n_att_partial, int64_t N, int H,
+                           int C, float slope, const uint32_t* seed, float p_drop, const rgbx_row_split_t* split,
+                           rgbx_stream_t stream);
+
+/* Source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i), run AFTER the target side:
+ *   g_xl[j,h,:] = sum_p (alpha_p kappa_p gout[i,h,:] + ds_p).
+ * `t2f` ([E'], needed when seed != NULL): the forward CSR slot of every transposed slot (the key of its keep bit).
+ * split->partial holds n_chunks * H*C floats. */
+int rgbx_gatv2_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const float* xl,
+                           int64_t ldl, const float* xr, int64_t ldr, const float* att, const float* nodeq,
+                           const float* gout, int64_t ldg, float* g_xl, int64_t ldgl, int64_t N, int H, int C,
+                           float slope, const uint32_t* seed, float p_drop, const rgbx_row_split_t* split,
+                           rgbx_stream_t stream);
+
+/* keep[p * H + h] = 1 where (forward CSR slot p, head h) survives the attention dropout. */
+int rgbx_gatv2_draws_u8(const uint32_t* seed, int64_t nnz, int H, float p_drop, uint8_t* keep, rgbx_stream_t stream);
 
 /* ---- dense layers on the MFMA units -------------------------------------------------------- */
 

@@ -108,6 +108,14 @@ SIGNATURES = {
     "rgbx_supergat_neg_loss_fwd_f32": [_P, _I64, _P, _P, _I64, _I, _I, _P, _I64, _P, _P],
     "rgbx_supergat_neg_loss_bwd_f32": [_P, _I64, _P, _P, _I64, _I, _I, _P, _P, _I64, _P],
     "rgbx_supergat_draws_u8": [_P, _I64, _I, _F, _F, _P, _P, _P],
+    "rgbx_gatv2_supported": [_I, _I],
+    "rgbx_gatv2_fwd_f32": [_P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _I, _I, _F, _P, _F, _P, _P],
+    "rgbx_gatv2_att_partial_floats": [_I64, _I, _I, _P, ctypes.POINTER(ctypes.c_int64)],
+    "rgbx_gatv2_bwd_dst_f32": [_P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64,
+                               _I64, _I, _I, _F, _P, _F, _P, _P],
+    "rgbx_gatv2_bwd_src_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I64, _I, _I, _F, _P, _F, _P,
+                               _P],
+    "rgbx_gatv2_draws_u8": [_P, _I64, _I, _F, _P, _P],
     "rgbx_gemm_tn_workspace_bytes": [_I64, _I64, _I64, ctypes.POINTER(ctypes.c_size_t)],
     "rgbx_gemm_tn_f32": [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _F, _P, ctypes.c_size_t, _P],
     "rgbx_bn_scratch_doubles": [_I64, _I64, ctypes.POINTER(ctypes.c_int64)],

@@ -794,6 +794,88 @@ class SuperGATConv(nn.Module):
         return out
 
 
+class GATv2Conv(nn.Module):
+    """GATv2's layer [PyG GATv2Conv; Brody et al., "How Attentive are Graph Attention Networks?"]: x_l = lin_l(x),
+    x_r = lin_r(x) viewed [N,H,C]; for an edge j -> i: e_ij = <att, LeakyReLU(x_l[j] + x_r[i])> per head — the
+    non-linearity in front of the attention vector, so the ranking of the neighbours depends on the target; softmax over
+    the in-edges of i (self-loops removed then re-added), dropout on the coefficients, out_i = sum_j alpha_ij x_l[j];
+    heads concatenated or averaged; + bias. Parameter names are PyG's (lin_l, lin_r, att, bias; lin_r is lin_l with
+    share_weights). All of it runs in the rgbx_gatv2_* kernels (ops.gatv2_attend)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0,
+                 add_self_loops=True, bias=True, share_weights=False, *, edge_dim=None, residual=False):
+        super().__init__()
+        if not add_self_loops:
+            raise NotImplementedError("GATv2Conv: add_self_loops=False is not built")
+        if edge_dim is not None:
+            raise NotImplementedError("GATv2Conv: edge features (edge_dim) are not built")
+        if residual:
+            raise NotImplementedError("GATv2Conv: residual=True is not built")
+        if not (0.0 <= dropout < 1.0):
+            raise ValueError("GATv2Conv: dropout in [0, 1)")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.heads, self.concat, self.negative_slope, self.dropout = heads, concat, negative_slope, dropout
+        self.add_self_loops, self.share_weights = add_self_loops, share_weights
+        self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.lin_r = self.lin_l if share_weights else nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.last_draw = {}  # dropout seed of the last forward (ops.gatv2_random_choices)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.lin_l, self.lin_r):
+            glorot_(lin.weight)
+            if lin.bias is not None:
+                nn.init.zeros_(lin.bias)
+        glorot_(self.att)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def _padded(self, lin, Cp):
+        """(weight, bias) of a projection with every head padded to Cp channels by zero rows / entries."""
+        H, C = self.heads, self.out_channels
+        if Cp == C:
+            return lin.weight, lin.bias
+        pad = torch.nn.functional.pad
+        weight = pad(lin.weight.view(H, C, -1), (0, 0, 0, Cp - C)).reshape(H * Cp, -1)
+        return weight, None if lin.bias is None else pad(lin.bias.view(H, C), (0, Cp - C)).reshape(-1)
+
+    def forward(self, x, edge_index):
+        _lib.require_device(x)
+        H, C = self.heads, self.out_channels
+        Cp = GATConv.kernel_channels(C)  # other widths: zero weight rows, attention entries and bias per head
+        F = H * Cp
+        graph = get_graph(edge_index, x.size(0), LOOPS_REMOVE_ADD)
+        in_kernel = self.bias is not None and (self.concat or H == 1)  # the bias rides in the aggregation kernel's store
+        att, bias = self.att, self.bias
+        w_l, b_l = self._padded(self.lin_l, Cp)
+        if Cp != C:
+            pad = torch.nn.functional.pad
+            att = pad(att, (0, Cp - C))
+            if in_kernel:
+                bias = pad(bias.view(H, C), (0, Cp - C)).reshape(-1)
+        if self.share_weights:
+            xl = xr = ops.linear(x, w_l, b_l)
+        else:  # one product over [W_l; W_r]; x_l and x_r are its column blocks
+            w_r, b_r = self._padded(self.lin_r, Cp)
+            h = ops.linear(x, torch.cat([w_l, w_r]), None if b_l is None else torch.cat([b_l, b_r]))
+            xl, xr = h[:, :F], h[:, F:]
+        self.last_draw = {}
+        out = ops.gatv2_attend(xl, xr, att, graph, H, Cp, self.negative_slope, bias=bias if in_kernel else None,
+                               training=self.training, p_drop=self.dropout, record=self.last_draw)
+        if Cp != C:
+            out = out.view(-1, H, Cp)[:, :, :C].reshape(-1, H * C)
+        if not self.concat and H > 1:
+            out = out.view(-1, H, C).mean(dim=1)
+        if self.bias is not None and not in_kernel:
+            out = out + self.bias
+        return out
+
+
 class FAConv(nn.Module):
     """FAGCN's layer [PyG FAConv; reference models/fagcn.py]: for an edge j -> i of the GCN-normalised graph (self-loops
     removed then re-added, w_ij = 1/sqrt(d_i d_j)), a_ij = tanh(<x_j, att_l> + <x_i, att_r>) — signed, no softmax —

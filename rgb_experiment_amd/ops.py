@@ -2168,6 +2168,136 @@ def supergat_attend(h, att_l, att_r, graph, H, C, slope=0.2, bias=None, training
                                  neg_edge_index, record)
 
 
+def _gatv2_split(csr, width, dev):
+    split, scratch = csr.split_arg(width, dev)
+    return (None if split is None else ctypes.byref(split)), split, scratch
+
+
+def gatv2_random_choices(record, graph, H):
+    """The attention-dropout decisions of the training forward that filled `record` (GATv2Conv keeps the record of its
+    last forward): {'keep': bool [E', H] in forward CSR slot order (True = kept), 'src' / 'dst': int64 [E'] endpoints of
+    every forward CSR slot}."""
+    csr = graph.fwd
+    dev, nnz = csr.rowptr.device, csr.nnz
+    if record.get("seed") is None:
+        keep = torch.ones((nnz, H), dtype=torch.uint8, device=dev)
+    else:
+        keep = torch.empty((nnz, H), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().rgbx_gatv2_draws_u8(_lib.ptr(record["seed"]), nnz, H, float(record["p_drop"]),
+                                                   _lib.ptr(keep), _lib.stream_ptr()), "rgbx_gatv2_draws_u8")
+    deg = (csr.rowptr[1:] - csr.rowptr[:-1]).long()
+    return {"keep": keep.bool(), "src": csr.col[:nnz].long(),
+            "dst": torch.repeat_interleave(torch.arange(csr.N, device=dev), deg)}
+
+
+class _GATv2Attend(torch.autograd.Function):
+    """One GATv2Conv attention block as a single autograd node: fused score + edge-softmax + aggregation (+ attention
+    dropout in training mode); backward = target-side pass (g_xr, g_att), source-side pass (g_xl). Saves xl, xr, att,
+    out, m / rden [N, H] and the dropout seed; nothing per edge (the backward recomputes scores and keep bits)."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, graph, H, C, slope, bias, train, p_drop, record, want_grad):
+        _lib.require_device(xl, xr, att, bias)
+        lib = _lib.load()
+        xl = xl if xl.dim() == 2 and xl.stride(1) == 1 else xl.contiguous()  # column blocks of one product stay views
+        xr = xr if xr.dim() == 2 and xr.stride(1) == 1 else xr.contiguous()
+        b = None if bias is None else bias.detach().reshape(H * C).contiguous()
+        a = att.detach().reshape(H * C).contiguous()
+        csr, N, dev = graph.fwd, graph.fwd.N, xl.device
+        if xl.size(0) != N or xr.size(0) != N or xl.size(1) != H * C or xr.size(1) != H * C:
+            raise RuntimeError(f"gatv2_attend: xl {tuple(xl.shape)} / xr {tuple(xr.shape)} for a graph of {N} nodes and "
+                               f"{H} x {C} channels")
+        seed = None
+        if train and p_drop > 0.0:
+            # two 32-bit words from torch's device generator (torch.manual_seed makes the run repeatable; under a
+            # hipGraph capture the generator's offset advances with every replay); they stay on the device
+            seed = torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32, device=dev)
+        if record is not None:
+            record.update(seed=seed, p_drop=float(p_drop))
+        out = torch.empty((N, H * C), dtype=torch.float32, device=dev)
+        # m / rden are the backward's; without one the kernel runs its inference form
+        m = torch.empty((N, H), dtype=torch.float32, device=dev) if want_grad or seed is not None else None
+        rden = None if m is None else torch.empty_like(m)
+        pl, ldl = _lib.mat(xl, "xl")
+        pr, ldr = _lib.mat(xr, "xr")
+        po, ldo = _lib.mat(out, "out")
+        split_ref, split, _scratch = _gatv2_split(csr, H * C + 2 * H, dev)
+        with _Timed("gatv2_fwd"):
+            _lib.check(lib.rgbx_gatv2_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pl, ldl, pr, ldr, _lib.ptr(a),
+                                              _lib.ptr(b), po, ldo, _lib.ptr(m), _lib.ptr(rden), N, H, C, float(slope),
+                                              _lib.ptr(seed), float(p_drop), split_ref, _lib.stream_ptr()),
+                       "rgbx_gatv2_fwd_f32")
+        ctx.graph, ctx.H, ctx.C, ctx.slope, ctx.p_drop = graph, H, C, float(slope), float(p_drop)
+        ctx.att_shape = att.shape
+        ctx.bias_shape = None if bias is None else bias.shape
+        ctx.save_for_backward(xl, xr, a, b, m, rden, out, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        xl, xr, a, b, m, rden, out, seed = ctx.saved_tensors
+        g, H, C, slope, p_drop = ctx.graph, ctx.H, ctx.C, ctx.slope, ctx.p_drop
+        lib = _lib.load()
+        N, dev = g.fwd.N, xl.device
+        F = H * C
+        gout = gout.contiguous()
+        nodeq = torch.empty((N, H, 2), dtype=torch.float32, device=dev)
+        g_xl = torch.empty((N, F), dtype=torch.float32, device=dev)
+        g_xr = torch.empty_like(g_xl)
+        g_att = torch.empty(F, dtype=torch.float32, device=dev)
+        pl, ldl = _lib.mat(xl, "xl")
+        pr, ldr = _lib.mat(xr, "xr")
+        po, ldo = _lib.mat(out, "out")
+        pg, ldg = _lib.mat(gout, "gout")
+        pgl, ldgl = _lib.mat(g_xl, "g_xl")
+        pgr, ldgr = _lib.mat(g_xr, "g_xr")
+        split_ref, split, _scratch = _gatv2_split(g.fwd, F, dev)
+        n_part = ctypes.c_int64(0)
+        _lib.check(lib.rgbx_gatv2_att_partial_floats(N, H, C, split_ref, ctypes.byref(n_part)),
+                   "rgbx_gatv2_att_partial_floats")
+        part = torch.empty(max(n_part.value, 1), dtype=torch.float32, device=dev)
+        with _Timed("gatv2_bwd_dst"):
+            _lib.check(
+                lib.rgbx_gatv2_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pl, ldl, pr, ldr, _lib.ptr(a),
+                                           _lib.ptr(m), _lib.ptr(rden), po, ldo, _lib.ptr(b), pg, ldg, _lib.ptr(nodeq),
+                                           pgr, ldgr, _lib.ptr(g_att), _lib.ptr(part), n_part.value, N, H, C, slope,
+                                           _lib.ptr(seed), p_drop, split_ref, _lib.stream_ptr()),
+                "rgbx_gatv2_bwd_dst_f32")
+        split_ref, split, _scratch2 = _gatv2_split(g.bwd, F, dev)
+        with _Timed("gatv2_bwd_src"):
+            _lib.check(
+                lib.rgbx_gatv2_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
+                                           _lib.ptr(g.t2f) if seed is not None else None, pl, ldl, pr, ldr, _lib.ptr(a),
+                                           _lib.ptr(nodeq), pg, ldg, pgl, ldgl, N, H, C, slope, _lib.ptr(seed), p_drop,
+                                           split_ref, _lib.stream_ptr()), "rgbx_gatv2_bwd_src_f32")
+        need = ctx.needs_input_grad
+        g_b = gout.sum(0).reshape(ctx.bias_shape) if b is not None and need[7] else None
+        return (g_xl if need[0] else None, g_xr if need[1] else None, g_att.reshape(ctx.att_shape) if need[2] else None,
+                None, None, None, None, g_b, None, None, None, None)
+
+
+def gatv2_supported(H, C):
+    return bool(_lib.load().rgbx_gatv2_supported(H, C))
+
+
+def gatv2_attend(xl, xr, att, graph, H, C, slope=0.2, bias=None, training=False, p_drop=0.0, record=None):
+    """One GATv2Conv attention block on xl = lin_l(x), xr = lin_r(x) [N, H*C] (rows contiguous; column blocks of one
+    wider matrix are taken as they are) and att [H*C]: out_i = sum_j softmax_i(sum_c att_c lrelu(xl_j + xr_i)_c) xl_j
+    (+ bias [H*C]) over the graph in mode LOOPS_REMOVE_ADD. In training mode with p_drop > 0 the coefficients are
+    dropped after the softmax with a seed from torch's device generator; `record` (a dict) receives it, for
+    gatv2_random_choices."""
+    if _is_dist(graph):
+        raise RuntimeError("GATv2Conv has no node-partitioned form: run it on one GPU")
+    _lib.require_device(xl, xr, att, bias)
+    if not (0.0 <= p_drop < 1.0):
+        raise ValueError("gatv2_attend: dropout must be in [0, 1)")
+    if not gatv2_supported(H, C):
+        raise RuntimeError(f"gatv2_attend: {H} heads of {C} channels; pad the head width (GATv2Conv does)")
+    want_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (xl, xr, att, bias))
+    return _GATv2Attend.apply(xl, xr, att, graph, H, C, float(slope), bias, bool(training), float(p_drop), record,
+                              want_grad)
+
+
 FACONV_FORMS = ("fused", "composed")
 
 
