@@ -226,6 +226,69 @@ int rgbx_extremum_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const i
                           const int32_t* arg, float* gx, int64_t ldgx, int64_t N, int64_t d, const rgbx_row_split_t* split,
                           rgbx_stream_t stream);
 
+/* ---- one-pass multi-aggregation: sum / mean / var / std / max / min of a neighbourhood from ONE gather ----------------
+ * MessagePassing.propagate with aggr='std' | 'var' or a LIST of aggregators (PyG's MultiAggregation, mode='cat': the PNA
+ * recipe) behind SAGEConv(aggr=...) (models/graphsage2.py:20-23 passes the keyword on) [PyG]. Every neighbour row is read
+ * once; each statistic goes straight to its own matrix (pointer + leading dimension), so the column blocks of ONE
+ * [N, k*d] tensor can be passed and the concatenation costs nothing. For target row i with n slots p, v_p = x[col[p], c]:
+ *   sum  = sum_p v_p                      mean = sum / max(n, 1)
+ *   var  = mean(v^2) - mean(v)^2          (biased, NOT clamped; PyG VarAggregation)
+ *   std  = sqrt(var) where var > 1e-5, else 0   (PyG StdAggregation: sqrt(max(var, 1e-5)), 0 where that is <= sqrt(1e-5))
+ *   max / min, argmax / argmin            exactly rgbx_spmm_csr_extremum_f32's values and arg (lowest slot wins on ties)
+ * A row without slots gets 0 in every statistic and arg = -1. INPUTS ARE FINITE. A NULL pointer means "not wanted": that
+ * statistic is neither computed nor stored; argmax / argmin NULL with max / min set is the inference form. An arg without
+ * its extremum, or no statistic at all: RGBX_E_ARG.
+ * The second moment is accumulated as deviations from a per-(row, column) shift (the first slot's value) and merged across
+ * lane groups and hub-row chunks by exact re-basing in a fixed order (Chan's update on shifted sums): offset features keep
+ * their variance, and a neighbourhood whose values are all equal gives var == 0 and std == 0 EXACTLY. No float atomics:
+ * bitwise reproducible.
+ * d % 4 == 0, 4 <= d <= 256 (rgbx_spmm_csr_multi_supported; other widths: pad, or cut into column blocks); x and every
+ * output 16-byte aligned with leading dimensions % 4 == 0 and >= d; no output may alias x. `split`: rows above
+ * split->threshold are cut into the plan's chunks, one wave each, merged in chunk order (the split changes no extremum or
+ * arg); split->partial must hold rgbx_spmm_csr_multi_partial_words(n_chunks, d, which) 4-byte words, 16-byte aligned,
+ * `which` = the OR of the RGBX_MULTI_* bits of the wanted statistics. */
+enum {
+  RGBX_MULTI_SUM = 1, RGBX_MULTI_MEAN = 2, RGBX_MULTI_VAR = 4, RGBX_MULTI_STD = 8, RGBX_MULTI_MAX = 16, RGBX_MULTI_MIN = 32,
+  RGBX_MULTI_ALL = 63
+};
+typedef struct rgbx_multi_out {
+  float* sum;      int64_t ld_sum;
+  float* mean;     int64_t ld_mean;
+  float* var;      int64_t ld_var;
+  float* std;      int64_t ld_std;
+  float* max;      int64_t ld_max;
+  int32_t* argmax; int64_t ld_argmax;
+  float* min;      int64_t ld_min;
+  int32_t* argmin; int64_t ld_argmin;
+} rgbx_multi_out_t;
+int rgbx_spmm_csr_multi_supported(int64_t d);
+int rgbx_spmm_csr_multi_partial_words(int64_t n_chunks, int64_t d, int which, int64_t* words);
+int rgbx_spmm_csr_multi_f32(const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx,
+                            const rgbx_multi_out_t* out, int64_t N, int64_t d, const rgbx_row_split_t* split,
+                            rgbx_stream_t stream);
+
+/* Source-side backward of rgbx_spmm_csr_multi_f32 in ONE pass over the TRANSPOSED CSR (rows = sources, col_t = targets),
+ * t2f[q] = the forward slot of transposed slot q (needed only with an extremum term). For source row j, slots q, i = col_t[q]:
+ *   gx[j,c] = sum_q a[i,c] + x[j,c] * sum_q b[i,c] + sum_q gmax[i,c] [argmax[i,c] == t2f[q]] + sum_q gmin[i,c] [argmin[i,c] == t2f[q]]
+ * a and b are per-TARGET rows the caller prepares (nothing in them is indexed by an edge):
+ *   b = g_std / (n std) (0 where std == 0) + 2 g_var / n,      a = g_sum + g_mean / n - b * mean.
+ * Any of the four terms may be NULL and is then neither read nor added (no term at all: RGBX_E_ARG); x is read only with b
+ * (row j, once). Row-wise sums in slot order with a fixed butterfly over the lane groups, hub rows through chunk partials
+ * added in chunk order, no float atomics: bitwise reproducible. Four rows in flight per lane group, two when a slot loads
+ * more than three 16-byte fragments. Widths and alignment as the forward; gx must alias no input; `split` (of the
+ * transposed CSR, with chunk_row): partial [n_chunks, d]. */
+typedef struct rgbx_multi_grad {
+  const float* a;        int64_t ld_a;
+  const float* b;        int64_t ld_b;
+  const float* x;        int64_t ld_x;
+  const float* gmax;     int64_t ld_gmax;
+  const int32_t* argmax; int64_t ld_argmax;
+  const float* gmin;     int64_t ld_gmin;
+  const int32_t* argmin; int64_t ld_argmin;
+} rgbx_multi_grad_t;
+int rgbx_multi_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const rgbx_multi_grad_t* terms,
+                       float* gx, int64_t ldgx, int64_t N, int64_t d, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
 /* rgbx_spmm_csr_f32 with an epilogue over the finished output rows, for layers that transform BEFORE they aggregate
  * (in > out — every default configuration of the reference, initial_params.py:25-29: F -> 64 -> C with C = 7, 6, 3, 40 ...),
  * whose last kernel is this gather and not the fused aggregate+transform one. A lane group holds a target's complete

@@ -25,6 +25,18 @@ class RowSplit(ctypes.Structure):
                 ("long_chunk_ptr", ctypes.c_void_p), ("partial", ctypes.c_void_p)]
 
 
+class MultiOut(ctypes.Structure):
+    """rgbx_multi_out_t"""
+    _fields_ = [(f, t) for name in ("sum", "mean", "var", "std", "max", "argmax", "min", "argmin")
+                for f, t in ((name, ctypes.c_void_p), ("ld_" + name, ctypes.c_int64))]
+
+
+class MultiGrad(ctypes.Structure):
+    """rgbx_multi_grad_t"""
+    _fields_ = [(f, t) for name in ("a", "b", "x", "gmax", "argmax", "gmin", "argmin")
+                for f, t in ((name, ctypes.c_void_p), ("ld_" + name, ctypes.c_int64))]
+
+
 class CeEpilogue(ctypes.Structure):
     """rgbx_ce_epilogue_t"""
     _fields_ = [("y", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("grad_scale", ctypes.c_void_p),
@@ -67,6 +79,10 @@ SIGNATURES = {
     "rgbx_spmm_csr_extremum_supported": [_I64],
     "rgbx_spmm_csr_extremum_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
     "rgbx_extremum_bwd_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P],
+    "rgbx_spmm_csr_multi_supported": [_I64],
+    "rgbx_spmm_csr_multi_partial_words": [_I64, _I64, _I, ctypes.POINTER(ctypes.c_int64)],
+    "rgbx_spmm_csr_multi_f32": [_P, _P, _P, _I64, _P, _I64, _I64, _P, _P],
+    "rgbx_multi_bwd_f32": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P],
     "rgbx_spmm_csr_epilogue_supported": [_I64],
     "rgbx_spmm_csr_epilogue_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P],
     "rgbx_spmm_csr_short_rows_supported": [_I64],

@@ -6,8 +6,9 @@ my_SAGEConv = MySAGEConv  # the reference's class name
 
 
 class GraphSAGE(ConvStack):
-    """`aggr` ('mean' | 'max' | 'min' | 'add' | 'sum') goes to every conv: the keyword my_SAGEConv leaves to its caller
-    (models/graphsage.py:38-40). It reaches this constructor through experiment()'s model_init_param."""
+    """`aggr` ('mean' | 'max' | 'min' | 'add' | 'sum' | 'std' | 'var') goes to every conv: the keyword my_SAGEConv leaves to
+    its caller (models/graphsage.py:38-40). It reaches this constructor through experiment()'s model_init_param. A list
+    of aggregators is refused (ValueError): my_SAGEConv has no projection for their concatenation; GraphSAGE2 takes one."""
 
     def __init__(self, num_layers, hidden_unit, input_dim, output_dim, dropout_rate, aggr="mean"):
         widths = [input_dim] + [hidden_unit] * (num_layers - 1) + [output_dim]

@@ -4,7 +4,9 @@ from ._stack import ConvStack
 
 
 class GraphSAGE2(ConvStack):
-    """`aggr` ('mean' | 'max' | 'min' | 'add' | 'sum') goes to every conv (PyG SAGEConv's keyword)."""
+    """`aggr` ('mean' | 'max' | 'min' | 'add' | 'sum' | 'std' | 'var', or a list of distinct ones such as
+    ['mean', 'max', 'min', 'std']: PyG's MultiAggregation, one gather pass per layer) goes to every conv (PyG SAGEConv's
+    keyword)."""
 
     def __init__(self, num_layers, hidden_unit, input_dim, output_dim, dropout_rate, aggr="mean"):
         widths = [input_dim] + [hidden_unit] * (num_layers - 1) + [output_dim]

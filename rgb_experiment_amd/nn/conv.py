@@ -36,28 +36,49 @@ def _no_weight_grad(edge_weight, who):
                          "GCNConv only)")
 
 
-AGGRS = {"mean": "mean", "max": "max", "min": "min", "add": "add", "sum": "add"}  # accepted keyword -> canonical name
+# accepted keyword -> canonical name
+AGGRS = {"mean": "mean", "max": "max", "min": "min", "add": "add", "sum": "add", "std": "std", "var": "var"}
 
 
-def _set_aggr(conv, aggr):
+def _set_aggr(conv, aggr, lists=False):
     """The `aggr` keyword of the SAGE layers (reference models/graphsage.py:38-40: kwargs.setdefault('aggr', 'mean'), the
     caller may choose; PyG's SAGEConv takes the same keyword). 'mean' leaves the layer exactly as it is. The others run
-    composed (ops.propagate_max / propagate_min / propagate_sum between the dense products): the loss-in-kernel, folded,
-    cached-aggregate and fused aggregate + transform forms are all forms of a weighted row SUM with rows that sum to 1, so
-    this instance switches them off."""
-    if aggr not in AGGRS:
+    composed (ops.propagate_max / propagate_min / propagate_sum / propagate_std / propagate_var between the dense
+    products): the loss-in-kernel, folded, cached-aggregate and fused aggregate + transform forms are all forms of a
+    weighted row SUM with rows that sum to 1, so this instance switches them off.
+
+    `lists`: the layer also takes a non-empty list / tuple of distinct names (PyG's MultiAggregation, mode='cat');
+    conv.aggr is then the tuple of canonical names, aggregated in one pass by ops.propagate_multi — ['mean'] as well: only
+    the STRING 'mean' keeps the layer's own routes. Returns the number of aggregates."""
+    if isinstance(aggr, (list, tuple)):
+        if not lists:
+            raise ValueError(f"{type(conv).__name__}: aggr must be one name out of {sorted(AGGRS)} (the layer has no "
+                             f"projection for a concatenation of aggregates), got {aggr!r}")
+        names = tuple(AGGRS.get(a) if isinstance(a, str) else None for a in aggr)
+        if not names or None in names or len(set(names)) != len(names):
+            raise ValueError(f"{type(conv).__name__}: aggr must be one of {sorted(AGGRS)} or a non-empty list of distinct "
+                             f"ones, got {aggr!r}")
+        conv.aggr = names
+    elif not isinstance(aggr, str) or aggr not in AGGRS:
         raise ValueError(f"{type(conv).__name__}: aggr must be one of {sorted(AGGRS)}, got {aggr!r}")
-    conv.aggr = AGGRS[aggr]
+    else:
+        conv.aggr = AGGRS[aggr]
     if conv.aggr != "mean":
         conv.accepts_ce = conv.accepts_ce_pair = conv.folds_post_affine = conv.emits_colsums = False
+    return len(conv.aggr) if isinstance(conv.aggr, tuple) else 1
 
 
 def _aggregate(x, graph, aggr):
-    """The non-mean neighbourhood reductions of the SAGE layers over `graph` (single GPU)."""
+    """The non-mean neighbourhood reductions of the SAGE layers over `graph` (single GPU); a tuple of names: their
+    concatenation [N, k * d] from one gather pass."""
     if getattr(graph, "is_distributed", False):
-        raise NotImplementedError(f"aggr='{aggr}' is not implemented on the partitioned (distributed) route")
+        raise NotImplementedError(f"aggr={aggr!r} is not implemented on the partitioned (distributed) route")
+    if isinstance(aggr, tuple):
+        return ops.propagate_multi(x, graph, aggr)
     if aggr == "add":
         return ops.propagate_sum(x, graph)
+    if aggr in ("std", "var"):
+        return ops.propagate_std(x, graph) if aggr == "std" else ops.propagate_var(x, graph)
     return ops.propagate_max(x, graph) if aggr == "max" else ops.propagate_min(x, graph)
 
 
@@ -244,9 +265,11 @@ class SAGEConv(nn.Module):
     """out = lin_l(mean_{j in N(i)} x_j) + lin_r(x_i); no self-loops; nodes without in-edges
     aggregate 0 [PyG SAGEConv defaults: aggr='mean', root_weight=True, lin_l bias, lin_r no bias].
 
-    ``aggr`` in {'mean', 'max', 'min', 'add'} ('sum' = 'add'): PyG's keyword. Other than 'mean' the layer runs in PyG's
-    order on separate kernels — aggregate the raw x (ops.propagate_max / propagate_min / propagate_sum), then
-    lin_l(agg) + lin_r(x) — and reports none of the fused forms (see _set_aggr)."""
+    ``aggr`` in {'mean', 'max', 'min', 'add', 'std', 'var'} ('sum' = 'add'): PyG's keyword. Other than 'mean' the layer runs
+    in PyG's order on separate kernels — aggregate the raw x (ops.propagate_max / propagate_min / propagate_sum /
+    propagate_std / propagate_var), then lin_l(agg) + lin_r(x) — and reports none of the fused forms (see _set_aggr).
+    A list or tuple of k distinct names (PyG's MultiAggregation, mode='cat', e.g. ['mean', 'max', 'min', 'std']): the k
+    aggregates come from ONE gather pass (ops.propagate_multi), concatenated, and lin_l takes k * in_channels columns."""
 
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # see GCNConv
@@ -254,8 +277,8 @@ class SAGEConv(nn.Module):
     def __init__(self, in_channels, out_channels, aggr="mean"):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
-        _set_aggr(self, aggr)
-        self.lin_l = nn.Linear(in_channels, out_channels, bias=True)
+        k = _set_aggr(self, aggr, lists=True)
+        self.lin_l = nn.Linear(k * in_channels, out_channels, bias=True)
         self.lin_r = nn.Linear(in_channels, out_channels, bias=False)
 
     accepts_ce = True         # see GCNConv
@@ -358,10 +381,11 @@ class MySAGEConv(nn.Module):
     """reference models/graphsage.py:36-62: x_l = lin_l(x), x_r = lin_r(x) (both with bias),
     remove_self_loops + add_self_loops, mean over N(i) ∪ {i} of x_l, then += x_r.
 
-    ``aggr`` in {'mean', 'max', 'min', 'add'} ('sum' = 'add'): the keyword the reference leaves to the caller
+    ``aggr`` in {'mean', 'max', 'min', 'add', 'std', 'var'} ('sum' = 'add'): the keyword the reference leaves to the caller
     (graphsage.py:38-40). Other than 'mean' the layer runs in the reference's order on separate kernels — [lin_l(x),
-    lin_r(x)] in one product, the reduction over the left half (ops.propagate_max / propagate_min / propagate_sum),
-    += x_r — and reports none of the fused forms (see _set_aggr)."""
+    lin_r(x)] in one product, the reduction over the left half (ops.propagate_max / propagate_min / propagate_sum /
+    propagate_std / propagate_var), += x_r — and reports none of the fused forms (see _set_aggr). A list of aggregators
+    is refused: the reference's layer has no projection for their concatenation."""
 
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # see GCNConv

@@ -382,6 +382,195 @@ def propagate_min(x, graph):
     return _propagate_extremum(x, graph, "min")
 
 
+# ---- several statistics of the neighbourhood from one gather (aggr='std' | 'var' | a list of aggregators) ------------
+
+MULTI_BITS = {"sum": 1, "mean": 2, "var": 4, "std": 8, "max": 16, "min": 32}  # RGBX_MULTI_*
+
+
+def multi_names(aggrs):
+    """A string or a non-empty list / tuple of distinct aggregator names as the tuple of the kernel's names ('add' is
+    'sum'); anything else: ValueError."""
+    seq = (aggrs,) if isinstance(aggrs, str) else aggrs
+    if not isinstance(seq, (list, tuple)) or not seq or not all(isinstance(a, str) for a in seq):
+        raise ValueError(f"aggr must be a name or a non-empty list of names out of {sorted(MULTI_BITS) + ['add']}, got {aggrs!r}")
+    names = tuple("sum" if a == "add" else a for a in seq)
+    if any(a not in MULTI_BITS for a in names) or len(set(names)) != len(names):
+        raise ValueError(f"aggr must name distinct aggregators out of {sorted(MULTI_BITS) + ['add']}, got {aggrs!r}")
+    return names
+
+
+def _block_ptr(t, c0, c1):
+    """(pointer, leading dimension) of the column block [c0, c1) of a row-major matrix."""
+    return t[:, c0:c1].data_ptr(), (t.stride(0) if t.size(0) > 1 else max(t.size(1), 1))
+
+
+def spmm_multi_raw(csr, x, which, want_arg, keep=(), kind="multi_fwd"):
+    """(out [N, k*d], argmax, argmin, kept): the k statistics `which` of every row's neighbourhood, concatenated in that
+    order, from ONE gather pass over `csr` (rgbx_spmm_csr_multi_f32: every statistic is written straight into its column
+    block). argmax / argmin: int32 [N, d] winning slots when `want_arg` and that extremum is asked for, else None
+    (`want_arg=False` is the inference form). `keep`: further statistics, computed in the same pass into [N, d] matrices
+    of their own (kept[name]) — what a backward needs and the output does not hold. No autograd. Widths that are no
+    multiple of 4 run zero-padded; widths above 256 in column blocks of 256 (every statistic is taken per column)."""
+    names = multi_names(which)
+    _lib.require_device(x)
+    d = x.size(1)
+    if d % 4:
+        x = torch.nn.functional.pad(x, (0, 4 - d % 4))
+    x = _vec4_rows(x)
+    N, dp, k, dev = csr.N, x.size(1), len(names), x.device
+    buf = torch.empty((N, k * dp), dtype=torch.float32, device=dev)
+    dest = {a: buf[:, s * dp:(s + 1) * dp] for s, a in enumerate(names)}
+    kept = {a: torch.empty((N, dp), dtype=torch.float32, device=dev) for a in multi_names(keep) if a not in dest} if keep else {}
+    dest.update(kept)
+    args = {a: torch.empty((N, dp), dtype=torch.int32, device=dev) for a in ("max", "min") if want_arg and a in names}
+    bits = sum(MULTI_BITS[a] for a in dest)
+    lib = _lib.load()
+    for c0 in range(0, dp, 256):
+        c1 = min(c0 + 256, dp)
+        w = c1 - c0
+        o = _lib.MultiOut()
+        for a, t in dest.items():
+            p, ld = _block_ptr(t, c0, c1)
+            setattr(o, a, p)
+            setattr(o, "ld_" + a, ld)
+        for a, t in args.items():
+            p, ld = _block_ptr(t, c0, c1)
+            setattr(o, "arg" + a, p)
+            setattr(o, "ld_arg" + a, ld)
+        px, ldx = _block_ptr(x, c0, c1)
+        split = None
+        if csr.split is not None:
+            words = ctypes.c_int64(0)
+            _lib.check(lib.rgbx_spmm_csr_multi_partial_words(csr.split["n_chunks"], w, bits, ctypes.byref(words)),
+                       "rgbx_spmm_csr_multi_partial_words")
+            split, _scratch = csr.split_arg(words.value // csr.split["n_chunks"], dev)
+        variant = f"rows+d{w}+{'+'.join(dest)}" + ("+arg" if args else "") if _EVENT_SINK is not None else None
+        with _Timed(kind, variant):
+            _lib.check(lib.rgbx_spmm_csr_multi_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), px, ldx, ctypes.byref(o), N, w,
+                                                   None if split is None else ctypes.byref(split), _lib.stream_ptr()),
+                       "rgbx_spmm_csr_multi_f32")
+    out = buf if dp == d else buf.view(N, k, dp)[:, :, :d].reshape(N, k * d)
+    cut = (lambda t: t) if dp == d else (lambda t: t[:, :d])
+    return (out, cut(args["max"]) if "max" in args else None, cut(args["min"]) if "min" in args else None,
+            {a: cut(t) for a, t in kept.items()})
+
+
+def multi_bwd_raw(graph, a=None, b=None, x=None, gmax=None, argmax=None, gmin=None, argmin=None, kind="multi_bwd"):
+    """gx[j] = sum_q a[i] + x[j] * sum_q b[i] + sum_q gmax[i] [argmax[i] == slot of q] + sum_q gmin[i] [argmin[i] == slot of
+    q] over the out-edges q of j (target i), in ONE pass over the transposed CSR (rgbx_multi_bwd_f32; fixed summation order,
+    no atomics). a, b, gmax, gmin: float32 [N, d] per TARGET (column blocks of a wider matrix are read in place); terms that
+    are None are neither read nor added. No autograd. Widths as spmm_multi_raw."""
+    terms = {"a": a, "b": b, "x": x if b is not None else None, "gmax": gmax, "argmax": argmax, "gmin": gmin,
+             "argmin": argmin}
+    terms = {k: v for k, v in terms.items() if v is not None}
+    if not terms:
+        raise ValueError("multi_bwd_raw: no term given")
+    _lib.require_device(*terms.values())
+    d = next(iter(terms.values())).size(1)
+    if d % 4:
+        terms = {k: torch.nn.functional.pad(v, (0, 4 - d % 4), value=-1 if k.startswith("arg") else 0)
+                 for k, v in terms.items()}
+    terms = {k: _vec4_rows(v) for k, v in terms.items()}
+    csr = graph.bwd
+    t2f = graph.t2f if ("gmax" in terms or "gmin" in terms) else None
+    dp, dev = (d + 3) // 4 * 4, next(iter(terms.values())).device
+    gx = torch.empty((csr.N, dp), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    for c0 in range(0, dp, 256):
+        c1 = min(c0 + 256, dp)
+        w = c1 - c0
+        t = _lib.MultiGrad()
+        for k, v in terms.items():
+            p, ld = _block_ptr(v, c0, c1)
+            setattr(t, k, p)
+            setattr(t, "ld_" + k, ld)
+        pg, ldgx = _block_ptr(gx, c0, c1)
+        split, _scratch = csr.split_arg(w, dev)
+        with _Timed(kind, f"rows+d{w}+{'+'.join(terms)}" if _EVENT_SINK is not None else None):
+            _lib.check(lib.rgbx_multi_bwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(t2f), ctypes.byref(t), pg,
+                                              ldgx, csr.N, w, None if split is None else ctypes.byref(split),
+                                              _lib.stream_ptr()), "rgbx_multi_bwd_f32")
+    return gx if dp == d else gx[:, :d]
+
+
+class _PropagateMulti(torch.autograd.Function):
+    """[stat_1(N(i)) | ... | stat_k(N(i))] over incoming edges (PyG MultiAggregation, mode='cat'; a single 'std' / 'var' is
+    the k = 1 case). The forward keeps x, the mean, the output (for its std block) and the winning slots only when a
+    gradient will be asked for; the backward folds every statistic's cotangent into two per-target rows (a, b) with
+    elementwise arithmetic and routes them, with the extremum cotangents, through one transposed gather."""
+
+    @staticmethod
+    def forward(ctx, x, graph, names, want):
+        second = want and ("std" in names or "var" in names)
+        keep = ("mean",) if second and "mean" not in names else ()
+        out, amax, amin, kept = spmm_multi_raw(graph.fwd, x, names, want, keep=keep)
+        ctx.graph, ctx.names = graph, names
+        if want:
+            # built here, outside the backward (their construction reads sizes back to the host)
+            graph.bwd, graph.inv_deg
+            if amax is not None or amin is not None:
+                graph.t2f
+            ctx.save_for_backward(x if second else None, out if second else None, kept.get("mean"), amax, amin)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, out, kept_mean, amax, amin = ctx.saved_tensors
+        names, g = ctx.names, ctx.graph
+        gy = _vec4_rows(gy)
+        dp = gy.size(1) // len(names)
+        blk = lambda t, a: t[:, names.index(a) * dp:(names.index(a) + 1) * dp]
+        inv_n = g.inv_deg[:g.N, None]  # 1 / max(n, 1)
+        a = b = None
+        if "std" in names:  # d std / d x_j = (x_j - mean) / (n std); 0 where the clamp or the mask is active (std == 0)
+            std = blk(out, "std")
+            b = torch.where(std > 0, blk(gy, "std") * inv_n / std, torch.zeros_like(std))
+        if "var" in names:  # d var / d x_j = 2 (x_j - mean) / n
+            t = blk(gy, "var") * (2.0 * inv_n)
+            b = t if b is None else b + t
+        if b is not None:
+            # sum_q b_i (x_j - mean_i) as x_j sum_q b_i - sum_q b_i mean_i cancels on features with an offset (x = 50 +
+            # 0.05 noise: both halves are 1000 times their difference). Both are taken relative to the column mean s of
+            # x — (x_j - s) sum_q b_i - sum_q b_i (mean_i - s), the same number — so the kernel's `x` is x - s
+            s = x.mean(0, keepdim=True)
+            a = -b * ((blk(out, "mean") if "mean" in names else kept_mean) - s)
+            x = x - s
+        if "sum" in names:
+            a = blk(gy, "sum") if a is None else a + blk(gy, "sum")
+        if "mean" in names:
+            t = blk(gy, "mean") * inv_n
+            a = t if a is None else a + t
+        gx = multi_bwd_raw(g, a=a, b=b, x=x, gmax=blk(gy, "max") if "max" in names else None, argmax=amax,
+                           gmin=blk(gy, "min") if "min" in names else None, argmin=amin)
+        return gx, None, None, None
+
+
+def propagate_multi(x, graph, aggrs):
+    """[N, k*d]: the statistics `aggrs` (a list out of 'sum' / 'add', 'mean', 'var', 'std', 'max', 'min') of every node's
+    in-neighbourhood, concatenated in that order, from one gather pass; 0 in every block where a node has no in-edge."""
+    names = multi_names(aggrs)
+    if _is_dist(graph):
+        raise NotImplementedError(f"aggr={aggrs!r} is not implemented on the partitioned (distributed) route")
+    _lib.require_device(x)
+    xp, d = _pad4(x)
+    # decided here: inside a Function's forward the grad mode is always off and cannot tell no_grad from training
+    want = torch.is_grad_enabled() and xp.requires_grad
+    out = _PropagateMulti.apply(xp, graph, names, want)
+    if xp is x:
+        return out
+    return out.view(out.size(0), len(names), xp.size(1))[:, :, :d].reshape(out.size(0), len(names) * d)
+
+
+def propagate_std(x, graph):
+    """out[i] = the (biased) standard deviation of x over N(i) per column, 0 where the variance is at most 1e-5."""
+    return propagate_multi(x, graph, ("std",))
+
+
+def propagate_var(x, graph):
+    """out[i] = mean(x^2) - mean(x)^2 over N(i) per column (biased, not clamped)."""
+    return propagate_multi(x, graph, ("var",))
+
+
 # ---- propagate of an already transformed matrix, with the passes that follow it taken in the same kernel --------------
 
 def pad_rows4(weight, *vectors):
