@@ -797,6 +797,29 @@ int rgbx_gemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, f
                      float* a_colsum, int64_t K, int64_t M, int64_t N, float alpha, void* workspace,
                      size_t workspace_bytes, rgbx_stream_t stream);
 
+/* rgbx_gemm_tn_f32 with A = BatchNorm's input gradient, formed as the A tiles are staged instead of being written by
+ * rgbx_bn_bwd_apply_f32 and read back: C = alpha * A'^T B and a_colsum = column sums of A' with
+ *   A'[r,c] = (G[r,c] - ca[c] - (X[r,c] - mean[c]) * rstd[c] * cb[c]) * ck[c]
+ * (G [K,M] = the gradient of BatchNorm's output, X [K,M] its input, the five [M] vectors as for rgbx_bn_bwd_apply_f32).
+ * Same slabs, MFMA order and reduce launches as rgbx_gemm_tn_f32 and the same arithmetic per element as the apply
+ * kernel: the results are those of the two-launch sequence, bit for bit. Workspace: rgbx_gemm_tn_workspace_bytes.
+ * 16-byte path only: G, X and B 16-byte aligned with ldg, ldx, ldb multiples of 4, else RGBX_E_ALIGN (the caller then
+ * runs rgbx_bn_bwd_apply_f32 + rgbx_gemm_tn_f32). */
+int rgbx_gemm_tn_bn_bwd_f32(const float* G, int64_t ldg, const float* X, int64_t ldx, const float* mean,
+                            const float* rstd, const float* ca, const float* cb, const float* ck, const float* B,
+                            int64_t ldb, float* C, int64_t ldc, float* a_colsum, int64_t K, int64_t M, int64_t N,
+                            float alpha, void* workspace, size_t workspace_bytes, rgbx_stream_t stream);
+
+/* rgbx_gemm_tn_f32 over the rows of an ascending int32 list `rows` ([n_rows], each in [0, K)), for an A whose other
+ * rows are all zero (the loss gradient outside the rows the loss selects): only the listed rows of A and B are read.
+ * The K-slabs are those of rgbx_gemm_tn_f32 on K rows and each multiplies the list entries inside its own row range,
+ * in list order, so the non-zero products are added in the order of the full product. Workspace:
+ * rgbx_gemm_tn_workspace_bytes(K, M, N). 16-byte path only (A, B aligned, lda, ldb multiples of 4), else
+ * RGBX_E_ALIGN; K must fit int32. */
+int rgbx_gemm_tn_rows_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rows,
+                          int64_t n_rows, float* C, int64_t ldc, float* a_colsum, int64_t K, int64_t M, int64_t N,
+                          float alpha, void* workspace, size_t workspace_bytes, rgbx_stream_t stream);
+
 /* ---- BatchNorm1d over the node axis --------------------------------------------------------- */
 
 /* Doubles of scratch the two column-reduction entry points need. */

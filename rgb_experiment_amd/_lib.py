@@ -134,6 +134,9 @@ SIGNATURES = {
     "rgbx_gatv2_draws_u8": [_P, _I64, _I, _F, _P, _P],
     "rgbx_gemm_tn_workspace_bytes": [_I64, _I64, _I64, ctypes.POINTER(ctypes.c_size_t)],
     "rgbx_gemm_tn_f32": [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _F, _P, ctypes.c_size_t, _P],
+    "rgbx_gemm_tn_bn_bwd_f32": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _F, _P,
+                                ctypes.c_size_t, _P],
+    "rgbx_gemm_tn_rows_f32": [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _F, _P, ctypes.c_size_t, _P],
     "rgbx_bn_scratch_doubles": [_I64, _I64, ctypes.POINTER(ctypes.c_int64)],
     "rgbx_bn_stats_f32": [_P, _I64, _I64, _I64, _P, _P, _I64, _P],
     "rgbx_bn_finalize_f32": [_P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64, _P],

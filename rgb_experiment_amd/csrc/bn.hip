@@ -162,7 +162,7 @@ bn_bwd_apply_kernel(const float* __restrict__ gy, int64_t ldg, const float* __re
     load_vec<VEC>(b, cb + c);
     load_vec<VEC>(k, ck + c);
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) g[i] = (g[i] - a[i] - (v[i] - mu[i]) * rs[i] * b[i]) * k[i];
+    for (int i = 0; i < VEC; ++i) g[i] = bn_bwd_input_grad(g[i], v[i], mu[i], rs[i], a[i], b[i], k[i]);
     store_vec<VEC>(gx + r * ldgx + c, g);
   }
 }

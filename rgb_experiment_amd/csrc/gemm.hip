@@ -21,12 +21,33 @@
 //      never stored. A feature matrix with F = 1433 is kept with a row stride of 1436 floats (ops.align_rows);
 //  (2) M <= 64 runs a 64 x 128 tile (one 32-row MFMA block per wave instead of two): half the MFMAs and half the A-side
 //      LDS traffic of the 128 x 128 tile, which multiplied 64 rows of zeros.
+//
+// Two forms of the A operand on the 16-byte path, same slabs, tile loop, MFMA order and reduce launches (so every sum
+// keeps its order and the results are those of the plain kernel on the materialised operand, bit for bit):
+//  - A_BN (rgbx_gemm_tn_bn_bwd_f32): A = BatchNorm's input gradient, formed from (G, X) and the per-column constants
+//    between fetch_tile and put_tile (bn_bwd_input_grad, the expression of bn_bwd_apply_kernel) — the [K, M] matrix gx
+//    is never written or read back. The constants sit in LDS (5 x MT floats): held in registers they would cost the
+//    third workgroup per CU;
+//  - A_ROWS (rgbx_gemm_tn_rows_f32): only the rows of an ascending list are multiplied, for operands whose other rows
+//    are all zero (the loss gradient outside the rows the loss selects). Slab s takes the list entries inside its own
+//    row range [s * slab, (s + 1) * slab), in list order: the non-zero products meet the accumulators in the order of
+//    the full product, a skipped row only added zeros.
 #include "rgbx_common.h"
 
 namespace rgbx {
 namespace {
 
 constexpr int BM = 128, BN = 128, KT = 32;
+enum { A_PLAIN = 0, A_BN = 1, A_ROWS = 2 };
+
+// What the A_BN / A_ROWS forms read beside A and B (unused, all zero, in the plain form)
+struct TnExtra {
+  const float* X;        // A_BN: BatchNorm's input, beside A = the gradient of its output
+  int64_t ldx;
+  const float *mean, *rstd, *ca, *cb, *ck;
+  const int32_t* rows;   // A_ROWS: ascending row list
+  int64_t n_rows;
+};
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // Scalar staging (rows that are not 16-byte aligned): [KT x W] tile, row-major in LDS; rows >= k_end and columns >= ncols
@@ -72,15 +93,69 @@ __device__ __forceinline__ void put_tile(float* __restrict__ lds, const float4 (
   }
 }
 
+// A_BN: the staged A tile is bn_bwd_input_grad(G, X, ...) of the two fetched tiles. Rows >= k_end and columns >= ncols
+// stay the zeros fetch_tile put there: they are not mapped. `lc` = [5][W] constants of columns c0 .. c0 + W (mean, rstd,
+// ca, cb, ck; zero past ncols)
+template <int W>
+__device__ __forceinline__ void put_tile_bn(float* __restrict__ lds, const float4 (&rg)[KT * (W / 4) / 256],
+                                            const float4 (&rx)[KT * (W / 4) / 256], const float* __restrict__ lc,
+                                            int64_t k0, int64_t k_end, int c0, int ncols) {
+#pragma unroll
+  for (int p = 0; p < KT * (W / 4) / 256; ++p) {
+    const int idx = p * 256 + threadIdx.x;
+    const int r = idx / (W / 4), c = (idx % (W / 4)) * 4;
+    float4 v = rg[p];
+    if (k0 + r < k_end && c0 + c < ncols) {
+      const float4 mu = *reinterpret_cast<const float4*>(lc + 0 * W + c);
+      const float4 rs = *reinterpret_cast<const float4*>(lc + 1 * W + c);
+      const float4 a = *reinterpret_cast<const float4*>(lc + 2 * W + c);
+      const float4 b = *reinterpret_cast<const float4*>(lc + 3 * W + c);
+      const float4 k = *reinterpret_cast<const float4*>(lc + 4 * W + c);
+      v.x = bn_bwd_input_grad(v.x, rx[p].x, mu.x, rs.x, a.x, b.x, k.x);
+      v.y = bn_bwd_input_grad(v.y, rx[p].y, mu.y, rs.y, a.y, b.y, k.y);
+      v.z = bn_bwd_input_grad(v.z, rx[p].z, mu.z, rs.z, a.z, b.z, k.z);
+      v.w = bn_bwd_input_grad(v.w, rx[p].w, mu.w, rs.w, a.w, b.w, k.w);
+    }
+    *reinterpret_cast<float4*>(lds + r * W + c) = v;
+  }
+}
+
+// A_ROWS: tile row r is row rows[j0 + r] of src; list entries >= j_end are zero-filled
+template <int W>
+__device__ __forceinline__ void fetch_tile_rows(float4 (&regs)[KT * (W / 4) / 256], const float* __restrict__ src,
+                                                int64_t ld, const int32_t* __restrict__ rows, int64_t j0, int64_t j_end,
+                                                int c0, int ncols) {
+#pragma unroll
+  for (int p = 0; p < KT * (W / 4) / 256; ++p) {
+    const int idx = p * 256 + threadIdx.x;
+    const int r = idx / (W / 4), c = (idx % (W / 4)) * 4;
+    const int64_t j = j0 + r;
+    regs[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < j_end && c0 + c < ncols) regs[p] = *reinterpret_cast<const float4*>(src + (int64_t)rows[j] * ld + c0 + c);
+  }
+}
+
+// first list position whose row is >= key (rows ascending)
+__device__ __forceinline__ int64_t lower_bound_rows(const int32_t* __restrict__ rows, int64_t n, int64_t key) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (rows[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // MT = rows of the output tile a workgroup owns: 128 (each wave a 64 x 64 quadrant = 2 x 2 MFMA blocks) or 64 (each wave
 // 32 x 64 = 1 x 2 blocks; M <= 64)
-template <bool VEC4, int MT>
+// MODE: the form of the A operand (A_PLAIN, or A_BN / A_ROWS on the 16-byte path; see the head of the file)
+template <bool VEC4, int MT, int MODE = A_PLAIN>
 __global__ void __launch_bounds__(256)
 gemm_tn_partial_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
                        float* __restrict__ part, float* __restrict__ colpart, int64_t K, int M, int N,
-                       int64_t slab) {
+                       int64_t slab, TnExtra ex) {
+  static_assert(MODE == A_PLAIN || VEC4, "the A_BN / A_ROWS forms exist on the 16-byte path only");
   constexpr int MI = MT / 64;  // 32-row MFMA blocks per wave along M
-  __shared__ float lds[KT * (MT + 128)];
+  __shared__ float lds[KT * (MT + 128) + (MODE == A_BN ? 5 * MT : 0)];
   float* la = lds;
   float* lb = lds + KT * MT;
   const int split = blockIdx.x;
@@ -120,7 +195,48 @@ gemm_tn_partial_kernel(const float* __restrict__ A, int64_t lda, const float* __
       }
     }
   };
-  if constexpr (VEC4) {
+  if constexpr (MODE == A_BN) {
+    float* lc = lds + KT * (MT + 128);
+    for (int i = threadIdx.x; i < 5 * MT; i += 256) {  // visible after the loop's first barrier
+      const float* src = i < MT ? ex.mean : i < 2 * MT ? ex.rstd : i < 3 * MT ? ex.ca : i < 4 * MT ? ex.cb : ex.ck;
+      const int c = m0 + i % MT;
+      lc[i] = c < M ? src[c] : 0.f;
+    }
+    float4 ra[KT * (MT / 4) / 256], rx[KT * (MT / 4) / 256], rb[KT * 32 / 256];
+    fetch_tile<MT>(ra, A, lda, k_begin, k_end, m0, M);
+    fetch_tile<MT>(rx, ex.X, ex.ldx, k_begin, k_end, m0, M);
+    fetch_tile<128>(rb, B, ldb, k_begin, k_end, n0, N);
+    for (int64_t k0 = k_begin; k0 < k_end; k0 += KT) {
+      __syncthreads();
+      put_tile_bn<MT>(la, ra, rx, lc, k0, k_end, m0, M);
+      put_tile<128>(lb, rb);
+      __syncthreads();
+      if (k0 + KT < k_end) {
+        fetch_tile<MT>(ra, A, lda, k0 + KT, k_end, m0, M);
+        fetch_tile<MT>(rx, ex.X, ex.ldx, k0 + KT, k_end, m0, M);
+        fetch_tile<128>(rb, B, ldb, k0 + KT, k_end, n0, N);
+      }
+      consume();
+    }
+  } else if constexpr (MODE == A_ROWS) {
+    // this slab's segment of the list: the entries inside [k_begin, k_end)
+    const int64_t j_begin = lower_bound_rows(ex.rows, ex.n_rows, k_begin);
+    const int64_t j_end = lower_bound_rows(ex.rows, ex.n_rows, k_end);
+    float4 ra[KT * (MT / 4) / 256], rb[KT * 32 / 256];
+    fetch_tile_rows<MT>(ra, A, lda, ex.rows, j_begin, j_end, m0, M);
+    fetch_tile_rows<128>(rb, B, ldb, ex.rows, j_begin, j_end, n0, N);
+    for (int64_t j0 = j_begin; j0 < j_end; j0 += KT) {
+      __syncthreads();
+      put_tile<MT>(la, ra);
+      put_tile<128>(lb, rb);
+      __syncthreads();
+      if (j0 + KT < j_end) {
+        fetch_tile_rows<MT>(ra, A, lda, ex.rows, j0 + KT, j_end, m0, M);
+        fetch_tile_rows<128>(rb, B, ldb, ex.rows, j0 + KT, j_end, n0, N);
+      }
+      consume();
+    }
+  } else if constexpr (VEC4) {
     float4 ra[KT * (MT / 4) / 256], rb[KT * 32 / 256];
     fetch_tile<MT>(ra, A, lda, k_begin, k_end, m0, M);
     fetch_tile<128>(rb, B, ldb, k_begin, k_end, n0, N);
@@ -213,18 +329,37 @@ extern "C" int rgbx_gemm_tn_workspace_bytes(int64_t K, int64_t M, int64_t N, siz
   return RGBX_OK;
 }
 
-extern "C" int rgbx_gemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
-                                int64_t ldc, float* a_colsum, int64_t K, int64_t M, int64_t N, float alpha,
-                                void* workspace, size_t workspace_bytes, rgbx_stream_t stream) {
-  if (K < 0 || M < 0 || N < 0) return fail(RGBX_E_ARG, "gemm_tn: negative size");
+namespace rgbx {
+namespace {
+
+// The three entry points: argument checks, one partial launch (the form of its A operand by `mode`), the reduce launches
+int run_gemm_tn(const char* name, int mode, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                int64_t ldc, float* a_colsum, int64_t K, int64_t M, int64_t N, float alpha, void* workspace,
+                size_t workspace_bytes, rgbx_stream_t stream, const TnExtra& ex) {
+  if (K < 0 || M < 0 || N < 0) return fail(RGBX_E_ARG, "%s: negative size", name);
   if (M == 0 || N == 0) return RGBX_OK;
-  if (!C || (K > 0 && (!A || !B))) return fail(RGBX_E_ARG, "gemm_tn: null pointer");
-  if (M >= INT32_MAX || N >= INT32_MAX) return fail(RGBX_E_RANGE, "gemm_tn: M or N exceeds int32");
-  if (lda < M || ldb < N || ldc < N) return fail(RGBX_E_ARG, "gemm_tn: leading dimension too small");
+  if (!C || (K > 0 && (!A || !B))) return fail(RGBX_E_ARG, "%s: null pointer", name);
+  if (M >= INT32_MAX || N >= INT32_MAX) return fail(RGBX_E_RANGE, "%s: M or N exceeds int32", name);
+  if (lda < M || ldb < N || ldc < N) return fail(RGBX_E_ARG, "%s: leading dimension too small", name);
+  // 16-byte path: aligned ROWS are enough — a row's last float4 may end in its padding (header: "rows are read in whole
+  // 16-byte groups")
+  bool v4 = aligned16(A) && aligned16(B) && lda % 4 == 0 && ldb % 4 == 0;
+  if (mode == A_BN) {
+    if (K > 0 && (!ex.X || !ex.mean || !ex.rstd || !ex.ca || !ex.cb || !ex.ck))
+      return fail(RGBX_E_ARG, "%s: null pointer", name);
+    if (ex.ldx < M) return fail(RGBX_E_ARG, "%s: leading dimension too small", name);
+    v4 = v4 && aligned16(ex.X) && ex.ldx % 4 == 0;
+  }
+  if (mode == A_ROWS) {
+    if (ex.n_rows < 0 || ex.n_rows > K || (ex.n_rows > 0 && !ex.rows)) return fail(RGBX_E_ARG, "%s: bad row list", name);
+    if (K >= INT32_MAX) return fail(RGBX_E_RANGE, "%s: K exceeds int32", name);
+  }
+  if (mode != A_PLAIN && !v4)
+    return fail(RGBX_E_ALIGN, "%s: operands must be 16-byte aligned with leading dimensions that are multiples of 4", name);
   size_t need = 0;
   if (int rc = rgbx_gemm_tn_workspace_bytes(K, M, N, &need)) return rc;
   if (!workspace || workspace_bytes < need)
-    return fail(RGBX_E_WS, "gemm_tn: workspace %zu < %zu bytes", workspace_bytes, need);
+    return fail(RGBX_E_WS, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
   const int S = choose_splits(K, (int)M, (int)N);
   const int64_t slab = cdiv(cdiv(K > 0 ? K : 1, S), KT) * KT;
@@ -232,13 +367,12 @@ extern "C" int rgbx_gemm_tn_f32(const float* A, int64_t lda, const float* B, int
   float* colpart = a_colsum ? part + (size_t)S * M * N : nullptr;
   const int mt = tile_rows((int)M);
   dim3 grid(S, (unsigned)cdiv(M, mt), (unsigned)cdiv(N, BN));
-  // 16-byte path: aligned ROWS are enough — a row's last float4 may end in its padding (header: "rows are read in whole
-  // 16-byte groups")
-  const bool v4 = aligned16(A) && aligned16(B) && lda % 4 == 0 && ldb % 4 == 0;
-#define RGBX_GEMM_TN(V4, MT) \
-  gemm_tn_partial_kernel<V4, MT><<<grid, 256, 0, s>>>(A, lda, B, ldb, part, colpart, K, (int)M, (int)N, slab)
-  if (v4) { if (mt == 64) RGBX_GEMM_TN(true, 64); else RGBX_GEMM_TN(true, 128); }
-  else { if (mt == 64) RGBX_GEMM_TN(false, 64); else RGBX_GEMM_TN(false, 128); }
+#define RGBX_GEMM_TN(V4, MT, MODE) \
+  gemm_tn_partial_kernel<V4, MT, MODE><<<grid, 256, 0, s>>>(A, lda, B, ldb, part, colpart, K, (int)M, (int)N, slab, ex)
+  if (mode == A_BN) { if (mt == 64) RGBX_GEMM_TN(true, 64, A_BN); else RGBX_GEMM_TN(true, 128, A_BN); }
+  else if (mode == A_ROWS) { if (mt == 64) RGBX_GEMM_TN(true, 64, A_ROWS); else RGBX_GEMM_TN(true, 128, A_ROWS); }
+  else if (v4) { if (mt == 64) RGBX_GEMM_TN(true, 64, A_PLAIN); else RGBX_GEMM_TN(true, 128, A_PLAIN); }
+  else { if (mt == 64) RGBX_GEMM_TN(false, 64, A_PLAIN); else RGBX_GEMM_TN(false, 128, A_PLAIN); }
 #undef RGBX_GEMM_TN
   RGBX_CHECK_LAUNCH("gemm_tn_partial_kernel");
   const int64_t MN = M * N;
@@ -251,4 +385,35 @@ extern "C" int rgbx_gemm_tn_f32(const float* A, int64_t lda, const float* B, int
     RGBX_CHECK_LAUNCH("gemm_tn_reduce_kernel");
   }
   return RGBX_OK;
+}
+
+}  // namespace
+}  // namespace rgbx
+
+extern "C" int rgbx_gemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                                int64_t ldc, float* a_colsum, int64_t K, int64_t M, int64_t N, float alpha,
+                                void* workspace, size_t workspace_bytes, rgbx_stream_t stream) {
+  return run_gemm_tn("gemm_tn", A_PLAIN, A, lda, B, ldb, C, ldc, a_colsum, K, M, N, alpha, workspace, workspace_bytes,
+                     stream, TnExtra{});
+}
+
+extern "C" int rgbx_gemm_tn_bn_bwd_f32(const float* G, int64_t ldg, const float* X, int64_t ldx, const float* mean,
+                                       const float* rstd, const float* ca, const float* cb, const float* ck,
+                                       const float* B, int64_t ldb, float* C, int64_t ldc, float* a_colsum, int64_t K,
+                                       int64_t M, int64_t N, float alpha, void* workspace, size_t workspace_bytes,
+                                       rgbx_stream_t stream) {
+  TnExtra ex{};
+  ex.X = X, ex.ldx = ldx, ex.mean = mean, ex.rstd = rstd, ex.ca = ca, ex.cb = cb, ex.ck = ck;
+  return run_gemm_tn("gemm_tn_bn_bwd", A_BN, G, ldg, B, ldb, C, ldc, a_colsum, K, M, N, alpha, workspace,
+                     workspace_bytes, stream, ex);
+}
+
+extern "C" int rgbx_gemm_tn_rows_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rows,
+                                     int64_t n_rows, float* C, int64_t ldc, float* a_colsum, int64_t K, int64_t M,
+                                     int64_t N, float alpha, void* workspace, size_t workspace_bytes,
+                                     rgbx_stream_t stream) {
+  TnExtra ex{};
+  ex.rows = rows, ex.n_rows = n_rows;
+  return run_gemm_tn("gemm_tn_rows", A_ROWS, A, lda, B, ldb, C, ldc, a_colsum, K, M, N, alpha, workspace,
+                     workspace_bytes, stream, ex);
 }

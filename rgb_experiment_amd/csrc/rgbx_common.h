@@ -72,6 +72,15 @@ __device__ __forceinline__ void store_vec(float* p, const float (&v)[VEC]) {
   *reinterpret_cast<V*>(p) = t;
 }
 
+// BatchNorm's input gradient from the gradient g of its output, its input x and the per-column constants (mean, rstd,
+// ca = sum g / n, cb = sum g * xhat / n, ck = gamma * rstd): (g - a - (x - mu) * rs * b) * k. Shared by
+// bn_bwd_apply_kernel (bn.hip) and the GEMM that forms its A operand from (g, x) (gemm.hip), which must agree bit for
+// bit: every rounding is written out — two subtractions, a product, ONE fused multiply-add, a product — so that no
+// caller's surroundings decide what the compiler contracts.
+__device__ __forceinline__ float bn_bwd_input_grad(float g, float x, float mu, float rs, float a, float b, float k) {
+  return __fmul_rn(fmaf(-b, __fmul_rn(__fsub_rn(x, mu), rs), __fsub_rn(g, a)), k);
+}
+
 // Memory-bound grid cap: 256 CUs x 8 blocks of 256 threads, x4 so the tail is short.
 constexpr int kMaxGrid = 256 * 8 * 4;
 

@@ -174,6 +174,11 @@ class ConvStack(nn.Module):
             if affine is not None:  # eval forward: BatchNorm's affine map folded into the conv's weights
                 x = conv(x, edge_index, post_affine=affine, **ew)
             else:
+                if (extra.get("want_colsums") and getattr(conv, "owns_next_bn_backward", False)
+                        and hasattr(self.convs[i + 1], "forward_after_bn")):
+                    # x goes, with this training-mode BatchNorm, to the next conv's forward_after_bn and nowhere else: the
+                    # conv's node may own the BatchNorm's backward (ops.BNHandover) and fold its apply pass into its dW
+                    extra["next_bn"] = bn
                 x, pending = conv(x, edge_index, **extra), bn
         if ce is not None and not isinstance(x, tuple):  # a last conv without the loss epilogue (GATConv)
             x = ops.ce_from_logits(x, ce[0], ce[1])

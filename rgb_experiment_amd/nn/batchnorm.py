@@ -138,6 +138,14 @@ def train_backward(gy, x, weight, mean, rstd, n, reduce, grads_out=None, sums=No
     bwd_sums of this rank's rows and their all-reduced copy when the caller made both (asynchronous all-reduce:
     dist/stack.py); `reduce` is then not called."""
     gy = gy if gy.stride(-1) == 1 else gy.contiguous()
+    ca, cb, ck, gw, gb = train_backward_coefficients(gy, x, weight, mean, rstd, n, reduce, grads_out, sums)
+    return bwd_apply(gy, x, mean, rstd, ca, cb, ck), gw, gb
+
+
+def train_backward_coefficients(gy, x, weight, mean, rstd, n, reduce, grads_out=None, sums=None):
+    """Everything of train_backward but its apply pass: (ca, cb, ck, g_weight, g_bias) with
+    gx = bwd_apply(gy, x, mean, rstd, ca, cb, ck) — for a caller that forms gx inside its own kernel
+    (ops.gemm_tn_bn_bwd). `gy` has contiguous rows."""
     d = x.size(1)
     if sums is None:
         local = bwd_sums(gy, x, mean, rstd)            # [2, d]: sum gy, sum gy * xhat over the local rows
@@ -163,7 +171,7 @@ def train_backward(gy, x, weight, mean, rstd, n, reduce, grads_out=None, sums=No
             grads_out[0].copy_(gw)
             grads_out[1].copy_(gb)
             gw, gb = grads_out
-    return bwd_apply(gy, x, mean, rstd, ca, cb, ck), gw, gb
+    return ca, cb, ck, gw, gb
 
 
 class _AffineCols(torch.autograd.Function):

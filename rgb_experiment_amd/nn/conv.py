@@ -147,6 +147,7 @@ class GCNConv(nn.Module):
 
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # forward(..., want_colsums=True): the output may carry its column sums (ops.COLSUMS)
+    owns_next_bn_backward = True  # forward(..., next_bn=bn): see ops.propagate_linear
 
     def __init__(self, in_channels, out_channels):
         super().__init__()
@@ -162,7 +163,7 @@ class GCNConv(nn.Module):
     accepts_ce = True         # forward(..., ce=(y, mask)): the model's last layer may take the loss into its kernel
     accepts_ce_pair = True    # ... and mask may be (mask_a, mask_b): (None, [2, 3] statistics) of one eval forward
 
-    def forward(self, x, edge_index, edge_weight=None, post_affine=None, want_colsums=False, ce=None):
+    def forward(self, x, edge_index, edge_weight=None, post_affine=None, want_colsums=False, ce=None, next_bn=None):
         """`post_affine` = (scale, shift) of an eval-mode BatchNorm that follows this layer (no_grad only): a
         per-column affine map of a linear layer's output is the same layer with rows of W and b rescaled, so the
         normalisation costs two [out]-sized vector ops instead of a pass over [N, out].
@@ -170,14 +171,17 @@ class GCNConv(nn.Module):
         sums that BatchNorm needs (attribute ops.COLSUMS), taken from the MFMA tiles instead of a pass over it.
         `ce` = (y, mask): this is the model's last layer and the caller wants the masked cross-entropy of its logits,
         not the logits: returns (loss, stats [nll sum, selected rows, correct]); where the fused kernel runs the loss
-        is taken from the output tiles and the logits are never written (ops.propagate_linear_ce)."""
+        is taken from the output tiles and the logits are never written (ops.propagate_linear_ce).
+        `next_bn`: the training-mode BatchNorm1d this output goes through into the next conv's forward_after_bn, and
+        nowhere else; where the fused kernel runs, this layer's autograd node then owns that BatchNorm's backward
+        (ops.propagate_linear)."""
         if ce is not None:
             return self._ce(x, edge_index, ce, None, None, edge_weight)
         weight, bias = self.lin.weight, self.bias
         if post_affine is not None:
             scale, shift = post_affine
             weight, bias = weight * scale[:, None], bias * scale + shift
-        return self._conv(x, edge_index, weight, bias, want_colsums, edge_weight)
+        return self._conv(x, edge_index, weight, bias, want_colsums, edge_weight, next_bn)
 
     def eval_operands(self, bn=None):
         """(W'^T, b', None) of this layer for an eval forward, the eval-mode BatchNorm `bn` behind it folded in."""
@@ -239,7 +243,7 @@ class GCNConv(nn.Module):
                                            want_colsums=want_colsums)
         return self.forward(bn(x, colsums=colsums), edge_index, edge_weight, want_colsums=want_colsums)
 
-    def _conv(self, x, edge_index, weight, bias, want_colsums=False, edge_weight=None):
+    def _conv(self, x, edge_index, weight, bias, want_colsums=False, edge_weight=None, next_bn=None):
         graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING, edge_weight)
         if self._learned(edge_weight):
             # transform first, then the gather whose backward also differentiates the normalisation in the weights
@@ -247,7 +251,7 @@ class GCNConv(nn.Module):
         if ops.fused_linear_ok(graph, self.in_channels, self.out_channels, x=x):
             # A_hat (x W^T) + b = (A_hat x) W^T + b in one kernel: the aggregate stays in LDS and the GEMM
             # runs on the MFMA units underneath the gather (ops._PropagateLinear)
-            return ops.propagate_linear(x, graph, "gcn", weight, bias, want_colsums=want_colsums)
+            return ops.propagate_linear(x, graph, "gcn", weight, bias, want_colsums=want_colsums, next_bn=next_bn)
         if not x.requires_grad and self.in_channels <= self.out_channels:
             # Input layer (and every layer under no_grad): A_hat (x W^T) = (A_hat x) W^T. Aggregating first
             # costs the same forward (in <= out) and makes dW = dy^T (A_hat x) a plain weight-gradient GEMM: no
@@ -273,6 +277,7 @@ class SAGEConv(nn.Module):
 
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # see GCNConv
+    owns_next_bn_backward = True  # see GCNConv
 
     def __init__(self, in_channels, out_channels, aggr="mean"):
         super().__init__()
@@ -349,7 +354,7 @@ class SAGEConv(nn.Module):
                                            root_weight=self.lin_r.weight, colsums=colsums, want_colsums=want_colsums)
         return self.forward(bn(x, colsums=colsums), edge_index, want_colsums=want_colsums)
 
-    def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None):
+    def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None, next_bn=None):
         if self.aggr != "mean":
             return _finish_composed(self._forward_composed(x, edge_index), post_affine, ce)
         if ce is not None:
@@ -361,7 +366,8 @@ class SAGEConv(nn.Module):
         graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
         if ops.fused_linear_ok(graph, self.in_channels, self.out_channels, root=True, x=x):
             # lin_l(mean_j x_j) + lin_r(x_i) in one kernel: both products accumulate in the same MFMA tile
-            return ops.propagate_linear(x, graph, "mean", w_l, b_l, root_weight=w_r, want_colsums=want_colsums)
+            return ops.propagate_linear(x, graph, "mean", w_l, b_l, root_weight=w_r, want_colsums=want_colsums,
+                                        next_bn=next_bn)
         if self.in_channels > self.out_channels and x.is_cuda and not getattr(graph, "is_distributed", False):
             # in > out (the reference's defaults: F -> 64 -> C; graphsage2 at F = 1433 is the row its README marks OOM,
             # README.md:74): mean_j(x_j) W_l^T = mean_j(x_j W_l^T) — transform first, gather at the OUTPUT width
@@ -389,6 +395,7 @@ class MySAGEConv(nn.Module):
 
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # see GCNConv
+    owns_next_bn_backward = True  # see GCNConv
 
     def __init__(self, in_channels, out_channels, add_self_loops=True, aggr="mean"):
         super().__init__()
@@ -476,7 +483,7 @@ class MySAGEConv(nn.Module):
                                                colsums=colsums, want_colsums=want_colsums)
         return self.forward(bn(x, colsums=colsums), edge_index, want_colsums=want_colsums)
 
-    def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None):
+    def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None, next_bn=None):
         if self.aggr != "mean":
             return _finish_composed(self._forward_composed(x, edge_index), post_affine, ce)
         if ce is not None:
@@ -486,17 +493,18 @@ class MySAGEConv(nn.Module):
             scale, shift = post_affine
             w_l, b_l = w_l * scale[:, None], b_l * scale
             w_r, b_r = w_r * scale[:, None], b_r * scale + shift
-        out = self._conv(x, edge_index, w_l, b_l, w_r, b_r, want_colsums)
+        out = self._conv(x, edge_index, w_l, b_l, w_r, b_r, want_colsums, next_bn)
         if post_affine is not None and not self.add_self_loops:
             out = out * post_affine[0] + post_affine[1]
         return out
 
-    def _conv(self, x, edge_index, w_l, b_l, w_r, b_r, want_colsums=False):
+    def _conv(self, x, edge_index, w_l, b_l, w_r, b_r, want_colsums=False, next_bn=None):
         mode = LOOPS_REMOVE_ADD if self.add_self_loops else LOOPS_KEEP
         graph = get_graph(edge_index, x.size(0), mode)
         if self.add_self_loops and ops.fused_linear_ok(graph, self.in_channels, self.out_channels, root=True, x=x):
             # mean_j(lin_l(x_j)) + lin_r(x_i) = (mean_j x_j) Wl^T + x_i Wr^T + (b_l + b_r), one kernel
-            return ops.propagate_linear(x, graph, "mean", w_l, b_l + b_r, root_weight=w_r, want_colsums=want_colsums)
+            return ops.propagate_linear(x, graph, "mean", w_l, b_l + b_r, root_weight=w_r, want_colsums=want_colsums,
+                                        next_bn=next_bn)
         fused_left = self.add_self_loops and ops.fused_linear_ok(graph, self.in_channels, self.out_channels, x=x)
         input_layer = not x.requires_grad and self.add_self_loops and self.in_channels <= self.out_channels
         if x.is_cuda and not getattr(graph, "is_distributed", False) and not fused_left and not input_layer:

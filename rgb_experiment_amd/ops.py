@@ -1102,6 +1102,41 @@ def fold_bn_linear(weight, bias=None, bias2=None, root_weight=None, bn=None):
     return wt, b_out, wrt
 
 
+# The dense tail of the backward, one switch for both forms (tests, A/B runs; False = the launches as they were):
+#  - the conv that feeds a training-mode BatchNorm owns that BatchNorm's backward (BNHandover) and forms the input
+#    gradient inside its weight-gradient GEMM (gemm_tn_bn_bwd) instead of reading back a written one;
+#  - the last conv's weight gradient runs over the rows the loss selects (gemm_tn_rows).
+# Either way every result is the same, bit for bit.
+FUSE_DENSE_BACKWARD = True
+
+BN_HANDOVER = "_rgbx_bn_handover"  # attribute of a conv output whose node owns the backward of the BatchNorm behind it
+
+
+class BNHandover:
+    """Plain record between the node of a conv (`_PropagateLinear`, the producer) and the node of the conv that takes the
+    producer's output through a training-mode BatchNorm `bn` without writing BN(.) (`_BNPropagateLinear` /
+    `_PropagateLinearCE`, the consumer). The producer's output tensor then STANDS FOR the BatchNorm's output in the
+    autograd graph: the consumer returns g_h, the true gradient of BN's output, for it, and nothing for bn.weight /
+    bn.bias; the producer, which has them as inputs, runs BatchNorm's backward on g_h and its own output. The consumer's
+    forward fills in what that needs of the statistics — constants only (mean, rstd, row count, the reduction over
+    ranks). A record nobody filled (the consumer took another route) leaves the producer's backward as it was."""
+    __slots__ = ("bn", "mean", "rstd", "n", "reduce")
+
+    def __init__(self, bn):
+        self.bn, self.mean, self.rstd, self.n, self.reduce = bn, None, None, None, None
+
+    def fill(self, mean, rstd, n, reduce):
+        self.mean, self.rstd, self.n, self.reduce = mean, rstd, n, reduce
+
+
+def _take_handover(x, bn):
+    """The unfilled BNHandover riding on `x` for this `bn`, if x's node will run (it returns bn's gradients)."""
+    rec = getattr(x, BN_HANDOVER, None)
+    if rec is None or rec.bn is not bn or rec.mean is not None or not x.requires_grad or not FUSE_DENSE_BACKWARD:
+        return None
+    return rec
+
+
 class _PropagateLinear(torch.autograd.Function):
     """y = (P x) W^T + b (+ x Wr^T) with P = A_hat ('gcn'), the mean operator ('mean') or the plain edge sum ('sum'), in one launch
     (rgbx_spmm_linear_f32). Backward: dW = dy^T (P x) on the split-K MFMA kernel (P x was stored by the
@@ -1111,9 +1146,12 @@ class _PropagateLinear(torch.autograd.Function):
     root part as its additive term."""
 
     @staticmethod
-    def forward(ctx, x, graph, kind, weight, bias, need_z=True, root_weight=None, x_root=None, want_colsums=False):
+    def forward(ctx, x, graph, kind, weight, bias, need_z=True, root_weight=None, x_root=None, want_colsums=False,
+                bn_weight=None, bn_bias=None, handover=None):
         """`x_root`: the targets' own rows when they are not simply the first rows of `x` viewed as a separate
-        tensor (partitioned graph: x = [local; halo], x_root = local). `want_colsums`: returns (out, colsums)."""
+        tensor (partitioned graph: x = [local; halo], x_root = local). `want_colsums`: returns (out, colsums).
+        `handover` (BNHandover, with the parameters of its BatchNorm as `bn_weight` / `bn_bias`): this node owns the
+        backward of the training-mode BatchNorm behind it, once the consumer has filled the record."""
         x = x.contiguous()
         xr = x if x_root is None else x_root.contiguous()
         w = graph.w if kind == "gcn" else None          # properties: each builds its vector on first use only
@@ -1125,8 +1163,9 @@ class _PropagateLinear(torch.autograd.Function):
                               None if root_weight is None else weight_t(root_weight),
                               kind=f"{getattr(graph, 'event_prefix', '')}{kind}_linear_fwd", want_colsums=want_colsums)
         out, z = res[0], res[1]
-        ctx.save_for_backward(z, weight, root_weight, xr if root_weight is not None else None)
-        ctx.graph, ctx.kind, ctx.has_bias = graph, kind, bias is not None
+        ctx.save_for_backward(z, weight, root_weight, xr if root_weight is not None else None,
+                              bn_weight if handover is not None else None, out if handover is not None else None)
+        ctx.graph, ctx.kind, ctx.has_bias, ctx.handover = graph, kind, bias is not None, handover
         if want_colsums:
             ctx.mark_non_differentiable(res[2])
             return out, res[2]
@@ -1134,12 +1173,26 @@ class _PropagateLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _g_colsums=None):
-        z, weight, root_weight, x = ctx.saved_tensors
+        z, weight, root_weight, x, bn_weight, y = ctx.saved_tensors
         g, kind = ctx.graph, ctx.kind
         gy = gy.contiguous()
-        gx = gw = gb = gwr = None
+        gx = gw = gb = gwr = g_bnw = g_bnb = None
         want_b = ctx.has_bias and ctx.needs_input_grad[4]
-        if ctx.needs_input_grad[3]:
+        rec, bn_a = ctx.handover, None
+        if rec is not None and rec.mean is not None:
+            # gy is g_h, the gradient of BN(y): BatchNorm's backward runs here — its column sums and coefficients as ever,
+            # its apply pass inside the dW GEMM unless something else reads gx too (dx, dWr, a bias gradient on its own)
+            from .nn import batchnorm as B
+            ca, cb, ck, g_bnw, g_bnb = B.train_backward_coefficients(gy, y, bn_weight, rec.mean, rec.rstd, rec.n,
+                                                                     rec.reduce)
+            if (ctx.needs_input_grad[0] or (root_weight is not None and ctx.needs_input_grad[6])
+                    or not ctx.needs_input_grad[3]):
+                gy = B.bwd_apply(gy, y, rec.mean, rec.rstd, ca, cb, ck)
+            else:
+                bn_a = (y, rec.mean, rec.rstd, ca, cb, ck)
+        if bn_a is not None:
+            gw, gb = gemm_tn_bn_bwd(gy, *bn_a, z, colsum=want_b)
+        elif ctx.needs_input_grad[3]:
             if want_b:
                 gw, gb = gemm_tn(gy, z, colsum=True)  # dy is read once for dW and db
             else:
@@ -1150,7 +1203,7 @@ class _PropagateLinear(torch.autograd.Function):
             gwr = gemm_tn(gy, x)
         if ctx.needs_input_grad[0]:
             gx = _propagate_linear_input_grad(g, kind, gy, weight, root_weight)
-        return gx, None, None, gw, gb, None, gwr, None, None
+        return gx, None, None, gw, gb, None, gwr, None, None, g_bnw, g_bnb, None
 
 
 def _propagate_linear_input_grad(g, kind, gy, weight, root_weight, ce_sel=None):
@@ -1187,10 +1240,15 @@ class _BNPropagateLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bn_weight, bn_bias, graph, kind, weight, bias, root_weight, eps, reduce, running, need_z,
-                colsums=None, want_colsums=False):
+                colsums=None, want_colsums=False, handover=None):
+        """`handover` (BNHandover): x's node owns BatchNorm's backward; x then stands for BN(x) in the graph and this
+        node's backward returns g_h for it."""
         from .nn import batchnorm as B
         x = x.contiguous()
         mean, rstd, scale, shift, n = B.train_statistics(x, bn_weight, bn_bias, eps, reduce, running, colsums)
+        if handover is not None:
+            handover.fill(mean, rstd, n, reduce)
+        ctx.handed_over = handover is not None
         w, rs = (graph.w, None) if kind == "gcn" else (None, graph.inv_deg)
         res = spmm_linear_raw(graph.fwd, w, rs, x, weight_t(weight), None if bias is None else bias.detach(), need_z,
                               x if root_weight is not None else None,
@@ -1221,8 +1279,10 @@ class _BNPropagateLinear(torch.autograd.Function):
             # dWr = dy^T BN(x) = (dy^T x) diag(s) + colsum(dy) t^T
             gwr = gemm_tn(gy, x) * scale + gcol[:, None] * shift
         g_h = _propagate_linear_input_grad(g, kind, gy, weight, root_weight)
+        if ctx.handed_over:
+            return g_h, None, None, None, None, gw, gb, gwr, None, None, None, None, None, None, None
         gx, g_bnw, g_bnb = B.train_backward(g_h, x, bn_weight, mean, rstd, n, ctx.reduce)
-        return gx, g_bnw, g_bnb, None, None, gw, gb, gwr, None, None, None, None, None, None
+        return gx, g_bnw, g_bnb, None, None, gw, gb, gwr, None, None, None, None, None, None, None
 
 
 _SCALE_CACHE = {}
@@ -1351,9 +1411,12 @@ class _PropagateLinearCE(torch.autograd.Function):
         x = x.contiguous()
         pre = None
         if bn_weight is not None:
-            eps, reduce, running, colsums = bn_args
+            eps, reduce, running, colsums, handover = bn_args
             mean, rstd, scale, shift, n = B.train_statistics(x, bn_weight, bn_bias, eps, reduce, running, colsums)
             pre = (scale, shift, graph.rowsum(kind))
+            if handover is not None:  # x's node owns BatchNorm's backward (BNHandover): the backward returns g_h for x
+                handover.fill(mean, rstd, n, reduce)
+        ctx.handed_over = bn_weight is not None and bn_args[4] is not None
         w, rs = (graph.w, None) if kind == "gcn" else (None, graph.inv_deg)
         grad_scale = mask_scale(y, mask, weight.size(0)) if want_grad else None
         dlogits, z, stats = spmm_linear_raw(
@@ -1389,7 +1452,9 @@ class _PropagateLinearCE(torch.autograd.Function):
         gw = gb = gwr = gx = g_bnw = g_bnb = None
         gcol = None
         if ctx.needs_input_grad[3]:  # z was stored by the forward exactly when the weight wants a gradient
-            gw, gcol = gemm_tn(gy, z, colsum=True)
+            # gy is zero outside the rows the loss selects: the product runs over the list of those rows where it exists
+            rows = selected_rows(*ctx.ce_sel) if FUSE_DENSE_BACKWARD else None
+            gw, gcol = gemm_tn_rows(gy, z, rows, colsum=True)
         if ctx.has_bias and ctx.needs_input_grad[4]:
             gb = gcol if gcol is not None else gy.sum(0)
         if root_weight is not None and ctx.needs_input_grad[5]:
@@ -1409,7 +1474,7 @@ class _PropagateLinearCE(torch.autograd.Function):
         gw, gb, gwr = sc.get("gw"), sc.get("gb"), sc.get("gwr")
         if need_h:
             g_h = _propagate_linear_input_grad(graph, kind, gy, sc["w"], sc.get("wr"), ce_sel=ctx.ce_sel)
-            if ctx.has_bn:
+            if ctx.has_bn and not ctx.handed_over:
                 gx, g_bnw, g_bnb = B.train_backward(g_h, x, bn_weight, mean, rstd, n, ctx.reduce)
             else:
                 gx = g_h
@@ -1424,7 +1489,7 @@ def propagate_linear_ce(x, graph, kind, weight, bias, root_weight, y, mask, bn=N
         t is not None and t.requires_grad
         for t in (weight, x, bias, root_weight) + ((bn.weight, bn.bias) if bn is not None else ()))
     if bn is not None:
-        bn_args = (bn.eps, bn._reduce, bn.begin_training_step(), colsums)
+        bn_args = (bn.eps, bn._reduce, bn.begin_training_step(), colsums, _take_handover(x, bn) if want_grad else None)
         return _PropagateLinearCE.apply(x, graph, kind, weight, bias, root_weight, y, mask, want_grad, bn.weight, bn.bias,
                                         bn_args)
     return _PropagateLinearCE.apply(x, graph, kind, weight, bias, root_weight, y, mask, want_grad, None, None, None)
@@ -1436,7 +1501,8 @@ def bn_propagate_linear(x, bn, graph, kind, weight, bias=None, root_weight=None,
     `colsums`: the [2, d] column sums of x and x^2 if the launch that produced x already took them."""
     need_z = weight.requires_grad
     return _tag_colsums(_BNPropagateLinear.apply(x, bn.weight, bn.bias, graph, kind, weight, bias, root_weight, bn.eps,
-                                                 bn._reduce, bn.begin_training_step(), need_z, colsums, want_colsums),
+                                                 bn._reduce, bn.begin_training_step(), need_z, colsums, want_colsums,
+                                                 _take_handover(x, bn)),
                         want_colsums)
 
 
@@ -1453,14 +1519,22 @@ def _tag_colsums(res, want_colsums):
     return out
 
 
-def propagate_linear(x, graph, kind, weight, bias=None, root_weight=None, want_colsums=False):
+def propagate_linear(x, graph, kind, weight, bias=None, root_weight=None, want_colsums=False, next_bn=None):
+    """`next_bn`: the training-mode BatchNorm1d the caller will hand, with this output, to the next conv
+    (forward_after_bn) and to nothing else: this node then owns that BatchNorm's backward (BNHandover)."""
     if _is_dist(graph):  # resident input features of a partitioned graph (fused_linear_ok checked it)
         return graph.propagate_linear(x, kind, weight, bias, root_weight)
     # the aggregate is kept only when the weight gradient (dy^T (P x)) will be asked for; Function.forward
     # cannot see the caller's grad mode, so the decision is taken here
     need_z = torch.is_grad_enabled() and weight.requires_grad
-    return _tag_colsums(_PropagateLinear.apply(x, graph, kind, weight, bias, need_z, root_weight, None, want_colsums),
-                        want_colsums)
+    if next_bn is None or not FUSE_DENSE_BACKWARD or not torch.is_grad_enabled():
+        return _tag_colsums(_PropagateLinear.apply(x, graph, kind, weight, bias, need_z, root_weight, None, want_colsums),
+                            want_colsums)
+    rec = BNHandover(next_bn)
+    out = _tag_colsums(_PropagateLinear.apply(x, graph, kind, weight, bias, need_z, root_weight, None, want_colsums,
+                                              next_bn.weight, next_bn.bias, rec), want_colsums)
+    setattr(out, BN_HANDOVER, rec)
+    return out
 
 
 def appnp_raw(csr, w, h, K, alpha, kind="appnp"):
@@ -2711,6 +2785,59 @@ def gemm_tn(a, b, alpha=1.0, colsum=False, out=None, sums_out=None):
     with _Timed("gemm_tn", f"{M}x{N}" if _EVENT_SINK is not None else None):
         _lib.check(lib.rgbx_gemm_tn_f32(pa, lda, pb, ldb, _lib.ptr(out), N, _lib.ptr(sums), K, M, N, float(alpha),
                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "rgbx_gemm_tn_f32")
+    return (out, sums) if colsum else out
+
+
+def _gemm_tn_v4(*mats):
+    """Operands the 16-byte-only forms of the GEMM take as they are: float32 device matrices, contiguous 16-byte aligned
+    rows, widths that are multiples of 4."""
+    return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.size(1) % 4 == 0
+               and t.stride(0) % 4 == 0 and t.stride(0) >= t.size(1) and t.data_ptr() % 16 == 0 for t in mats)
+
+
+def _gemm_tn_buffers(K, M, N, device, colsum):
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_lib.load().rgbx_gemm_tn_workspace_bytes(K, M, N, ctypes.byref(nbytes)), "rgbx_gemm_tn_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=device)
+    out = torch.empty((M, N), dtype=torch.float32, device=device)
+    return ws, out, torch.empty(M, dtype=torch.float32, device=device) if colsum else None
+
+
+def gemm_tn_bn_bwd(g, x, mean, rstd, ca, cb, ck, b, colsum=False):
+    """gemm_tn(gx, b, colsum=colsum) for gx = BatchNorm's input gradient bwd_apply(g, x, mean, rstd, ca, cb, ck), which
+    is formed inside the GEMM as its A tiles are staged (rgbx_gemm_tn_bn_bwd_f32) instead of being written and read
+    back: same result, bit for bit. Operands off the 16-byte path take the two launches."""
+    from .nn import batchnorm as B
+    _lib.require_device(g, x, b)
+    if not _gemm_tn_v4(g, x, b) or g.shape != x.shape:
+        res = gemm_tn(B.bwd_apply(g, x, mean, rstd, ca, cb, ck), b, colsum=colsum)
+        return res if colsum else (res, None)
+    K, M, N = g.size(0), g.size(1), b.size(1)
+    consts = [t.contiguous() for t in (mean, rstd, ca, cb, ck)]
+    ws, out, sums = _gemm_tn_buffers(K, M, N, g.device, colsum)
+    (pg, ldg), (px, ldx), (pb, ldb) = (_lib.mat(t, n) for t, n in ((g, "g"), (x, "x"), (b, "b")))
+    with _Timed("gemm_tn", f"{M}x{N}+bn_bwd" if _EVENT_SINK is not None else None):
+        _lib.check(_lib.load().rgbx_gemm_tn_bn_bwd_f32(
+            pg, ldg, px, ldx, *(_lib.ptr(t) for t in consts), pb, ldb, _lib.ptr(out), N, _lib.ptr(sums), K, M, N, 1.0,
+            _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "rgbx_gemm_tn_bn_bwd_f32")
+    return out, sums
+
+
+def gemm_tn_rows(a, b, rows, colsum=False):
+    """gemm_tn(a, b, colsum=colsum) for an `a` that is zero outside the rows of the ascending int32 device list `rows`
+    (selected_rows): only those rows of a and b are read (rgbx_gemm_tn_rows_f32), every non-zero product is added where
+    the full product adds it: same result, bit for bit. rows = None, or operands off the 16-byte path: the full
+    product."""
+    _lib.require_device(a, b)
+    if rows is None or not _gemm_tn_v4(a, b) or a.size(0) != b.size(0) or a.size(0) >= 2**31:
+        return gemm_tn(a, b, colsum=colsum)
+    K, M, N = a.size(0), a.size(1), b.size(1)
+    ws, out, sums = _gemm_tn_buffers(K, M, N, a.device, colsum)
+    (pa, lda), (pb, ldb) = _lib.mat(a, "a"), _lib.mat(b, "b")
+    with _Timed("gemm_tn", f"{M}x{N}+rows" if _EVENT_SINK is not None else None):
+        _lib.check(_lib.load().rgbx_gemm_tn_rows_f32(
+            pa, lda, pb, ldb, _lib.ptr(rows), rows.numel(), _lib.ptr(out), N, _lib.ptr(sums), K, M, N, 1.0,
+            _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "rgbx_gemm_tn_rows_f32")
     return (out, sums) if colsum else out
 
 
