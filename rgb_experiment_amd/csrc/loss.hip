@@ -120,15 +120,18 @@ nll_acc_kernel(const float* __restrict__ logp, int64_t ld, const int64_t* __rest
   }
 }
 
-// logsumexp of one row by a wave (lane-strided), plus the arg-max (lowest index on ties); every lane gets both
-__device__ __forceinline__ void row_lse_argmax(const float* __restrict__ row, int C, int lane, float& lse, int& arg) {
-  float best;
+// logsumexp of one row by a wave (lane-strided) as its two parts, the maximum `best` and `ls` = log sum exp(z - best),
+// plus the arg-max (lowest index on ties); every lane gets all three. The parts stay apart: their float32 sum rounds
+// at ulp(|best|) / 2 (8e-6 at logits of +-150), which softmax = exp(z - lse) would inherit as a RELATIVE error, while
+// (z - best) - ls is exact in its first step wherever the result matters.
+__device__ __forceinline__ void row_lse_argmax(const float* __restrict__ row, int C, int lane, float& best, float& ls,
+                                               int& arg) {
   row_argmax(row, C, lane, best, arg);
   wave_argmax(best, arg);
   float s = 0.f;
   for (int c = lane; c < C; c += 64) s += expf(row[c] - best);
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  lse = best + logf(s);
+  ls = logf(s);
 }
 
 // Cross-entropy from logits over the selected rows: loss = sum(lse_i - z[i, y_i]), count, arg-max hits.
@@ -152,12 +155,12 @@ ce_fwd_kernel(const float* __restrict__ z, int64_t ld, const int64_t* __restrict
       const int r0 = __builtin_ctzll(sel);
       sel &= sel - 1;
       const float* row = z + (base + r0) * ld;
-      float lse;
+      float best, ls;
       int arg;
-      row_lse_argmax(row, C, lane, lse, arg);
+      row_lse_argmax(row, C, lane, best, ls, arg);
       const int t0 = __shfl(t, r0);
       if (lane == 0) {
-        loss += (double)(lse - row[t0]);
+        loss += (double)(best - row[t0]) + (double)ls;
         cnt += 1.0;
         hit += arg == t0 ? 1.0 : 0.0;
       }
@@ -193,17 +196,18 @@ ce_bwd_kernel(const float* __restrict__ z, int64_t ld, const int64_t* __restrict
       continue;
     }
     const float* row = z + i * ld;
-    float lse;
+    float best, ls;
     int arg;
-    row_lse_argmax(row, C, lane, lse, arg);
-    for (int c = lane; c < C; c += 64) g[c] = s * (expf(row[c] - lse) - (c == t ? 1.f : 0.f));
+    row_lse_argmax(row, C, lane, best, ls, arg);
+    for (int c = lane; c < C; c += 64) g[c] = s * (expf((row[c] - best) - ls) - (c == t ? 1.f : 0.f));
   }
 }
 
 // ---- C % 4 == 0, C <= 256: a row is ONE float4 per lane of a group of LPR = pow2ceil(C / 4) lanes, so a wave holds
 // 64 / LPR rows in registers at once: one global read per row, group-wide shuffles for max / sum / arg-max.
-__device__ __forceinline__ void group_lse_argmax(const float (&v)[4], int c, int C, int lpr, float& lse, int& arg) {
-  float best = -INFINITY;
+__device__ __forceinline__ void group_lse_argmax(const float (&v)[4], int c, int C, int lpr, float& best, float& ls,
+                                                 int& arg) {
+  best = -INFINITY;
   arg = INT32_MAX;
   if (c < C) {
 #pragma unroll
@@ -221,7 +225,7 @@ __device__ __forceinline__ void group_lse_argmax(const float (&v)[4], int c, int
     for (int k = 0; k < 4; ++k) s += expf(v[k] - best);
   }
   for (int off = lpr >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  lse = best + logf(s);
+  ls = logf(s);
 }
 
 // BLK: the logits are BLOCKED (element (i, c) at z + (c / bc) * bs + i * bc + c % bc: column slices as a node-partitioned
@@ -270,15 +274,15 @@ ce_fwd_vec_kernel(const float* __restrict__ z, int64_t ld, const int64_t* __rest
           load_vec<4>(v, row + c);
         }
       }
-      float lse;
+      float best, ls;
       int arg;
-      group_lse_argmax(v, c, C, lpr, lse, arg);
+      group_lse_argmax(v, c, C, lpr, best, ls, arg);
       const int tr = __shfl(t, myrow >= 0 ? myrow : 0);
       if (myrow >= 0 && c == 0) {
         float zt;
         if constexpr (BLK) zt = z[(int64_t)(tr / (int)bc) * bs + ri * bc + (tr % (int)bc)] + (bias ? bias[tr] : 0.f);
         else zt = row[tr];
-        loss += (double)(lse - zt);
+        loss += (double)(best - zt) + (double)ls;
         cnt += 1.0;
         hit += arg == tr ? 1.0 : 0.0;
       }
@@ -328,13 +332,13 @@ ce_bwd_vec_kernel(const float* __restrict__ z, int64_t ld, const int64_t* __rest
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int64_t i = i0 + r * nr + grp;
-      float lse;
+      float best, ls;
       int arg;
-      group_lse_argmax(v[r], c, C, lpr, lse, arg);  // every lane takes part in the shuffles
+      group_lse_argmax(v[r], c, C, lpr, best, ls, arg);  // every lane takes part in the shuffles
       if (i < N && c < C) {
         float g[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) g[k] = t[r] >= 0 ? s * (expf(v[r][k] - lse) - (c + k == t[r] ? 1.f : 0.f)) : 0.f;
+        for (int k = 0; k < 4; ++k) g[k] = t[r] >= 0 ? s * (expf((v[r][k] - best) - ls) - (c + k == t[r] ? 1.f : 0.f)) : 0.f;
         store_vec<4>(grad + i * ldg + c, g);
       }
     }

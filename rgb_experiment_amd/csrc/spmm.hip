@@ -382,10 +382,10 @@ __global__ void __launch_bounds__(256) spmm_tile_epilogue_kernel(const SpmmArgs 
       }
     } else {
       float e[VEC] = {0.f, 0.f, 0.f, 0.f};
-      float lse = 0.f;
+      float best = 0.f, ls = 0.f;  // logsumexp as its two parts (see row_lse_argmax in loss.hip)
       if (tgt >= 0) {
         // NLLLoss(log_softmax(z))_i = lse_i - z[i, y_i]; arg-max = the first maximal column (rgbx_masked_ce_fwd_f32)
-        float best = -INFINITY;
+        best = -INFINITY;
         int arg = INT32_MAX;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
@@ -411,8 +411,8 @@ __global__ void __launch_bounds__(256) spmm_tile_epilogue_kernel(const SpmmArgs 
           se += __shfl_xor(se, off);
           tv += __shfl_xor(tv, off);  // exactly one lane of the group holds the target column
         }
-        lse = best + logf(se);
-        const double term = (double)(lse - tv);
+        ls = logf(se);
+        const double term = (double)(best - tv) + (double)ls;
         const int h = arg == tgt ? 1 : 0;
         if (bits & 1) { nll += term; cnt += 1; hit += h; }
         if (bits & 2) { nll2 += term; cnt2 += 1; hit2 += h; }
@@ -422,7 +422,7 @@ __global__ void __launch_bounds__(256) spmm_tile_epilogue_kernel(const SpmmArgs 
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
           const bool valid = c + i < E.C;
-          gr[i] = (tgt >= 0 && valid) ? sc * (expf(r[i] - lse) - (c + i == tgt ? 1.f : 0.f)) : 0.f;
+          gr[i] = (tgt >= 0 && valid) ? sc * (expf((r[i] - best) - ls) - (c + i == tgt ? 1.f : 0.f)) : 0.f;
         }
         using f4v = __attribute__((ext_vector_type(4))) float;
         f4v o = {gr[0], gr[1], gr[2], gr[3]};
