@@ -28,6 +28,7 @@
  *   rgbx_gat_*            GATConv.forward/message + segment softmax (models/gat.py:28,30) [PyG].
  *   rgbx_supergat_*       SuperGATConv ('MX' attention, attention loss, negative sampling; models/supergat.py) [PyG].
  *   rgbx_gatv2_*          GATv2Conv (dynamic attention) [PyG]; not in the reference's zoo, shaped like models/gat.py.
+ *   rgbx_transformer_*    TransformerConv (scaled dot-product attention) [PyG]; not in the reference's zoo.
  *   rgbx_gemm_tn_f32      dW = dY^T X of the nn.Linear / conv.lin layers under loss.backward()
  *                         (itexperiments.py:439; layers at models/gcn.py:18-21, appnp_stack.py:19-20).
  *   rgbx_bn_* / rgbx_affine_cols_f32
@@ -777,6 +778,53 @@ int rgbx_gatv2_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const 
 
 /* keep[p * H + h] = 1 where (forward CSR slot p, head h) survives the attention dropout. */
 int rgbx_gatv2_draws_u8(const uint32_t* seed, int64_t nnz, int H, float p_drop, uint8_t* keep, rgbx_stream_t stream);
+
+/* ---- TransformerConv: scaled dot-product attention over the in-edges --------------------------------------------- */
+
+/* For an edge j -> i (p = its slot in the target-grouped CSR) and head h, with q, k, v [N, H*C] (each with its own
+ * pointer and leading dimension; column blocks of one wider matrix are taken as they are):
+ *   e_p    = <q[i,h,:], k[j,h,:]> * scale     (scale = 1 / sqrt(C) of the TRUE head width: the caller passes it, so
+ *                                              zero-padding a head changes nothing)
+ *   alpha  = softmax over the in-edges of i of e_p (online, max-shifted)
+ *   out[i,h,:] = sum_p alpha_p * kappa_p * v[j,h,:]
+ * (TransformerConv.forward / message [PyG]; Shi et al., "Masked Label Prediction". The reference's zoo has no
+ * TransformerConv.) The scored row k_j is not the message v_j: two rows are gathered per slot. The edges are taken as
+ * they are (RGBX_LOOPS_KEEP): a row WITHOUT slots stores exact zeros in `out`, the state m = rden = 0, the record
+ * (0, 0) and a zero g_q row; a source without out-edges gets zero g_k and g_v rows. Every output row is written.
+ *
+ * Attention dropout as for rgbx_gatv2_*: `seed` = two 32-bit words ON THE DEVICE, NULL = no dropout; the keep bit of
+ * (forward CSR slot, head) is the same hash, so rgbx_gatv2_draws_u8 writes these decisions out as well. No entry point
+ * uses float atomics: two runs are bit-identical. */
+
+/* 1 if the kernels take H heads of C channels (the set of rgbx_gatv2_supported), else 0. */
+int rgbx_transformer_supported(int H, int C);
+
+/* Forward over the target-grouped CSR: one gather pass with an online softmax. m / rden ([N, H], of the UNDROPPED
+ * softmax) are saved for the backward; both NULL = inference form (and then seed must be NULL). `split`: hub rows as
+ * in rgbx_gatv2_fwd_f32; split->partial holds n_chunks * (H*C + 2*H) floats, merged in chunk order. */
+int rgbx_transformer_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* q, int64_t ldq, const float* k,
+                             int64_t ldk, const float* v, int64_t ldv, float* out, int64_t ldo, float* m, float* rden,
+                             int64_t N, int H, int C, float scale, const uint32_t* seed, float p_drop,
+                             const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward. Per edge and head, with D_i = <gout_i, out_i>:  de = alpha (kappa <gout_i, v_j> - D_i).
+ * Target side, over the forward CSR: g_q[i,h,:] = scale * sum_p de k_j and the record nodeq[i,h] = (m - log(rden), D_i)
+ * ([N, H, 2], 8-byte aligned) of the source side. split->partial holds n_chunks * H*C floats. */
+int rgbx_transformer_bwd_dst_f32(const int32_t* rowptr, const int32_t* col, const float* q, int64_t ldq, const float* k,
+                                 int64_t ldk, const float* v, int64_t ldv, const float* m, const float* rden,
+                                 const float* out, int64_t ldo, const float* gout, int64_t ldg, float* nodeq, float* g_q,
+                                 int64_t ldgq, int64_t N, int H, int C, float scale, const uint32_t* seed, float p_drop,
+                                 const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i), run AFTER the target side:
+ *   g_k[j,h,:] = scale * sum_p de q_i,   g_v[j,h,:] = sum_p alpha_p kappa_p gout[i,h,:].
+ * `t2f` ([E'], needed when seed != NULL): the forward CSR slot of every transposed slot (the key of its keep bit).
+ * split->partial holds n_chunks * 2*H*C floats (g_k | g_v per chunk). */
+int rgbx_transformer_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const float* q,
+                                 int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                 const float* nodeq, const float* gout, int64_t ldg, float* g_k, int64_t ldgk,
+                                 float* g_v, int64_t ldgv, int64_t N, int H, int C, float scale, const uint32_t* seed,
+                                 float p_drop, const rgbx_row_split_t* split, rgbx_stream_t stream);
 
 /* ---- dense layers on the MFMA units -------------------------------------------------------- */
 

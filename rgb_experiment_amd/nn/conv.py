@@ -908,6 +908,91 @@ class GATv2Conv(nn.Module):
         return out
 
 
+class TransformerConv(nn.Module):
+    """UniMP's layer [PyG TransformerConv; Shi et al., "Masked Label Prediction"]: q = lin_query(x), k = lin_key(x),
+    v = lin_value(x) viewed [N,H,C]; for an edge j -> i: e_ij = <q_i, k_j> / sqrt(C) per head, softmax over the in-edges
+    of i — the edges AS GIVEN (self-loops stay, duplicates count twice, a node without in-edges aggregates zeros) —
+    dropout on the coefficients, out_i = sum_j alpha_ij v_j; heads concatenated or averaged; root skip
+    x_r = lin_skip(x): out + x_r, or with beta: b = sigmoid(lin_beta([out, x_r, out - x_r])), b x_r + (1 - b) out.
+    Parameter names are PyG's (lin_key, lin_query, lin_value, lin_skip, lin_beta; `bias` is lin_skip's, the three
+    projections always carry one; lin_skip exists without root_weight too, unused, as in PyG). The attention runs in
+    the rgbx_transformer_* kernels (ops.transformer_attend); the root / gate arithmetic is dense per-node work."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None,
+                 bias=True, root_weight=True):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("TransformerConv: edge features (edge_dim) are not built")
+        if not (0.0 <= dropout < 1.0):
+            raise ValueError("TransformerConv: dropout in [0, 1)")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.heads, self.concat, self.dropout, self.edge_dim = heads, concat, dropout, edge_dim
+        self.root_weight, self.beta = root_weight, bool(beta and root_weight)
+        wide = heads * out_channels
+        self.lin_key = nn.Linear(in_channels, wide)
+        self.lin_query = nn.Linear(in_channels, wide)
+        self.lin_value = nn.Linear(in_channels, wide)
+        self.lin_skip = nn.Linear(in_channels, wide if concat else out_channels, bias=bias)
+        if self.beta:
+            self.lin_beta = nn.Linear(3 * (wide if concat else out_channels), 1, bias=False)
+        else:
+            self.lin_beta = None
+        self.last_draw = {}  # dropout seed of the last forward (ops.transformer_random_choices)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip, self.lin_beta):
+            if lin is not None:
+                lin.reset_parameters()  # the Linear's own default, as in PyG's layer
+
+    def _padded(self, lin, Cp):
+        """(weight, bias) of a projection with every head padded to Cp channels by zero rows / entries."""
+        H, C = self.heads, self.out_channels
+        if Cp == C:
+            return lin.weight, lin.bias
+        pad = torch.nn.functional.pad
+        weight = pad(lin.weight.view(H, C, -1), (0, 0, 0, Cp - C)).reshape(H * Cp, -1)
+        return weight, pad(lin.bias.view(H, C), (0, Cp - C)).reshape(-1)
+
+    def forward(self, x, edge_index):
+        _lib.require_device(x)
+        H, C = self.heads, self.out_channels
+        Cp = GATConv.kernel_channels(C)  # other widths: zero weight rows and bias entries per head
+        F = H * Cp
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        # one product over [W_q; W_k; W_v; W_skip]: the four projections are its column blocks, k and v of a source
+        # side by side
+        blocks = [self._padded(lin, Cp) for lin in (self.lin_query, self.lin_key, self.lin_value)]
+        S = self.lin_skip.weight.size(0)
+        if self.root_weight:
+            # the skip block is padded to a multiple of 4 columns with zero weight rows: the rows of q, k and v (views
+            # into the product) keep the 16-byte alignment the wide head widths (C > 128: 4 floats per lane) need
+            w_skip, b_skip, extra = self.lin_skip.weight, self.lin_skip.bias, -S % 4
+            if b_skip is None:
+                b_skip = torch.zeros(S, dtype=x.dtype, device=x.device)
+            if extra:
+                pad = torch.nn.functional.pad
+                w_skip, b_skip = pad(w_skip, (0, 0, 0, extra)), pad(b_skip, (0, extra))
+            blocks.append((w_skip, b_skip))
+        h = ops.linear(x, torch.cat([w for w, _ in blocks]), torch.cat([b for _, b in blocks]))
+        self.last_draw = {}
+        # the scale is that of the true head width: zero-padded channels add nothing to a dot product
+        out = ops.transformer_attend(h[:, :F], h[:, F:2 * F], h[:, 2 * F:3 * F], graph, H, Cp, 1.0 / math.sqrt(C),
+                                     training=self.training, p_drop=self.dropout, record=self.last_draw)
+        if Cp != C:
+            out = out.view(-1, H, Cp)[:, :, :C].reshape(-1, H * C)
+        if not self.concat:
+            out = out.view(-1, H, C).mean(dim=1)
+        if self.root_weight:
+            x_r = h[:, 3 * F:3 * F + S]
+            if self.beta:
+                b = torch.sigmoid(ops.linear(torch.cat([out, x_r, out - x_r], dim=-1), self.lin_beta.weight))
+                out = b * x_r + (1.0 - b) * out
+            else:
+                out = out + x_r
+        return out
+
+
 class FAConv(nn.Module):
     """FAGCN's layer [PyG FAConv; reference models/fagcn.py]: for an edge j -> i of the GCN-normalised graph (self-loops
     removed then re-added, w_ij = 1/sqrt(d_i d_j)), a_ij = tanh(<x_j, att_l> + <x_i, att_r>) — signed, no softmax —

@@ -2561,6 +2561,117 @@ def gatv2_attend(xl, xr, att, graph, H, C, slope=0.2, bias=None, training=False,
                               want_grad)
 
 
+def transformer_random_choices(record, graph, H):
+    """The attention-dropout decisions of the training forward that filled `record` (TransformerConv keeps the record
+    of its last forward): {'keep': bool [E, H] in forward CSR slot order (True = kept), 'src' / 'dst': int64 [E]
+    endpoints of every forward CSR slot}. The keep hash is GATv2's, so its inspection entry point serves."""
+    return gatv2_random_choices(record, graph, H)
+
+
+class _TransformerAttend(torch.autograd.Function):
+    """One TransformerConv attention block as a single autograd node: fused scaled dot-product score + edge-softmax +
+    aggregation of the value rows (+ attention dropout in training mode); backward = target-side pass (g_q and the
+    per-node record), source-side pass (g_k, g_v). Saves q, k, v, out, m / rden [N, H] and the dropout seed; nothing
+    per edge (the backward recomputes scores and keep bits)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, graph, H, C, scale, train, p_drop, record, want_grad):
+        _lib.require_device(q, k, v)
+        lib = _lib.load()
+        # column blocks of one product stay views
+        q, k, v = (t if t.dim() == 2 and t.stride(1) == 1 else t.contiguous() for t in (q, k, v))
+        csr, N, dev = graph.fwd, graph.fwd.N, q.device
+        if any(t.size(0) != N or t.size(1) != H * C for t in (q, k, v)):
+            raise RuntimeError(f"transformer_attend: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} for a "
+                               f"graph of {N} nodes and {H} x {C} channels")
+        seed = None
+        if train and p_drop > 0.0:
+            # two 32-bit words from torch's device generator, as _GATv2Attend draws them; they stay on the device
+            seed = torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32, device=dev)
+        if record is not None:
+            record.update(seed=seed, p_drop=float(p_drop))
+        out = torch.empty((N, H * C), dtype=torch.float32, device=dev)
+        # m / rden are the backward's; without one the kernel runs its inference form
+        m = torch.empty((N, H), dtype=torch.float32, device=dev) if want_grad or seed is not None else None
+        rden = None if m is None else torch.empty_like(m)
+        pq, ldq = _lib.mat(q, "q")
+        pk, ldk = _lib.mat(k, "k")
+        pv, ldv = _lib.mat(v, "v")
+        po, ldo = _lib.mat(out, "out")
+        split_ref, _, _scratch = _gatv2_split(csr, H * C + 2 * H, dev)
+        with _Timed("transformer_fwd"):
+            _lib.check(lib.rgbx_transformer_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pq, ldq, pk, ldk, pv, ldv,
+                                                    po, ldo, _lib.ptr(m), _lib.ptr(rden), N, H, C, float(scale),
+                                                    _lib.ptr(seed), float(p_drop), split_ref, _lib.stream_ptr()),
+                       "rgbx_transformer_fwd_f32")
+        ctx.graph, ctx.H, ctx.C, ctx.scale, ctx.p_drop = graph, H, C, float(scale), float(p_drop)
+        ctx.save_for_backward(q, k, v, m, rden, out, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, v, m, rden, out, seed = ctx.saved_tensors
+        g, H, C, scale, p_drop = ctx.graph, ctx.H, ctx.C, ctx.scale, ctx.p_drop
+        lib = _lib.load()
+        N, dev = g.fwd.N, q.device
+        F = H * C
+        gout = gout.contiguous()
+        # every row of the four buffers is written by the kernels (rows without slots as zeros)
+        nodeq = torch.empty((N, H, 2), dtype=torch.float32, device=dev)
+        g_q = torch.empty((N, F), dtype=torch.float32, device=dev)
+        g_k = torch.empty_like(g_q)
+        g_v = torch.empty_like(g_q)
+        pq, ldq = _lib.mat(q, "q")
+        pk, ldk = _lib.mat(k, "k")
+        pv, ldv = _lib.mat(v, "v")
+        po, ldo = _lib.mat(out, "out")
+        pg, ldg = _lib.mat(gout, "gout")
+        pgq, ldgq = _lib.mat(g_q, "g_q")
+        pgk, ldgk = _lib.mat(g_k, "g_k")
+        pgv, ldgv = _lib.mat(g_v, "g_v")
+        split_ref, _, _scratch = _gatv2_split(g.fwd, F, dev)
+        with _Timed("transformer_bwd_dst"):
+            _lib.check(
+                lib.rgbx_transformer_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pq, ldq, pk, ldk, pv, ldv,
+                                                 _lib.ptr(m), _lib.ptr(rden), po, ldo, pg, ldg, _lib.ptr(nodeq), pgq,
+                                                 ldgq, N, H, C, scale, _lib.ptr(seed), p_drop, split_ref,
+                                                 _lib.stream_ptr()), "rgbx_transformer_bwd_dst_f32")
+        split_ref, _, _scratch2 = _gatv2_split(g.bwd, 2 * F, dev)
+        with _Timed("transformer_bwd_src"):
+            _lib.check(
+                lib.rgbx_transformer_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
+                                                 _lib.ptr(g.t2f) if seed is not None else None, pq, ldq, pk, ldk, pv,
+                                                 ldv, _lib.ptr(nodeq), pg, ldg, pgk, ldgk, pgv, ldgv, N, H, C, scale,
+                                                 _lib.ptr(seed), p_drop, split_ref, _lib.stream_ptr()),
+                "rgbx_transformer_bwd_src_f32")
+        need = ctx.needs_input_grad
+        return (g_q if need[0] else None, g_k if need[1] else None, g_v if need[2] else None, None, None, None, None,
+                None, None, None, None)
+
+
+def transformer_supported(H, C):
+    return bool(_lib.load().rgbx_transformer_supported(H, C))
+
+
+def transformer_attend(q, k, v, graph, H, C, scale, training=False, p_drop=0.0, record=None):
+    """One TransformerConv attention block on q, k, v [N, H*C] (rows contiguous; column blocks of one wider matrix are
+    taken as they are): out_i = sum_j softmax_i(<q_i, k_j> * scale) v_j per head over the in-edges of i, the graph in
+    mode LOOPS_KEEP (edges as given; a node without in-edges gets zeros). `scale` is 1 / sqrt(C) of the TRUE head
+    width (the caller may have zero-padded the heads). In training mode with p_drop > 0 the coefficients are dropped
+    after the softmax with a seed from torch's device generator; `record` (a dict) receives it, for
+    transformer_random_choices."""
+    if _is_dist(graph):
+        raise RuntimeError("TransformerConv has no node-partitioned form: run it on one GPU")
+    _lib.require_device(q, k, v)
+    if not (0.0 <= p_drop < 1.0):
+        raise ValueError("transformer_attend: dropout must be in [0, 1)")
+    if not transformer_supported(H, C):
+        raise RuntimeError(f"transformer_attend: {H} heads of {C} channels; pad the head width (TransformerConv does)")
+    want_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
+    return _TransformerAttend.apply(q, k, v, graph, H, C, float(scale), bool(training), float(p_drop), record,
+                                    want_grad)
+
+
 FACONV_FORMS = ("fused", "composed")
 
 
