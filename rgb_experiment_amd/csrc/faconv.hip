@@ -16,61 +16,21 @@
 //
 // Dropout is counter-based (rgbx_rng.h): the keep of a slot is a hash of (seed, FORWARD slot id); the source-side
 // pass finds that id in t2f. Lane layout, row-split plan and reproducibility are those of spmm.hip / supergat.hip.
-#include "rgbx_common.h"
-#include "rgbx_rng.h"
+#include "attn_common.h"
 
 namespace rgbx {
 namespace {
 
 constexpr uint32_t kStreamFaDrop = 0xA4093822u;
 
-struct FaSplit {
-  int threshold;
-  const int* chunk_row;
-  const int* chunk_begin;
-  const int* chunk_end;
-  float* pacc;  // [n_chunks, C]
-  float* p0;    // [n_chunks]  (backward only)
-};
-
-struct FaRng {
-  const uint32_t* seed;  // two 32-bit words on the device
-  float p_drop;
-  float inv_keep;
-};
-
-__device__ __forceinline__ float fa_keep(uint32_t s0, uint32_t s1, int slot, const FaRng& rng) {
+// AttnSplit here: pacc [n_chunks, C], p0 [n_chunks] (backward only). AttnRng, row_item, dot_vec: attn_common.h
+__device__ __forceinline__ float fa_keep(uint32_t s0, uint32_t s1, int slot, const AttnRng& rng) {
   return unit24(draw32(s0, s1, kStreamFaDrop, (uint32_t)slot, 0u)) >= rng.p_drop ? rng.inv_keep : 0.f;
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
-}
-
-template <int VEC>
-__device__ __forceinline__ float dot_vec(const float (&a)[VEC], const float (&b)[VEC]) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) s = fmaf(a[i], b[i], s);
-  return s;
-}
-
-// The row (or hub-row chunk) a wave owns. false: the main kernel leaves this row to the chunk + combine kernels.
-template <bool CHUNK>
-__device__ __forceinline__ bool fa_item(const int* __restrict__ rowptr, const FaSplit& sp, int item, int* row,
-                                        int* start, int* end) {
-  if constexpr (CHUNK) {
-    *row = __builtin_amdgcn_readfirstlane(sp.chunk_row[item]);
-    *start = __builtin_amdgcn_readfirstlane(sp.chunk_begin[item]);
-    *end = __builtin_amdgcn_readfirstlane(sp.chunk_end[item]);
-    return true;
-  } else {
-    *row = item;
-    *start = __builtin_amdgcn_readfirstlane(rowptr[item]);
-    *end = __builtin_amdgcn_readfirstlane(rowptr[item + 1]);
-    return !(sp.threshold > 0 && *end - *start > sp.threshold);
-  }
 }
 
 // alr[r] = (<x_r, att_l>, <x_r, att_r>): a group of G = 2^lg lanes per row, any C.
@@ -110,7 +70,7 @@ __global__ void __launch_bounds__(256)
 fa_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ w,
               const float* __restrict__ x, int64_t ldx, const float2* __restrict__ alr, const float* __restrict__ x0,
               int64_t ldx0, float eps, float* __restrict__ out, int64_t ldo, int n_items, int C, int lg,
-              const FaSplit sp, const FaRng rng) {
+              const AttnSplit sp, const AttnRng rng) {
   constexpr int U = 4;  // neighbour rows in flight per lane group
   const int lane = threadIdx.x & 63;
   const int G = 1 << lg, NG = kWave >> lg;
@@ -125,7 +85,7 @@ fa_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, const
   }
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < n_items; item += gridDim.x * wpb) {
     int row, start, end;
-    if (!fa_item<CHUNK>(rowptr, sp, item, &row, &start, &end)) continue;
+    if (!row_item<CHUNK>(rowptr, sp, item, row, start, end)) continue;
     const float ar = alr[row].y;
     float acc[VEC];
 #pragma unroll
@@ -190,7 +150,7 @@ __global__ void __launch_bounds__(256)
 fa_combine_kernel(int n_long, const int* __restrict__ long_row, const int* __restrict__ long_chunk_ptr,
                   const float* __restrict__ x0, int64_t ldx0, float eps, const float* __restrict__ att_l,
                   const float* __restrict__ att_r, float* __restrict__ g_alr, float* __restrict__ out, int64_t ldo,
-                  int C, const FaSplit sp) {
+                  int C, const AttnSplit sp) {
   const int lane = threadIdx.x & 63;
   const int wpb = blockDim.x >> 6;
   for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < n_long; r += gridDim.x * wpb) {
@@ -239,7 +199,7 @@ __global__ void __launch_bounds__(256)
 fa_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ w,
                   const float* __restrict__ x, int64_t ldx, const float2* __restrict__ alr,
                   const float* __restrict__ gout, int64_t ldg, float* __restrict__ g_alr, int n_items, int C, int lg,
-                  const FaSplit sp, const FaRng rng) {
+                  const AttnSplit sp, const AttnRng rng) {
   constexpr int U = 4;
   const int lane = threadIdx.x & 63;
   const int G = 1 << lg, NG = kWave >> lg;
@@ -254,7 +214,7 @@ fa_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, c
   }
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < n_items; item += gridDim.x * wpb) {
     int row, start, end;
-    if (!fa_item<CHUNK>(rowptr, sp, item, &row, &start, &end)) continue;
+    if (!row_item<CHUNK>(rowptr, sp, item, row, start, end)) continue;
     const float ar = alr[row].y;
     float go[VEC];
 #pragma unroll
@@ -307,8 +267,8 @@ fa_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ col_
                   const int* __restrict__ t2f, const float* __restrict__ x, int64_t ldx,
                   const float2* __restrict__ alr, const float* __restrict__ gout, int64_t ldg,
                   const float* __restrict__ att_l, const float* __restrict__ att_r, float* __restrict__ g_alr,
-                  float* __restrict__ g_x, int64_t ldgx, int n_items, int C, int lg, const FaSplit sp,
-                  const FaRng rng) {
+                  float* __restrict__ g_x, int64_t ldgx, int n_items, int C, int lg, const AttnSplit sp,
+                  const AttnRng rng) {
   constexpr int U = 4;
   const int lane = threadIdx.x & 63;
   const int G = 1 << lg, NG = kWave >> lg;
@@ -323,7 +283,7 @@ fa_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ col_
   }
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < n_items; item += gridDim.x * wpb) {
     int row, start, end;
-    if (!fa_item<CHUNK>(rowptr_t, sp, item, &row, &start, &end)) continue;
+    if (!row_item<CHUNK>(rowptr_t, sp, item, row, start, end)) continue;
     const float al = alr[row].x;
     float xj[VEC], acc[VEC];
 #pragma unroll
@@ -396,7 +356,7 @@ template <bool TRAIN>
 __global__ void __launch_bounds__(256)
 fa_edge_coef_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ w,
                     const int* __restrict__ slot, const float2* __restrict__ alr, int transposed, int N,
-                    const FaRng rng, float* __restrict__ coef, float* __restrict__ q) {
+                    const AttnRng rng, float* __restrict__ coef, float* __restrict__ q) {
   const int lane = threadIdx.x & 63;
   const int wpb = blockDim.x >> 6;
   uint32_t s0 = 0, s1 = 0;
@@ -441,7 +401,7 @@ fa_edge_dot_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, 
 
 // The dropout decisions of a training forward, written out for inspection (tests): keep[p] in forward CSR slot order.
 __global__ void __launch_bounds__(256)
-fa_draws_kernel(const uint32_t* __restrict__ seed, int64_t nnz, const FaRng rng, uint8_t* __restrict__ keep) {
+fa_draws_kernel(const uint32_t* __restrict__ seed, int64_t nnz, const AttnRng rng, uint8_t* __restrict__ keep) {
   const uint32_t s0 = seed[0], s1 = seed[1];
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += (int64_t)gridDim.x * blockDim.x)
     keep[p] = fa_keep(s0, s1, (int)p, rng) != 0.f ? 1 : 0;
@@ -456,8 +416,6 @@ int fa_lg(int64_t C, int vec) {  // log2 of the lanes per row, capped at a whole
   while ((1 << lg) * vec < C && lg < 6) ++lg;
   return lg;
 }
-
-int fa_grid(int64_t items) { return (int)std::max<int64_t>(1, cdiv(items, 4)); }  // one row per wave, uncapped
 
 int fa_check(int64_t N, int64_t C, bool fused, const char* name) {
   if (N < 0 || C <= 0) return fail(RGBX_E_ARG, "%s: bad size", name);
@@ -482,59 +440,17 @@ int fa_aligned(int64_t C, std::initializer_list<const void*> ptrs, std::initiali
   return RGBX_OK;
 }
 
-int fa_split_view(const rgbx_row_split_t* split, int64_t C, FaSplit* sd, const char* name) {
-  *sd = FaSplit{0, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (!split || split->threshold <= 0 || split->n_chunks <= 0) return RGBX_OK;
-  if (split->n_long <= 0 || !split->chunk_row || !split->chunk_begin || !split->chunk_end || !split->long_row ||
-      !split->long_chunk_ptr || !split->partial)
-    return fail(RGBX_E_ARG, "%s: incomplete row-split plan", name);
-  if (reinterpret_cast<uintptr_t>(split->partial) % 16)
+// pacc [n_chunks, C] and one scalar per chunk; the fragments are read vec floats at a time.
+int fa_split_view(const rgbx_row_split_t* split, int64_t C, AttnSplit* sd, const char* name) {
+  if (int rc = split_view(split, 1, (int)C, 1, sd, name)) return rc;
+  if (sd->threshold > 0 && reinterpret_cast<uintptr_t>(split->partial) % 16)
     return fail(RGBX_E_ALIGN, "%s: split->partial must be 16-byte aligned", name);
-  sd->threshold = split->threshold;
-  sd->chunk_row = split->chunk_row;
-  sd->chunk_begin = split->chunk_begin;
-  sd->chunk_end = split->chunk_end;
-  sd->pacc = split->partial;                         // [n_chunks, C]
-  sd->p0 = sd->pacc + (int64_t)split->n_chunks * C;  // [n_chunks]
   return RGBX_OK;
 }
 
-int fa_rng(const uint32_t* seed, float p_drop, FaRng* rng, const char* name) {
-  *rng = FaRng{seed, p_drop, 1.0f};
-  if (!seed) return RGBX_OK;
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(RGBX_E_ARG, "%s: dropout must be in [0, 1)", name);
-  rng->inv_keep = 1.0f / (1.0f - p_drop);
-  return RGBX_OK;
-}
-
-// KERNEL<VEC, CHUNK, TRAIN> over the rows, then (with a split plan) over the hub-row chunks.
-#define RGBX_FA_ROWS(KERNEL, V, T, n_rows, ...)                                                        \
-  do {                                                                                                 \
-    KERNEL<V, false, T><<<fa_grid(n_rows), 256, 0, s>>>(__VA_ARGS__, (int)(n_rows), (int)C, lg, sd, rng); \
-    if (sd.threshold > 0)                                                                              \
-      KERNEL<V, true, T><<<fa_grid(split->n_chunks), 256, 0, s>>>(__VA_ARGS__, split->n_chunks, (int)C, lg, sd, rng); \
-  } while (0)
-
-#define RGBX_FA_DISPATCH(KERNEL, n_rows, ...)                              \
-  do {                                                                     \
-    if (rng.seed) {                                                        \
-      if (vec == 4) RGBX_FA_ROWS(KERNEL, 4, true, n_rows, __VA_ARGS__);    \
-      else if (vec == 2) RGBX_FA_ROWS(KERNEL, 2, true, n_rows, __VA_ARGS__); \
-      else RGBX_FA_ROWS(KERNEL, 1, true, n_rows, __VA_ARGS__);             \
-    } else {                                                               \
-      if (vec == 4) RGBX_FA_ROWS(KERNEL, 4, false, n_rows, __VA_ARGS__);   \
-      else if (vec == 2) RGBX_FA_ROWS(KERNEL, 2, false, n_rows, __VA_ARGS__); \
-      else RGBX_FA_ROWS(KERNEL, 1, false, n_rows, __VA_ARGS__);            \
-    }                                                                      \
-  } while (0)
-
-#define RGBX_FA_COMBINE(MODE, ...)                                                                              \
-  do {                                                                                                          \
-    const int gc = fa_grid(split->n_long);                                                                      \
-    if (vec == 4) fa_combine_kernel<4, MODE><<<gc, 256, 0, s>>>(split->n_long, split->long_row, split->long_chunk_ptr, __VA_ARGS__, (int)C, sd); \
-    else if (vec == 2) fa_combine_kernel<2, MODE><<<gc, 256, 0, s>>>(split->n_long, split->long_row, split->long_chunk_ptr, __VA_ARGS__, (int)C, sd); \
-    else fa_combine_kernel<1, MODE><<<gc, 256, 0, s>>>(split->n_long, split->long_row, split->long_chunk_ptr, __VA_ARGS__, (int)C, sd); \
-  } while (0)
+#define RGBX_FA_COMBINE(MODE, ...)                                                                        \
+  RGBX_VEC_SWITCH(vec, fa_combine_kernel<V, MODE><<<row_grid(split->n_long), 256, 0, s>>>(                \
+                           split->n_long, split->long_row, split->long_chunk_ptr, __VA_ARGS__, (int)C, sd))
 
 }  // namespace
 }  // namespace rgbx
@@ -542,7 +458,7 @@ int fa_rng(const uint32_t* seed, float p_drop, FaRng* rng, const char* name) {
 using namespace rgbx;
 
 extern "C" int rgbx_faconv_supported(int64_t C) {
-  return C > 0 && (C <= 64 || (C % 2 == 0 && C <= 128) || (C % 4 == 0 && C <= 256));
+  return head_width_supported(C);
 }
 
 extern "C" int rgbx_faconv_scores_f32(const float* x, int64_t ldx, const float* att_l, const float* att_r, float* alr,
@@ -553,12 +469,10 @@ extern "C" int rgbx_faconv_scores_f32(const float* x, int64_t ldx, const float* 
   if (int rc = fa_aligned(C, {x, att_l, att_r}, {ldx}, "faconv_scores")) return rc;
   if (reinterpret_cast<uintptr_t>(alr) % 8) return fail(RGBX_E_ALIGN, "faconv_scores: alr must be 8-byte aligned");
   const int vec = fa_vec(C), lg = fa_lg(C, vec);
-  const int grid = (int)std::min<int64_t>(kMaxGrid, std::max<int64_t>(1, cdiv(N, 4 * (kWave >> lg))));
+  const int grid = capped_grid(N, 4 * (kWave >> lg));
   hipStream_t s = (hipStream_t)stream;
   float2* o = reinterpret_cast<float2*>(alr);
-  if (vec == 4) fa_scores_kernel<4><<<grid, 256, 0, s>>>(x, ldx, att_l, att_r, o, (int)N, (int)C, lg);
-  else if (vec == 2) fa_scores_kernel<2><<<grid, 256, 0, s>>>(x, ldx, att_l, att_r, o, (int)N, (int)C, lg);
-  else fa_scores_kernel<1><<<grid, 256, 0, s>>>(x, ldx, att_l, att_r, o, (int)N, (int)C, lg);
+  RGBX_VEC_SWITCH(vec, fa_scores_kernel<V><<<grid, 256, 0, s>>>(x, ldx, att_l, att_r, o, (int)N, (int)C, lg));
   RGBX_CHECK_LAUNCH("fa_scores_kernel");
   return RGBX_OK;
 }
@@ -576,14 +490,15 @@ extern "C" int rgbx_faconv_fwd_f32(const int32_t* rowptr, const int32_t* col, co
     if (int rc = fa_aligned(C, {x0}, {ldx0}, "faconv_fwd")) return rc;
   }
   if (reinterpret_cast<uintptr_t>(alr) % 8) return fail(RGBX_E_ALIGN, "faconv_fwd: alr must be 8-byte aligned");
-  FaSplit sd;
+  AttnSplit sd;
   if (int rc = fa_split_view(split, C, &sd, "faconv_fwd")) return rc;
-  FaRng rng;
-  if (int rc = fa_rng(seed, p_drop, &rng, "faconv_fwd")) return rc;
+  AttnRng rng;
+  if (int rc = make_rng(seed, p_drop, &rng, "faconv_fwd")) return rc;
   const int vec = fa_vec(C), lg = fa_lg(C, vec);
   hipStream_t s = (hipStream_t)stream;
   const float2* a2 = reinterpret_cast<const float2*>(alr);
-  RGBX_FA_DISPATCH(fa_fwd_kernel, N, rowptr, col, w, x, ldx, a2, x0, ldx0, eps, out, ldo);
+  RGBX_ATTN_DISPATCH(fa_fwd_kernel, row_grid, N, rowptr, col, w, x, ldx, a2, x0, ldx0, eps, out, ldo, n_items, (int)C,
+                     lg, sd, rng);
   if (sd.threshold > 0) RGBX_FA_COMBINE(0, x0, ldx0, eps, nullptr, nullptr, nullptr, out, ldo);
   RGBX_CHECK_LAUNCH("fa_fwd_kernel");
   return RGBX_OK;
@@ -598,14 +513,15 @@ extern "C" int rgbx_faconv_bwd_dst_f32(const int32_t* rowptr, const int32_t* col
   if (!rowptr || !col || !w || !x || !alr || !gout || !g_alr) return fail(RGBX_E_ARG, "faconv_bwd_dst: null pointer");
   if (int rc = fa_aligned(C, {x, gout}, {ldx, ldg}, "faconv_bwd_dst")) return rc;
   if (reinterpret_cast<uintptr_t>(alr) % 8) return fail(RGBX_E_ALIGN, "faconv_bwd_dst: alr must be 8-byte aligned");
-  FaSplit sd;
+  AttnSplit sd;
   if (int rc = fa_split_view(split, C, &sd, "faconv_bwd_dst")) return rc;
-  FaRng rng;
-  if (int rc = fa_rng(seed, p_drop, &rng, "faconv_bwd_dst")) return rc;
+  AttnRng rng;
+  if (int rc = make_rng(seed, p_drop, &rng, "faconv_bwd_dst")) return rc;
   const int vec = fa_vec(C), lg = fa_lg(C, vec);
   hipStream_t s = (hipStream_t)stream;
   const float2* a2 = reinterpret_cast<const float2*>(alr);
-  RGBX_FA_DISPATCH(fa_bwd_dst_kernel, N, rowptr, col, w, x, ldx, a2, gout, ldg, g_alr);
+  RGBX_ATTN_DISPATCH(fa_bwd_dst_kernel, row_grid, N, rowptr, col, w, x, ldx, a2, gout, ldg, g_alr, n_items, (int)C, lg,
+                     sd, rng);
   if (sd.threshold > 0) RGBX_FA_COMBINE(1, nullptr, 0, 0.f, nullptr, nullptr, g_alr, nullptr, 0);
   RGBX_CHECK_LAUNCH("fa_bwd_dst_kernel");
   return RGBX_OK;
@@ -625,14 +541,15 @@ extern "C" int rgbx_faconv_bwd_src_f32(const int32_t* rowptr_t, const int32_t* c
   if (g_x == gout || g_x == x) return fail(RGBX_E_ARG, "faconv_bwd_src: g_x must not alias gout or x");
   if (int rc = fa_aligned(C, {x, gout, g_x, att_l, att_r}, {ldx, ldg, ldgx}, "faconv_bwd_src")) return rc;
   if (reinterpret_cast<uintptr_t>(alr) % 8) return fail(RGBX_E_ALIGN, "faconv_bwd_src: alr must be 8-byte aligned");
-  FaSplit sd;
+  AttnSplit sd;
   if (int rc = fa_split_view(split, C, &sd, "faconv_bwd_src")) return rc;
-  FaRng rng;
-  if (int rc = fa_rng(seed, p_drop, &rng, "faconv_bwd_src")) return rc;
+  AttnRng rng;
+  if (int rc = make_rng(seed, p_drop, &rng, "faconv_bwd_src")) return rc;
   const int vec = fa_vec(C), lg = fa_lg(C, vec);
   hipStream_t s = (hipStream_t)stream;
   const float2* a2 = reinterpret_cast<const float2*>(alr);
-  RGBX_FA_DISPATCH(fa_bwd_src_kernel, N, rowptr_t, col_t, w_t, t2f, x, ldx, a2, gout, ldg, att_l, att_r, g_alr, g_x, ldgx);
+  RGBX_ATTN_DISPATCH(fa_bwd_src_kernel, row_grid, N, rowptr_t, col_t, w_t, t2f, x, ldx, a2, gout, ldg, att_l, att_r,
+                     g_alr, g_x, ldgx, n_items, (int)C, lg, sd, rng);
   if (sd.threshold > 0) RGBX_FA_COMBINE(2, nullptr, 0, 0.f, att_l, att_r, g_alr, g_x, ldgx);
   RGBX_CHECK_LAUNCH("fa_bwd_src_kernel");
   return RGBX_OK;
@@ -646,12 +563,13 @@ extern "C" int rgbx_faconv_edge_coef_f32(const int32_t* rowptr, const int32_t* c
   if (N == 0) return RGBX_OK;
   if (!rowptr || !col || !w || !alr || !coef) return fail(RGBX_E_ARG, "faconv_edge_coef: null pointer");
   if (reinterpret_cast<uintptr_t>(alr) % 8) return fail(RGBX_E_ALIGN, "faconv_edge_coef: alr must be 8-byte aligned");
-  FaRng rng;
-  if (int rc = fa_rng(seed, p_drop, &rng, "faconv_edge_coef")) return rc;
+  AttnRng rng;
+  if (int rc = make_rng(seed, p_drop, &rng, "faconv_edge_coef")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const float2* a2 = reinterpret_cast<const float2*>(alr);
-  if (seed) fa_edge_coef_kernel<true><<<fa_grid(N), 256, 0, s>>>(rowptr, col, w, slot, a2, transposed, (int)N, rng, coef, q);
-  else fa_edge_coef_kernel<false><<<fa_grid(N), 256, 0, s>>>(rowptr, col, w, slot, a2, transposed, (int)N, rng, coef, q);
+  const int grid = row_grid(N);
+  if (seed) fa_edge_coef_kernel<true><<<grid, 256, 0, s>>>(rowptr, col, w, slot, a2, transposed, (int)N, rng, coef, q);
+  else fa_edge_coef_kernel<false><<<grid, 256, 0, s>>>(rowptr, col, w, slot, a2, transposed, (int)N, rng, coef, q);
   RGBX_CHECK_LAUNCH("fa_edge_coef_kernel");
   return RGBX_OK;
 }
@@ -664,7 +582,7 @@ extern "C" int rgbx_faconv_edge_dot_f32(const int32_t* rowptr, const int32_t* co
   if (!rowptr || !col || !q || !a || !b || !out) return fail(RGBX_E_ARG, "faconv_edge_dot: null pointer");
   if (out_stride < 1) return fail(RGBX_E_ARG, "faconv_edge_dot: output stride < 1");
   if (int rc = fa_aligned(C, {a, b}, {lda, ldb}, "faconv_edge_dot")) return rc;
-  fa_edge_dot_kernel<<<fa_grid(N), 256, 0, (hipStream_t)stream>>>(rowptr, col, q, a, lda, b, ldb, out, out_stride,
+  fa_edge_dot_kernel<<<row_grid(N), 256, 0, (hipStream_t)stream>>>(rowptr, col, q, a, lda, b, ldb, out, out_stride,
                                                                   (int)N, (int)C);
   RGBX_CHECK_LAUNCH("fa_edge_dot_kernel");
   return RGBX_OK;
@@ -676,9 +594,9 @@ extern "C" int rgbx_faconv_draws_u8(const uint32_t* seed, int64_t nnz, float p_d
   if (nnz == 0) return RGBX_OK;
   if (nnz >= INT32_MAX) return fail(RGBX_E_RANGE, "faconv_draws: E' exceeds int32");
   if (!seed || !keep) return fail(RGBX_E_ARG, "faconv_draws: null pointer");
-  FaRng rng;
-  if (int rc = fa_rng(seed, p_drop, &rng, "faconv_draws")) return rc;
-  const int grid = (int)std::min<int64_t>(kMaxGrid, cdiv(nnz, 256));
+  AttnRng rng;
+  if (int rc = make_rng(seed, p_drop, &rng, "faconv_draws")) return rc;
+  const int grid = capped_grid(nnz, 256);
   fa_draws_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(seed, nnz, rng, keep);
   RGBX_CHECK_LAUNCH("fa_draws_kernel");
   return RGBX_OK;

@@ -11,119 +11,10 @@
 // The attention dropout keep of (forward CSR slot, head) is a hash of a 64-bit seed that lives on the device; the
 // backward recomputes it and every score. No [E', H] tensor is ever written, there are no float atomics, and every sum
 // runs in a fixed order.
-#include "rgbx_common.h"
-#include "rgbx_rng.h"
+#include "attn_common.h"
 
 namespace rgbx {
 namespace {
-
-// Lane layout and host helpers: the same as gat.hip's and supergat.hip's (a head occupies LPH = pow2ceil(C / VEC)
-// consecutive lanes of VEC channels, HPC heads side by side in a group of G lanes that reads one neighbour row per
-// step, NG = 64 / G rows per wave-instruction). Copied rather than shared: the text of gat.hip and supergat.hip keys
-// the recorded counter measurements of their kernels (bench.py KERNEL_SOURCES), which an edit would invalidate.
-struct GatLayout {
-  int H, C;
-  int LPH;  // lanes per head (power of two)
-  int HPC;  // heads per chunk
-  int G;    // lanes per neighbour row (power of two, >= HPC * LPH)
-};
-
-constexpr float kNegBig = -1.0e30f;
-
-template <int VEC>
-__device__ __forceinline__ float dot_vec(const float (&a)[VEC], const float (&b)[VEC]) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) s = fmaf(a[i], b[i], s);
-  return s;
-}
-
-// Sum over the LPH lanes of a head; every lane of the head ends with the total.
-__device__ __forceinline__ float head_sum(float v, int LPH) {
-  for (int off = LPH >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-int pow2ceil(int x) {
-  int p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
-// VEC must divide C so that a lane's channels stay inside one head.
-int pick_vec(int C, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> lds) {
-  for (int v : {4, 2}) {
-    bool ok = C % v == 0;
-    for (const void* p : ptrs) ok = ok && (reinterpret_cast<uintptr_t>(p) % (v * 4) == 0);
-    for (int64_t ld : lds) ok = ok && (ld % v == 0);
-    if (ok) return v;
-  }
-  return 1;
-}
-
-int make_layout(int H, int C, int vec, GatLayout* L, const char* name) {
-  const int lph = pow2ceil((C + vec - 1) / vec);
-  if (lph > kWave)
-    return fail(RGBX_E_SHAPE, "%s: C=%d needs %d lanes per head (> 64) at vector width %d", name, C, lph, vec);
-  L->H = H;
-  L->C = C;
-  L->LPH = lph;
-  L->HPC = std::min(H, kWave / lph);
-  L->G = pow2ceil(L->HPC * lph);
-  return RGBX_OK;
-}
-
-int gat_grid(int64_t N) {  // one row per wave, no cap (see spmm.hip: uncapped grids balance ragged rows better)
-  return (int)cdiv(N, 4);
-}
-
-// The target-side backward leaves one g_att record per workgroup, so its grid is capped and the waves stride over the
-// rows.
-int att_grid(int64_t N) {
-  const int64_t b = cdiv(N, 4);
-  return (int)(b < 1 ? 1 : (b < kMaxGrid ? b : kMaxGrid));
-}
-
-int flat_grid(int64_t n, int per_block) {
-  const int64_t b = cdiv(n, per_block);
-  return (int)(b < 1 ? 1 : (b < kMaxGrid ? b : kMaxGrid));
-}
-
-int check_common(int64_t N, int H, int C, const char* name) {
-  if (N < 0 || H <= 0 || C <= 0) return fail(RGBX_E_ARG, "%s: bad size", name);
-  if (N >= INT32_MAX || (int64_t)H * C >= INT32_MAX) return fail(RGBX_E_RANGE, "%s: size exceeds int32", name);
-  return RGBX_OK;
-}
-
-bool aligned_to(std::initializer_list<const void*> ptrs, unsigned bytes) {
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) % bytes) return false;
-  return true;
-}
-
-struct V2Split {
-  int threshold;
-  const int* chunk_row;
-  const int* chunk_begin;
-  const int* chunk_end;
-  float* pacc;  // [n_chunks, F]
-  float* p0;    // [n_chunks, H]  (forward only: running max)
-  float* p1;    // [n_chunks, H]  (forward only: denominator)
-};
-
-// Training-mode state of one forward: `seed` = two 32-bit words on the device (NULL: no dropout).
-struct V2Rng {
-  const uint32_t* seed;
-  float p_drop;
-  float inv_keep;  // 1 / (1 - p_drop)
-};
-
-constexpr uint32_t kStreamDrop = 0xA4093822u;
-
-// mix32 / draw32 / unit24: rgbx_rng.h (shared with supergat.hip and faconv.hip)
-__device__ __forceinline__ bool drop_keep(uint32_t s0, uint32_t s1, int slot, int head, float p) {
-  return unit24(draw32(s0, s1, kStreamDrop, (uint32_t)slot, (uint32_t)head)) >= p;
-}
 
 // This lane's share of the score: sum_v att_v lrelu(xl_v + xr_v); lr receives lrelu(s), s the pre-activation.
 template <int VEC>
@@ -139,8 +30,6 @@ __device__ __forceinline__ float score_part(const float (&xl)[VEC], const float 
   return e;
 }
 
-__device__ __forceinline__ float softmax_shift(float m, float rden) { return rden > 0.f ? m - logf(rden) : 0.f; }
-
 // ------------------------------------------------------------------------------------------
 // Forward: online softmax (running max, denominator, rescaled accumulator) over the slots of a row, read once.
 // TRAIN: attention dropout in the accumulation (the normaliser stays that of the undropped softmax).
@@ -149,17 +38,10 @@ __global__ void __launch_bounds__(256)
 gatv2_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ xl, int64_t ldl,
                  const float* __restrict__ xr, int64_t ldr, const float* __restrict__ att,
                  const float* __restrict__ bias, float* __restrict__ out, int64_t ldo, float* __restrict__ m_out,
-                 float* __restrict__ rden_out, int N, float slope, const GatLayout L, const V2Split sp,
-                 const V2Rng rng) {
+                 float* __restrict__ rden_out, int N, float slope, const GatLayout L, const AttnSplit sp,
+                 const AttnRng rng) {
   constexpr int U = 4;  // neighbour rows in flight per lane group
-  const int lane = threadIdx.x & 63;
-  const int NG = kWave / L.G;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
+  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
   uint32_t s0 = 0, s1 = 0;
   if constexpr (TRAIN) {
     s0 = rng.seed[0];
@@ -168,16 +50,7 @@ gatv2_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, co
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
     int row, start, end;
-    if constexpr (CHUNK) {
-      row = __builtin_amdgcn_readfirstlane(sp.chunk_row[item]);
-      start = __builtin_amdgcn_readfirstlane(sp.chunk_begin[item]);
-      end = __builtin_amdgcn_readfirstlane(sp.chunk_end[item]);
-    } else {
-      row = item;
-      start = __builtin_amdgcn_readfirstlane(rowptr[row]);
-      end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-      if (sp.threshold > 0 && end - start > sp.threshold) continue;  // the chunk + combine kernels own it
-    }
+    if (!row_item<CHUNK>(rowptr, sp, item, row, start, end)) continue;
     for (int hbase = 0; hbase < L.H; hbase += L.HPC) {
       const int head = hbase + hl;
       const bool active = hl < L.HPC && head < L.H && ch < L.C;
@@ -216,27 +89,14 @@ gatv2_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, co
             l = fmaf(l, sc, p);
             float pk = p;
             if constexpr (TRAIN)
-              pk = drop_keep(s0, s1, base + k + u * NG + g, head, rng.p_drop) ? p * rng.inv_keep : 0.f;
+              pk = drop_keep<kStreamAttnDrop>(s0, s1, base + k + u * NG + g, head, rng.p_drop) ? p * rng.inv_keep : 0.f;
 #pragma unroll
             for (int i = 0; i < VEC; ++i) acc[i] = fmaf(acc[i], sc, pk * v[u][i]);
             m = mn;
           }
         }
       }
-      // merge the NG online-softmax states
-      for (int off = 32; off >= L.G; off >>= 1) {
-        const float m2 = __shfl_xor(m, off);
-        const float l2 = __shfl_xor(l, off);
-        const float mn = fmaxf(m, m2);
-        const float s1m = expf(m - mn), s2m = expf(m2 - mn);
-        l = l * s1m + l2 * s2m;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-          const float a2 = __shfl_xor(acc[i], off);
-          acc[i] = acc[i] * s1m + a2 * s2m;
-        }
-        m = mn;
-      }
+      softmax_merge_groups<VEC>(m, l, acc, L.G);
       if (g == 0 && active) {
         if constexpr (CHUNK) {  // un-normalised online-softmax state of this chunk
           store_vec<VEC>(sp.pacc + (int64_t)item * F + cofs, acc);
@@ -263,59 +123,6 @@ gatv2_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, co
   }
 }
 
-// One wave per hub row: merge the chunk states in chunk order, normalise, store.
-template <int VEC>
-__global__ void __launch_bounds__(256)
-gatv2_fwd_combine_kernel(int n_long, const int* __restrict__ long_row, const int* __restrict__ long_chunk_ptr,
-                         const float* __restrict__ bias, float* __restrict__ out, int64_t ldo,
-                         float* __restrict__ m_out, float* __restrict__ rden_out, const GatLayout L,
-                         const V2Split sp) {
-  const int lane = threadIdx.x & 63;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
-  for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < n_long; r += gridDim.x * wpb) {
-    const int row = long_row[r];
-    const int c0 = long_chunk_ptr[r], c1 = long_chunk_ptr[r + 1];
-    for (int hbase = 0; hbase < L.H; hbase += L.HPC) {
-      const int head = hbase + hl;
-      if (!(g == 0 && hl < L.HPC && head < L.H && ch < L.C)) continue;
-      const int cofs = head * L.C + ch;
-      float m = kNegBig, l = 0.f;
-      float acc[VEC];
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-      for (int c = c0; c < c1; ++c) {
-        const float m2 = sp.p0[(int64_t)c * L.H + head];
-        const float l2 = sp.p1[(int64_t)c * L.H + head];
-        float a2[VEC];
-        load_vec<VEC>(a2, sp.pacc + (int64_t)c * F + cofs);
-        const float mn = fmaxf(m, m2);
-        const float s1 = expf(m - mn), s2 = expf(m2 - mn);
-        l = l * s1 + l2 * s2;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = acc[i] * s1 + a2[i] * s2;
-        m = mn;
-      }
-      const float rd = l > 0.f ? 1.0f / (l + 1e-16f) : 0.f;
-      float bv[VEC];
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) bv[i] = 0.f;
-      if (bias) load_vec<VEC>(bv, bias + cofs);
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc[i] = acc[i] * rd + bv[i];
-      store_vec<VEC>(out + (int64_t)row * ldo + cofs, acc);
-      if (m_out && ch == 0) {
-        m_out[(int64_t)row * L.H + head] = l > 0.f ? m : 0.f;
-        rden_out[(int64_t)row * L.H + head] = rd;
-      }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // Backward. With kappa = keep / (1 - p) (1 without dropout), D_i = <gout_i, out_i - bias> per head:
 //   de = alpha (kappa <gout_i, xl_j> - D_i),  ds_c = de att_c lrelu'(s_c)
@@ -332,18 +139,11 @@ gatv2_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col
                      const float* __restrict__ m_in, const float* __restrict__ rden_in, const float* __restrict__ out,
                      int64_t ldo, const float* __restrict__ bias, const float* __restrict__ gout, int64_t ldg,
                      float2* __restrict__ nodeq, float* __restrict__ g_xr, int64_t ldgr, float* __restrict__ att_part,
-                     int N, float slope, const GatLayout L, const V2Split sp, const V2Rng rng) {
+                     int N, float slope, const GatLayout L, const AttnSplit sp, const AttnRng rng) {
   constexpr int U = 3;
   __shared__ float red[4][kWave * 4];
-  const int lane = threadIdx.x & 63;
+  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
   const int wave = threadIdx.x >> 6;
-  const int NG = kWave / L.G;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
   uint32_t s0 = 0, s1 = 0;
   if constexpr (TRAIN) {
     s0 = rng.seed[0];
@@ -361,17 +161,8 @@ gatv2_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col
 
     for (int item = blockIdx.x * wpb + wave; item < N; item += gridDim.x * wpb) {
       int row, start, end;
-      bool hub = false;
-      if constexpr (CHUNK) {
-        row = __builtin_amdgcn_readfirstlane(sp.chunk_row[item]);
-        start = __builtin_amdgcn_readfirstlane(sp.chunk_begin[item]);
-        end = __builtin_amdgcn_readfirstlane(sp.chunk_end[item]);
-      } else {
-        row = item;
-        start = __builtin_amdgcn_readfirstlane(rowptr[row]);
-        end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-        hub = sp.threshold > 0 && end - start > sp.threshold;  // record here, sums by the chunk + combine kernels
-      }
+      // a hub row: its record here, its sums by the chunk + combine kernels
+      const bool hub = !row_item<CHUNK>(rowptr, sp, item, row, start, end);
       float xri[VEC], go[VEC], acc[VEC];
       float shift = 0.f, dsum = 0.f;
       {
@@ -419,7 +210,7 @@ gatv2_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col
             const float dal = head_sum(dot_vec<VEC>(v[u], go), L.LPH);
             float kappa = 1.f;
             if constexpr (TRAIN)
-              kappa = drop_keep(s0, s1, base + k + u * NG + g, head, rng.p_drop) ? rng.inv_keep : 0.f;
+              kappa = drop_keep<kStreamAttnDrop>(s0, s1, base + k + u * NG + g, head, rng.p_drop) ? rng.inv_keep : 0.f;
             const float alpha = ok[u] ? expf(e - shift) : 0.f;
             const float de = alpha * (kappa * dal - dsum);
 #pragma unroll
@@ -430,10 +221,7 @@ gatv2_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col
           }
         }
       }
-      for (int off = 32; off >= L.G; off >>= 1) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] += __shfl_xor(acc[i], off);
-      }
+      groups_sum<VEC>(acc, L.G);
       if (g == 0 && active) {
         if constexpr (CHUNK) store_vec<VEC>(sp.pacc + (int64_t)item * F + cofs, acc);
         else store_vec<VEC>(g_xr + (int64_t)row * ldgr + cofs, acc);
@@ -441,10 +229,7 @@ gatv2_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col
     }
 
     // this workgroup's g_att record for the chunk: lane groups, then waves, in a fixed order
-    for (int off = 32; off >= L.G; off >>= 1) {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) ga[i] += __shfl_xor(ga[i], off);
-    }
+    groups_sum<VEC>(ga, L.G);
     if (g == 0) {
 #pragma unroll
       for (int i = 0; i < VEC; ++i) red[wave][t * VEC + i] = ga[i];
@@ -472,16 +257,9 @@ gatv2_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ c
                      const float* __restrict__ xl, int64_t ldl, const float* __restrict__ xr, int64_t ldr,
                      const float* __restrict__ att, const float2* __restrict__ nodeq, const float* __restrict__ gout,
                      int64_t ldg, float* __restrict__ g_xl, int64_t ldgl, int N, float slope, const GatLayout L,
-                     const V2Split sp, const V2Rng rng) {
+                     const AttnSplit sp, const AttnRng rng) {
   constexpr int U = 2;
-  const int lane = threadIdx.x & 63;
-  const int NG = kWave / L.G;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
+  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
   uint32_t s0 = 0, s1 = 0;
   if constexpr (TRAIN) {
     s0 = rng.seed[0];
@@ -490,16 +268,7 @@ gatv2_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ c
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
     int row, start, end;
-    if constexpr (CHUNK) {
-      row = __builtin_amdgcn_readfirstlane(sp.chunk_row[item]);
-      start = __builtin_amdgcn_readfirstlane(sp.chunk_begin[item]);
-      end = __builtin_amdgcn_readfirstlane(sp.chunk_end[item]);
-    } else {
-      row = item;
-      start = __builtin_amdgcn_readfirstlane(rowptr_t[row]);
-      end = __builtin_amdgcn_readfirstlane(rowptr_t[row + 1]);
-      if (sp.threshold > 0 && end - start > sp.threshold) continue;
-    }
+    if (!row_item<CHUNK>(rowptr_t, sp, item, row, start, end)) continue;
     for (int hbase = 0; hbase < L.H; hbase += L.HPC) {
       const int head = hbase + hl;
       const bool active = hl < L.HPC && head < L.H && ch < L.C;
@@ -545,7 +314,8 @@ gatv2_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ c
             const float dal = head_sum(dot_vec<VEC>(go[u], xlj), L.LPH);
             float kappa = 1.f;
             if constexpr (TRAIN)
-              kappa = drop_keep(s0, s1, __shfl(myslot, idx & 63), head, rng.p_drop) ? rng.inv_keep : 0.f;
+              kappa = drop_keep<kStreamAttnDrop>(s0, s1, __shfl(myslot, idx & 63), head, rng.p_drop)
+                          ? rng.inv_keep : 0.f;
             const float alpha = ok[u] ? expf(e - sh[u]) : 0.f;
             const float de = alpha * (kappa * dal - dsm[u]);
             const float ak = alpha * kappa;
@@ -555,47 +325,11 @@ gatv2_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ c
           }
         }
       }
-      for (int off = 32; off >= L.G; off >>= 1) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] += __shfl_xor(acc[i], off);
-      }
+      groups_sum<VEC>(acc, L.G);
       if (g == 0 && active) {
         if constexpr (CHUNK) store_vec<VEC>(sp.pacc + (int64_t)item * F + cofs, acc);
         else store_vec<VEC>(g_xl + (int64_t)row * ldgl + cofs, acc);
       }
-    }
-  }
-}
-
-// One wave per hub row of either backward pass: chunk sums added in chunk order.
-template <int VEC>
-__global__ void __launch_bounds__(256)
-gatv2_bwd_combine_kernel(int n_long, const int* __restrict__ long_row, const int* __restrict__ long_chunk_ptr,
-                         float* __restrict__ gx, int64_t ldgx, const GatLayout L, const V2Split sp) {
-  const int lane = threadIdx.x & 63;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
-  for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < n_long; r += gridDim.x * wpb) {
-    const int row = long_row[r];
-    const int c0 = long_chunk_ptr[r], c1 = long_chunk_ptr[r + 1];
-    for (int hbase = 0; hbase < L.H; hbase += L.HPC) {
-      const int head = hbase + hl;
-      if (!(g == 0 && hl < L.HPC && head < L.H && ch < L.C)) continue;
-      const int cofs = head * L.C + ch;
-      float acc[VEC];
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-      for (int c = c0; c < c1; ++c) {
-        float a2[VEC];
-        load_vec<VEC>(a2, sp.pacc + (int64_t)c * F + cofs);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] += a2[i];
-      }
-      store_vec<VEC>(gx + (int64_t)row * ldgx + cofs, acc);
     }
   }
 }
@@ -624,35 +358,12 @@ __global__ void __launch_bounds__(256)
 gatv2_draws_kernel(const uint32_t* __restrict__ seed, int64_t nnz, int H, float p_drop, uint8_t* __restrict__ keep) {
   const uint32_t s0 = seed[0], s1 = seed[1];
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += (int64_t)gridDim.x * blockDim.x)
-    for (int h = 0; h < H; ++h) keep[p * H + h] = drop_keep(s0, s1, (int)p, h, p_drop) ? 1 : 0;
+    for (int h = 0; h < H; ++h) keep[p * H + h] = drop_keep<kStreamAttnDrop>(s0, s1, (int)p, h, p_drop) ? 1 : 0;
 }
 
-int split_view(const rgbx_row_split_t* split, int H, int C, bool fwd, V2Split* sd, const char* name) {
-  *sd = V2Split{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (!split || split->threshold <= 0 || split->n_chunks <= 0) return RGBX_OK;
-  if (split->n_long <= 0 || !split->chunk_row || !split->chunk_begin || !split->chunk_end || !split->long_row ||
-      !split->long_chunk_ptr || !split->partial)
-    return fail(RGBX_E_ARG, "%s: incomplete row-split plan", name);
-  const int64_t F = (int64_t)H * C;
-  sd->threshold = split->threshold;
-  sd->chunk_row = split->chunk_row;
-  sd->chunk_begin = split->chunk_begin;
-  sd->chunk_end = split->chunk_end;
-  sd->pacc = split->partial;  // [n_chunks, F]
-  if (fwd) {
-    sd->p0 = sd->pacc + (int64_t)split->n_chunks * F;  // [n_chunks, H]
-    sd->p1 = sd->p0 + (int64_t)split->n_chunks * H;    // [n_chunks, H]
-  }
-  return RGBX_OK;
-}
-
-int make_rng(const uint32_t* seed, float p_drop, V2Rng* rng, const char* name) {
-  *rng = V2Rng{seed, p_drop, 1.0f};
-  if (!seed) return RGBX_OK;
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(RGBX_E_ARG, "%s: dropout must be in [0, 1)", name);
-  rng->inv_keep = 1.0f / (1.0f - p_drop);
-  return RGBX_OK;
-}
+// The target-side backward leaves one g_att record per workgroup, so its grid is capped and the waves stride over the
+// rows.
+int att_grid(int64_t N) { return capped_grid(N, 4); }
 
 int64_t att_records(int64_t N, const rgbx_row_split_t* split) {
   return att_grid(N) + (split && split->threshold > 0 && split->n_chunks > 0 ? att_grid(split->n_chunks) : 0);
@@ -664,8 +375,7 @@ int64_t att_records(int64_t N, const rgbx_row_split_t* split) {
 using namespace rgbx;
 
 extern "C" int rgbx_gatv2_supported(int H, int C) {
-  if (H <= 0 || C <= 0) return 0;
-  return C <= 64 || (C % 2 == 0 && C <= 128) || (C % 4 == 0 && C <= 256);
+  return H > 0 && head_width_supported(C);
 }
 
 extern "C" int rgbx_gatv2_att_partial_floats(int64_t N, int H, int C, const rgbx_row_split_t* split, int64_t* count) {
@@ -681,8 +391,7 @@ extern "C" int rgbx_gatv2_fwd_f32(const int32_t* rowptr, const int32_t* col, con
                                   const uint32_t* seed, float p_drop, const rgbx_row_split_t* split,
                                   rgbx_stream_t stream) {
   if (int rc = check_common(N, H, C, "gatv2_fwd")) return rc;
-  if (!rgbx_gatv2_supported(H, C))
-    return fail(RGBX_E_SHAPE, "gatv2_fwd: %d channels per head (any C <= 64, even C <= 128, C %% 4 == 0 up to 256)", C);
+  if (!head_width_supported(C)) return fail_head_width("gatv2_fwd", C);
   if (N == 0) return RGBX_OK;
   if (!rowptr || !col || !xl || !xr || !att || !out) return fail(RGBX_E_ARG, "gatv2_fwd: null pointer");
   if ((m == nullptr) != (rden == nullptr)) return fail(RGBX_E_ARG, "gatv2_fwd: m and rden go together");
@@ -691,36 +400,17 @@ extern "C" int rgbx_gatv2_fwd_f32(const int32_t* rowptr, const int32_t* col, con
   if (ldl < F || ldr < F || ldo < F) return fail(RGBX_E_ARG, "gatv2_fwd: leading dimension < H*C");
   if (!aligned_to({xl, xr, att, bias, out, m, rden}, 4))
     return fail(RGBX_E_ALIGN, "gatv2_fwd: float pointers must be 4-byte aligned");
-  V2Split sd;
-  if (int rc = split_view(split, H, C, true, &sd, "gatv2_fwd")) return rc;
-  V2Rng rng;
+  AttnSplit sd;
+  if (int rc = split_view(split, H, C, 2, &sd, "gatv2_fwd")) return rc;
+  AttnRng rng;
   if (int rc = make_rng(seed, p_drop, &rng, "gatv2_fwd")) return rc;
   const int vec = pick_vec(C, {xl, xr, att, bias, out, sd.pacc}, {ldl, ldr, ldo});
   GatLayout L;
   if (int rc = make_layout(H, C, vec, &L, "gatv2_fwd")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = gat_grid(N);
-#define RGBX_GATV2_FWD(V, T)                                                                                         \
-  do {                                                                                                               \
-    gatv2_fwd_kernel<V, false, T><<<grid, 256, 0, s>>>(rowptr, col, xl, ldl, xr, ldr, att, bias, out, ldo, m, rden,  \
-                                                       (int)N, slope, L, sd, rng);                                   \
-    if (sd.threshold > 0) {                                                                                          \
-      gatv2_fwd_kernel<V, true, T><<<gat_grid(split->n_chunks), 256, 0, s>>>(                                        \
-          rowptr, col, xl, ldl, xr, ldr, att, bias, out, ldo, m, rden, split->n_chunks, slope, L, sd, rng);          \
-      gatv2_fwd_combine_kernel<V><<<gat_grid(split->n_long), 256, 0, s>>>(                                           \
-          split->n_long, split->long_row, split->long_chunk_ptr, bias, out, ldo, m, rden, L, sd);                    \
-    }                                                                                                                \
-  } while (0)
-  if (seed) {
-    if (vec == 4) RGBX_GATV2_FWD(4, true);
-    else if (vec == 2) RGBX_GATV2_FWD(2, true);
-    else RGBX_GATV2_FWD(1, true);
-  } else {
-    if (vec == 4) RGBX_GATV2_FWD(4, false);
-    else if (vec == 2) RGBX_GATV2_FWD(2, false);
-    else RGBX_GATV2_FWD(1, false);
-  }
-#undef RGBX_GATV2_FWD
+  RGBX_ATTN_DISPATCH(gatv2_fwd_kernel, row_grid, N, rowptr, col, xl, ldl, xr, ldr, att, bias, out, ldo, m, rden,
+                     n_items, slope, L, sd, rng);
+  if (sd.threshold > 0) RGBX_ATTN_FWD_COMBINE(true, bias, out, ldo, m, rden);
   RGBX_CHECK_LAUNCH("gatv2_fwd_kernel");
   return RGBX_OK;
 }
@@ -733,9 +423,7 @@ extern "C" int rgbx_gatv2_bwd_dst_f32(const int32_t* rowptr, const int32_t* col,
                                       float slope, const uint32_t* seed, float p_drop, const rgbx_row_split_t* split,
                                       rgbx_stream_t stream) {
   if (int rc = check_common(N, H, C, "gatv2_bwd_dst")) return rc;
-  if (!rgbx_gatv2_supported(H, C))
-    return fail(RGBX_E_SHAPE, "gatv2_bwd_dst: %d channels per head (any C <= 64, even C <= 128, C %% 4 == 0 up to 256)",
-                C);
+  if (!head_width_supported(C)) return fail_head_width("gatv2_bwd_dst", C);
   if (!g_att) return fail(RGBX_E_ARG, "gatv2_bwd_dst: null pointer");
   const int64_t F = (int64_t)H * C;
   hipStream_t s = (hipStream_t)stream;
@@ -750,9 +438,9 @@ extern "C" int rgbx_gatv2_bwd_dst_f32(const int32_t* rowptr, const int32_t* col,
   if (!aligned_to({nodeq}, 8)) return fail(RGBX_E_ALIGN, "gatv2_bwd_dst: nodeq must be 8-byte aligned");
   if (!aligned_to({xl, xr, att, m, rden, out, bias, gout, g_xr, g_att, att_partial}, 4))
     return fail(RGBX_E_ALIGN, "gatv2_bwd_dst: float pointers must be 4-byte aligned");
-  V2Split sd;
-  if (int rc = split_view(split, H, C, false, &sd, "gatv2_bwd_dst")) return rc;
-  V2Rng rng;
+  AttnSplit sd;
+  if (int rc = split_view(split, H, C, 0, &sd, "gatv2_bwd_dst")) return rc;
+  AttnRng rng;
   if (int rc = make_rng(seed, p_drop, &rng, "gatv2_bwd_dst")) return rc;
   const int64_t n_rec = att_records(N, split);
   if (n_att_partial < n_rec * F)
@@ -763,29 +451,10 @@ extern "C" int rgbx_gatv2_bwd_dst_f32(const int32_t* rowptr, const int32_t* col,
   if (int rc = make_layout(H, C, vec, &L, "gatv2_bwd_dst")) return rc;
   const int grid = att_grid(N);
   float2* nq = reinterpret_cast<float2*>(nodeq);
-#define RGBX_GATV2_BD(V, T)                                                                                          \
-  do {                                                                                                               \
-    gatv2_bwd_dst_kernel<V, false, T><<<grid, 256, 0, s>>>(rowptr, col, xl, ldl, xr, ldr, att, m, rden, out, ldo,    \
-                                                           bias, gout, ldg, nq, g_xr, ldgr, att_partial, (int)N,     \
-                                                           slope, L, sd, rng);                                       \
-    if (sd.threshold > 0) {                                                                                          \
-      gatv2_bwd_dst_kernel<V, true, T><<<att_grid(split->n_chunks), 256, 0, s>>>(                                    \
-          rowptr, col, xl, ldl, xr, ldr, att, m, rden, out, ldo, bias, gout, ldg, nq, g_xr, ldgr,                    \
-          att_partial + (int64_t)grid * F, split->n_chunks, slope, L, sd, rng);                                      \
-      gatv2_bwd_combine_kernel<V><<<gat_grid(split->n_long), 256, 0, s>>>(                                           \
-          split->n_long, split->long_row, split->long_chunk_ptr, g_xr, ldgr, L, sd);                                 \
-    }                                                                                                                \
-  } while (0)
-  if (seed) {
-    if (vec == 4) RGBX_GATV2_BD(4, true);
-    else if (vec == 2) RGBX_GATV2_BD(2, true);
-    else RGBX_GATV2_BD(1, true);
-  } else {
-    if (vec == 4) RGBX_GATV2_BD(4, false);
-    else if (vec == 2) RGBX_GATV2_BD(2, false);
-    else RGBX_GATV2_BD(1, false);
-  }
-#undef RGBX_GATV2_BD
+  RGBX_ATTN_DISPATCH(gatv2_bwd_dst_kernel, att_grid, N, rowptr, col, xl, ldl, xr, ldr, att, m, rden, out, ldo, bias,
+                     gout, ldg, nq, g_xr, ldgr, att_partial + (chunk_pass ? (int64_t)grid * F : 0), n_items, slope, L,
+                     sd, rng);
+  if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(g_xr, ldgr, F, 0);
   RGBX_CHECK_LAUNCH("gatv2_bwd_dst_kernel");
   gatv2_att_reduce_kernel<<<(int)cdiv(F, 16), 256, 0, s>>>(att_partial, n_rec, (int)F, g_att);
   RGBX_CHECK_LAUNCH("gatv2_att_reduce_kernel");
@@ -798,9 +467,7 @@ extern "C" int rgbx_gatv2_bwd_src_f32(const int32_t* rowptr_t, const int32_t* co
                                       int64_t N, int H, int C, float slope, const uint32_t* seed, float p_drop,
                                       const rgbx_row_split_t* split, rgbx_stream_t stream) {
   if (int rc = check_common(N, H, C, "gatv2_bwd_src")) return rc;
-  if (!rgbx_gatv2_supported(H, C))
-    return fail(RGBX_E_SHAPE, "gatv2_bwd_src: %d channels per head (any C <= 64, even C <= 128, C %% 4 == 0 up to 256)",
-                C);
+  if (!head_width_supported(C)) return fail_head_width("gatv2_bwd_src", C);
   if (N == 0) return RGBX_OK;
   if (!rowptr_t || !col_t || !xl || !xr || !att || !nodeq || !gout || !g_xl)
     return fail(RGBX_E_ARG, "gatv2_bwd_src: null pointer");
@@ -810,38 +477,18 @@ extern "C" int rgbx_gatv2_bwd_src_f32(const int32_t* rowptr_t, const int32_t* co
   if (!aligned_to({nodeq}, 8)) return fail(RGBX_E_ALIGN, "gatv2_bwd_src: nodeq must be 8-byte aligned");
   if (!aligned_to({xl, xr, att, gout, g_xl}, 4))
     return fail(RGBX_E_ALIGN, "gatv2_bwd_src: float pointers must be 4-byte aligned");
-  V2Split sd;
-  if (int rc = split_view(split, H, C, false, &sd, "gatv2_bwd_src")) return rc;
-  V2Rng rng;
+  AttnSplit sd;
+  if (int rc = split_view(split, H, C, 0, &sd, "gatv2_bwd_src")) return rc;
+  AttnRng rng;
   if (int rc = make_rng(seed, p_drop, &rng, "gatv2_bwd_src")) return rc;
   const int vec = pick_vec(C, {xl, xr, att, gout, g_xl, sd.pacc}, {ldl, ldr, ldg, ldgl});
   GatLayout L;
   if (int rc = make_layout(H, C, vec, &L, "gatv2_bwd_src")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = gat_grid(N);
   const float2* nq = reinterpret_cast<const float2*>(nodeq);
-#define RGBX_GATV2_BS(V, T)                                                                                          \
-  do {                                                                                                               \
-    gatv2_bwd_src_kernel<V, false, T><<<grid, 256, 0, s>>>(rowptr_t, col_t, t2f, xl, ldl, xr, ldr, att, nq, gout,    \
-                                                           ldg, g_xl, ldgl, (int)N, slope, L, sd, rng);              \
-    if (sd.threshold > 0) {                                                                                          \
-      gatv2_bwd_src_kernel<V, true, T><<<gat_grid(split->n_chunks), 256, 0, s>>>(                                    \
-          rowptr_t, col_t, t2f, xl, ldl, xr, ldr, att, nq, gout, ldg, g_xl, ldgl, split->n_chunks, slope, L, sd,     \
-          rng);                                                                                                      \
-      gatv2_bwd_combine_kernel<V><<<gat_grid(split->n_long), 256, 0, s>>>(                                           \
-          split->n_long, split->long_row, split->long_chunk_ptr, g_xl, ldgl, L, sd);                                 \
-    }                                                                                                                \
-  } while (0)
-  if (seed) {
-    if (vec == 4) RGBX_GATV2_BS(4, true);
-    else if (vec == 2) RGBX_GATV2_BS(2, true);
-    else RGBX_GATV2_BS(1, true);
-  } else {
-    if (vec == 4) RGBX_GATV2_BS(4, false);
-    else if (vec == 2) RGBX_GATV2_BS(2, false);
-    else RGBX_GATV2_BS(1, false);
-  }
-#undef RGBX_GATV2_BS
+  RGBX_ATTN_DISPATCH(gatv2_bwd_src_kernel, row_grid, N, rowptr_t, col_t, t2f, xl, ldl, xr, ldr, att, nq, gout, ldg,
+                     g_xl, ldgl, n_items, slope, L, sd, rng);
+  if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(g_xl, ldgl, F, 0);
   RGBX_CHECK_LAUNCH("gatv2_bwd_src_kernel");
   return RGBX_OK;
 }
@@ -852,7 +499,7 @@ extern "C" int rgbx_gatv2_draws_u8(const uint32_t* seed, int64_t nnz, int H, flo
   if (nnz == 0) return RGBX_OK;
   if (nnz >= INT32_MAX) return fail(RGBX_E_RANGE, "gatv2_draws: E' exceeds int32");
   if (!seed || !keep) return fail(RGBX_E_ARG, "gatv2_draws: null pointer");
-  gatv2_draws_kernel<<<flat_grid(nnz, 256), 256, 0, (hipStream_t)stream>>>(seed, nnz, H, p_drop, keep);
+  gatv2_draws_kernel<<<capped_grid(nnz, 256), 256, 0, (hipStream_t)stream>>>(seed, nnz, H, p_drop, keep);
   RGBX_CHECK_LAUNCH("gatv2_draws_kernel");
   return RGBX_OK;
 }

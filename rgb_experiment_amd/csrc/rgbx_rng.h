@@ -1,6 +1,6 @@
 // Counter-based random draws shared by the kernels that recompute their random decisions in the backward pass
-// (supergat.hip, faconv.hip): a draw is a hash of a 64-bit seed that lives on the device, a stream constant of the
-// caller and two 32-bit counters; no state, no per-edge tensor.
+// (the attention families, through attn_common.h): a draw is a hash of a 64-bit seed that lives on the device, a stream
+// constant of the caller and two 32-bit counters; no state, no per-edge tensor.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -11,106 +11,20 @@
 // Randomness is counter-based: the attention-dropout keep of (forward CSR slot, head), the positive keep of a slot
 // and the negative pairs are hashes of a 64-bit seed that lives on the device. The backward recomputes them; no
 // [E', H] tensor is ever written.
-#include "rgbx_common.h"
-#include "rgbx_rng.h"
+#include "attn_common.h"
 
 namespace rgbx {
 namespace {
 
-// Lane layout and host helpers: the same as gat.hip's (a head occupies LPH = pow2ceil(C / VEC) consecutive lanes of VEC
-// channels, HPC heads side by side in a group of G lanes that reads one neighbour row per step, NG = 64 / G rows per
-// wave-instruction). Kept here rather than moved to a shared header: the text of gat.hip keys the recorded counter
-// measurements of its kernels (bench.py KERNEL_SOURCES), which an edit would invalidate.
-struct GatLayout {
-  int H, C;
-  int LPH;  // lanes per head (power of two)
-  int HPC;  // heads per chunk
-  int G;    // lanes per neighbour row (power of two, >= HPC * LPH)
-};
-
-constexpr float kNegBig = -1.0e30f;
-
-template <int VEC>
-__device__ __forceinline__ float dot_vec(const float (&a)[VEC], const float (&b)[VEC]) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) s = fmaf(a[i], b[i], s);
-  return s;
-}
-
-// Sum over the LPH lanes of a head; every lane of the head ends with the total.
-__device__ __forceinline__ float head_sum(float v, int LPH) {
-  for (int off = LPH >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-int pow2ceil(int x) {
-  int p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
-// VEC must divide C so that a lane's channels stay inside one head.
-int pick_vec(int C, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> lds) {
-  for (int v : {4, 2}) {
-    bool ok = C % v == 0;
-    for (const void* p : ptrs) ok = ok && (reinterpret_cast<uintptr_t>(p) % (v * 4) == 0);
-    for (int64_t ld : lds) ok = ok && (ld % v == 0);
-    if (ok) return v;
-  }
-  return 1;
-}
-
-int make_layout(int H, int C, int vec, GatLayout* L, const char* name) {
-  const int lph = pow2ceil((C + vec - 1) / vec);
-  if (lph > kWave)
-    return fail(RGBX_E_SHAPE, "%s: C=%d needs %d lanes per head (> 64) at vector width %d", name, C,
-                lph, vec);
-  L->H = H;
-  L->C = C;
-  L->LPH = lph;
-  L->HPC = std::min(H, kWave / lph);
-  L->G = pow2ceil(L->HPC * lph);
-  return RGBX_OK;
-}
-
-int gat_grid(int64_t N) {  // one row per wave, no cap (see spmm.hip: uncapped grids balance ragged rows better)
-  return (int)cdiv(N, 4);
-}
-
-int check_common(int64_t N, int H, int C, const char* name) {
-  if (N < 0 || H <= 0 || C <= 0) return fail(RGBX_E_ARG, "%s: bad size", name);
-  if (N >= INT32_MAX || (int64_t)H * C >= INT32_MAX) return fail(RGBX_E_RANGE, "%s: size exceeds int32", name);
-  return RGBX_OK;
-}
-
-
-struct SgatSplit {
-  int threshold;
-  const int* chunk_row;
-  const int* chunk_begin;
-  const int* chunk_end;
-  float* pacc;  // [n_chunks, F]
-  float* p0;    // [n_chunks, H]
-  float* p1;    // [n_chunks, H]  (forward only)
-};
-
-// Training-mode state of one forward: `seed` = two 32-bit words on the device.
-struct SgatRng {
-  const uint32_t* seed;
-  float p_drop;     // attention dropout probability
-  float inv_keep;   // 1 / (1 - p_drop)
-  float pos_ratio;  // edge_sample_ratio
+// Training-mode state of one forward: the attention dropout's, and edge_sample_ratio beside it.
+struct SgatRng : AttnRng {
+  float pos_ratio;
 };
 
 constexpr uint32_t kStreamDrop = 0x243F6A88u, kStreamPos = 0x85A308D3u, kStreamNegU = 0x13198A2Eu,
                    kStreamNegV = 0x03707344u;
 
-// mix32 / draw32 / unit24: rgbx_rng.h (shared with faconv.hip)
-
-__device__ __forceinline__ bool drop_keep(uint32_t s0, uint32_t s1, int slot, int head, float p) {
-  return unit24(draw32(s0, s1, kStreamDrop, (uint32_t)slot, (uint32_t)head)) >= p;
-}
+// mix32 / draw32 / unit24: rgbx_rng.h; drop_keep<kStreamDrop>: attn_common.h
 
 __device__ __forceinline__ bool pos_keep(uint32_t s0, uint32_t s1, int slot, float ratio) {
   return unit24(draw32(s0, s1, kStreamPos, (uint32_t)slot, 0u)) < ratio;
@@ -174,17 +88,10 @@ __global__ void __launch_bounds__(256)
 sgat_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ hfeat,
                 int64_t ldh, const float* __restrict__ att_l, const float* __restrict__ att_r,
                 const float* __restrict__ bias, float* __restrict__ out, int64_t ldo, float* __restrict__ m_out,
-                float* __restrict__ rden_out, int N, float slope, const GatLayout L, const SgatSplit sp,
+                float* __restrict__ rden_out, int N, float slope, const GatLayout L, const AttnSplit sp,
                 const SgatRng rng, float2* __restrict__ loss_part) {
   constexpr int U = TRAIN ? 3 : 4;  // neighbour rows in flight per lane group
-  const int lane = threadIdx.x & 63;
-  const int NG = kWave / L.G;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
+  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
   const bool multi = L.H > L.HPC;
   const float inv_h = 1.0f / (float)L.H;
   uint32_t s0 = 0, s1 = 0;
@@ -196,16 +103,7 @@ sgat_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, con
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
     int row, start, end;
-    if constexpr (CHUNK) {
-      row = __builtin_amdgcn_readfirstlane(sp.chunk_row[item]);
-      start = __builtin_amdgcn_readfirstlane(sp.chunk_begin[item]);
-      end = __builtin_amdgcn_readfirstlane(sp.chunk_end[item]);
-    } else {
-      row = item;
-      start = __builtin_amdgcn_readfirstlane(rowptr[row]);
-      end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-      if (sp.threshold > 0 && end - start > sp.threshold) continue;  // the chunk + combine kernels own it
-    }
+    if (!row_item<CHUNK>(rowptr, sp, item, row, start, end)) continue;
     const float* hrow = hfeat + (int64_t)row * ldh;
     for (int hbase = 0; hbase < L.H; hbase += L.HPC) {
       const int head = hbase + hl;
@@ -257,7 +155,8 @@ sgat_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, con
             const float p = ok[u] ? expf(e - mn) : 0.f;
             l = fmaf(l, sc, p);
             float pk = p;
-            if constexpr (TRAIN) pk = drop_keep(s0, s1, base + idx, head, rng.p_drop) ? p * rng.inv_keep : 0.f;
+            if constexpr (TRAIN)
+              pk = drop_keep<kStreamDrop>(s0, s1, base + idx, head, rng.p_drop) ? p * rng.inv_keep : 0.f;
 #pragma unroll
             for (int i = 0; i < VEC; ++i) acc[i] = fmaf(acc[i], sc, pk * v[u][i]);
             m = mn;
@@ -276,20 +175,7 @@ sgat_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, con
           }
         }
       }
-      // merge the NG online-softmax states
-      for (int off = 32; off >= L.G; off >>= 1) {
-        const float m2 = __shfl_xor(m, off);
-        const float l2 = __shfl_xor(l, off);
-        const float mn = fmaxf(m, m2);
-        const float s1m = expf(m - mn), s2m = expf(m2 - mn);
-        l = l * s1m + l2 * s2m;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-          const float a2 = __shfl_xor(acc[i], off);
-          acc[i] = acc[i] * s1m + a2 * s2m;
-        }
-        m = mn;
-      }
+      softmax_merge_groups<VEC>(m, l, acc, L.G);
       if (g == 0 && active) {
         if constexpr (CHUNK) {  // un-normalised online-softmax state of this chunk
           store_vec<VEC>(sp.pacc + (int64_t)item * F + cofs, acc);
@@ -315,59 +201,6 @@ sgat_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col, con
     }
   }
   if constexpr (TRAIN) block_loss_store(lsum, lcnt, loss_part);
-}
-
-// One wave per hub row: merge the chunk states in chunk order, normalise, store.
-template <int VEC>
-__global__ void __launch_bounds__(256)
-sgat_fwd_combine_kernel(int n_long, const int* __restrict__ long_row, const int* __restrict__ long_chunk_ptr,
-                        const float* __restrict__ bias, float* __restrict__ out, int64_t ldo,
-                        float* __restrict__ m_out, float* __restrict__ rden_out, const GatLayout L,
-                        const SgatSplit sp) {
-  const int lane = threadIdx.x & 63;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
-  for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < n_long; r += gridDim.x * wpb) {
-    const int row = long_row[r];
-    const int c0 = long_chunk_ptr[r], c1 = long_chunk_ptr[r + 1];
-    for (int hbase = 0; hbase < L.H; hbase += L.HPC) {
-      const int head = hbase + hl;
-      if (!(g == 0 && hl < L.HPC && head < L.H && ch < L.C)) continue;
-      const int cofs = head * L.C + ch;
-      float m = kNegBig, l = 0.f;
-      float acc[VEC];
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-      for (int c = c0; c < c1; ++c) {
-        const float m2 = sp.p0[(int64_t)c * L.H + head];
-        const float l2 = sp.p1[(int64_t)c * L.H + head];
-        float a2[VEC];
-        load_vec<VEC>(a2, sp.pacc + (int64_t)c * F + cofs);
-        const float mn = fmaxf(m, m2);
-        const float s1 = expf(m - mn), s2 = expf(m2 - mn);
-        l = l * s1 + l2 * s2;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = acc[i] * s1 + a2[i] * s2;
-        m = mn;
-      }
-      const float rd = l > 0.f ? 1.0f / (l + 1e-16f) : 0.f;
-      float bv[VEC];
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) bv[i] = 0.f;
-      if (bias) load_vec<VEC>(bv, bias + cofs);
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc[i] = acc[i] * rd + bv[i];
-      store_vec<VEC>(out + (int64_t)row * ldo + cofs, acc);
-      if (ch == 0) {
-        m_out[(int64_t)row * L.H + head] = l > 0.f ? m : 0.f;
-        rden_out[(int64_t)row * L.H + head] = rd;
-      }
-    }
-  }
 }
 
 // Per-workgroup (sum, count) records added in record order, in double: stats[0] = sum, stats[1] = count.
@@ -421,8 +254,6 @@ __device__ __forceinline__ EdgeGrad edge_grad(float d, float t, float dal, float
   return r;
 }
 
-__device__ __forceinline__ float softmax_shift(float m, float rden) { return rden > 0.f ? m - logf(rden) : 0.f; }
-
 // Backward, target side, over the forward CSR (row = target i):
 //   g_hfeat[i,h,:] = sum_p g_d_p h_j + (sum_p g_t_p) att_r[h,:],   g_ar[i,h] = sum_p g_t_p
 // and the per-(target, head) record nodeq = (<h_i, att_r>, m - log(rden), <gout_i, out_i - bias>, 0) of the source pass.
@@ -433,17 +264,10 @@ sgat_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                     const float* __restrict__ m_in, const float* __restrict__ rden_in, const float* __restrict__ out,
                     int64_t ldo, const float* __restrict__ bias, const float* __restrict__ gout, int64_t ldg,
                     float4* __restrict__ nodeq, float* __restrict__ g_hfeat, int64_t ldgh, float* __restrict__ g_ar,
-                    int N, float slope, const GatLayout L, const SgatSplit sp, const SgatRng rng,
+                    int N, float slope, const GatLayout L, const AttnSplit sp, const SgatRng rng,
                     const float* __restrict__ gl) {
   constexpr int U = 3;
-  const int lane = threadIdx.x & 63;
-  const int NG = kWave / L.G;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
+  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
   const bool multi = L.H > L.HPC;
   const float inv_h = 1.0f / (float)L.H;
   uint32_t s0 = 0, s1 = 0;
@@ -456,17 +280,8 @@ sgat_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
     int row, start, end;
-    bool hub = false;
-    if constexpr (CHUNK) {
-      row = __builtin_amdgcn_readfirstlane(sp.chunk_row[item]);
-      start = __builtin_amdgcn_readfirstlane(sp.chunk_begin[item]);
-      end = __builtin_amdgcn_readfirstlane(sp.chunk_end[item]);
-    } else {
-      row = item;
-      start = __builtin_amdgcn_readfirstlane(rowptr[row]);
-      end = __builtin_amdgcn_readfirstlane(rowptr[row + 1]);
-      hub = sp.threshold > 0 && end - start > sp.threshold;  // record here, sums by the chunk + combine kernels
-    }
+    // a hub row: its record here, its sums by the chunk + combine kernels
+    const bool hub = !row_item<CHUNK>(rowptr, sp, item, row, start, end);
     const float* hrow = hfeat + (int64_t)row * ldh;
     for (int hbase = 0; hbase < L.H; hbase += L.HPC) {
       const int head = hbase + hl;
@@ -527,7 +342,8 @@ sgat_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
             const float al = head_sum(dot_vec<VEC>(v[u], atl), L.LPH);
             const float dal = head_sum(dot_vec<VEC>(v[u], go), L.LPH);
             float kappa = 1.f;
-            if constexpr (TRAIN) kappa = drop_keep(s0, s1, base + idx, head, rng.p_drop) ? rng.inv_keep : 0.f;
+            if constexpr (TRAIN)
+              kappa = drop_keep<kStreamDrop>(s0, s1, base + idx, head, rng.p_drop) ? rng.inv_keep : 0.f;
             const EdgeGrad eg = edge_grad(d, al + ar, dal, shift, dsum, kappa, slope, ok[u]);
             float g_d = eg.g_d;
             if constexpr (TRAIN) {
@@ -574,16 +390,9 @@ sgat_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ co
                     const float* __restrict__ hfeat, int64_t ldh, const float* __restrict__ att_l,
                     const float4* __restrict__ nodeq, const float* __restrict__ gout, int64_t ldg,
                     float* __restrict__ g_hfeat, int64_t ldgh, float* __restrict__ g_al, int N, float slope,
-                    const GatLayout L, const SgatSplit sp, const SgatRng rng, const float* __restrict__ gl) {
+                    const GatLayout L, const AttnSplit sp, const SgatRng rng, const float* __restrict__ gl) {
   constexpr int U = 2;  // two rows (h_i, gout_i) are gathered per edge
-  const int lane = threadIdx.x & 63;
-  const int NG = kWave / L.G;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
+  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
   const bool multi = L.H > L.HPC;
   const float inv_h = 1.0f / (float)L.H;
   uint32_t s0 = 0, s1 = 0;
@@ -596,16 +405,7 @@ sgat_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ co
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
     int row, start, end;
-    if constexpr (CHUNK) {
-      row = __builtin_amdgcn_readfirstlane(sp.chunk_row[item]);
-      start = __builtin_amdgcn_readfirstlane(sp.chunk_begin[item]);
-      end = __builtin_amdgcn_readfirstlane(sp.chunk_end[item]);
-    } else {
-      row = item;
-      start = __builtin_amdgcn_readfirstlane(rowptr_t[row]);
-      end = __builtin_amdgcn_readfirstlane(rowptr_t[row + 1]);
-      if (sp.threshold > 0 && end - start > sp.threshold) continue;
-    }
+    if (!row_item<CHUNK>(rowptr_t, sp, item, row, start, end)) continue;
     const float* hrow = hfeat + (int64_t)row * ldh;
     for (int hbase = 0; hbase < L.H; hbase += L.HPC) {
       const int head = hbase + hl;
@@ -657,7 +457,7 @@ sgat_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ co
             int slot = 0;
             if constexpr (TRAIN) {
               slot = __shfl(myslot, idx & 63);
-              kappa = drop_keep(s0, s1, slot, head, rng.p_drop) ? rng.inv_keep : 0.f;
+              kappa = drop_keep<kStreamDrop>(s0, s1, slot, head, rng.p_drop) ? rng.inv_keep : 0.f;
             }
             const EdgeGrad eg = edge_grad(d, al + ar[u], dal, sh[u], dsm[u], kappa, slope, ok[u]);
             float g_d = eg.g_d;
@@ -702,14 +502,8 @@ template <int VEC>
 __global__ void __launch_bounds__(256)
 sgat_bwd_combine_kernel(int n_long, const int* __restrict__ long_row, const int* __restrict__ long_chunk_ptr,
                         const float* __restrict__ att, float* __restrict__ g_hfeat, int64_t ldgh,
-                        float* __restrict__ g_a, int accumulate, const GatLayout L, const SgatSplit sp) {
-  const int lane = threadIdx.x & 63;
-  const int g = lane / L.G;
-  const int t = lane % L.G;
-  const int hl = t / L.LPH;
-  const int ch = (t % L.LPH) * VEC;
-  const int wpb = blockDim.x >> 6;
-  const int F = L.H * L.C;
+                        float* __restrict__ g_a, int accumulate, const GatLayout L, const AttnSplit sp) {
+  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
   for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < n_long; r += gridDim.x * wpb) {
     const int row = long_row[r];
     const int c0 = long_chunk_ptr[r], c1 = long_chunk_ptr[r + 1];
@@ -831,39 +625,23 @@ sgat_draws_kernel(const uint32_t* __restrict__ seed, int64_t nnz, int H, float p
   const uint32_t s0 = seed[0], s1 = seed[1];
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += (int64_t)gridDim.x * blockDim.x) {
     pos[p] = pos_keep(s0, s1, (int)p, pos_ratio) ? 1 : 0;
-    for (int h = 0; h < H; ++h) drop[p * H + h] = drop_keep(s0, s1, (int)p, h, p_drop) ? 1 : 0;
+    for (int h = 0; h < H; ++h) drop[p * H + h] = drop_keep<kStreamDrop>(s0, s1, (int)p, h, p_drop) ? 1 : 0;
   }
 }
 
-int sgat_split_view(const rgbx_row_split_t* split, int H, int C, int scalars, SgatSplit* sd, const char* name) {
-  *sd = SgatSplit{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (!split || split->threshold <= 0 || split->n_chunks <= 0) return RGBX_OK;
-  if (split->n_long <= 0 || !split->chunk_row || !split->chunk_begin || !split->chunk_end || !split->long_row ||
-      !split->long_chunk_ptr || !split->partial)
-    return fail(RGBX_E_ARG, "%s: incomplete row-split plan", name);
-  const int64_t F = (int64_t)H * C;
-  sd->threshold = split->threshold;
-  sd->chunk_row = split->chunk_row;
-  sd->chunk_begin = split->chunk_begin;
-  sd->chunk_end = split->chunk_end;
-  sd->pacc = split->partial;                            // [n_chunks, F]
-  sd->p0 = sd->pacc + (int64_t)split->n_chunks * F;     // [n_chunks, H]
-  sd->p1 = scalars > 1 ? sd->p0 + (int64_t)split->n_chunks * H : nullptr;
-  return RGBX_OK;
+void launch_sgat_bwd_combine(int vec, const rgbx_row_split_t* split, const float* att, float* g_hfeat, int64_t ldgh,
+                             float* g_a, int accumulate, const GatLayout& L, const AttnSplit& sd, hipStream_t s) {
+  RGBX_VEC_SWITCH(vec, sgat_bwd_combine_kernel<V><<<row_grid(split->n_long), 256, 0, s>>>(split->n_long,
+                  split->long_row, split->long_chunk_ptr, att, g_hfeat, ldgh, g_a, accumulate, L, sd));
 }
 
 int sgat_rng(const uint32_t* seed, float p_drop, float pos_ratio, bool train, SgatRng* rng, const char* name) {
-  *rng = SgatRng{seed, p_drop, 1.0f, pos_ratio};
+  *rng = SgatRng{{seed, p_drop, 1.0f}, pos_ratio};
   if (!train) return RGBX_OK;
   if (!(p_drop >= 0.f && p_drop < 1.f) || !(pos_ratio >= 0.f && pos_ratio <= 1.f))
     return fail(RGBX_E_ARG, "%s: dropout must be in [0, 1) and edge_sample_ratio in [0, 1]", name);
   rng->inv_keep = 1.0f / (1.0f - p_drop);
   return RGBX_OK;
-}
-
-int neg_grid(int64_t n_neg, int pairs_per_block) {
-  const int64_t b = cdiv(n_neg, pairs_per_block);
-  return (int)(b < 1 ? 1 : (b < kMaxGrid ? b : kMaxGrid));
 }
 
 }  // namespace
@@ -872,13 +650,12 @@ int neg_grid(int64_t n_neg, int pairs_per_block) {
 using namespace rgbx;
 
 extern "C" int rgbx_supergat_supported(int H, int C) {
-  if (H <= 0 || C <= 0) return 0;
-  return C <= 64 || (C % 2 == 0 && C <= 128) || (C % 4 == 0 && C <= 256);
+  return H > 0 && head_width_supported(C);
 }
 
 extern "C" int rgbx_supergat_loss_records(int64_t N, const rgbx_row_split_t* split, int64_t* count) {
   if (!count || N < 0) return fail(RGBX_E_ARG, "supergat_loss_records: bad argument");
-  *count = gat_grid(N) + (split && split->threshold > 0 && split->n_chunks > 0 ? gat_grid(split->n_chunks) : 0);
+  *count = row_grid(N) + (split && split->threshold > 0 && split->n_chunks > 0 ? row_grid(split->n_chunks) : 0);
   return RGBX_OK;
 }
 
@@ -896,12 +673,12 @@ extern "C" int rgbx_supergat_aggregate_fwd_f32(const int32_t* rowptr, const int3
   if (ldh < (int64_t)H * C || ldo < (int64_t)H * C) return fail(RGBX_E_ARG, "supergat_fwd: leading dimension < H*C");
   const bool train = seed != nullptr;
   if (train && (!loss_records || !pos_stats)) return fail(RGBX_E_ARG, "supergat_fwd: training mode needs loss buffers");
-  SgatSplit sd;
-  if (int rc = sgat_split_view(split, H, C, 2, &sd, "supergat_fwd")) return rc;
+  AttnSplit sd;
+  if (int rc = split_view(split, H, C, 2, &sd, "supergat_fwd")) return rc;
   SgatRng rng;
   if (int rc = sgat_rng(seed, p_drop, pos_ratio, train, &rng, "supergat_fwd")) return rc;
-  const int grid = gat_grid(N);
-  const int grid_c = sd.threshold > 0 ? gat_grid(split->n_chunks) : 0;
+  const int grid = row_grid(N);
+  const int grid_c = sd.threshold > 0 ? row_grid(split->n_chunks) : 0;
   if (train && n_loss_records < (int64_t)grid + grid_c)
     return fail(RGBX_E_WS, "supergat_fwd: %lld loss records < %lld", (long long)n_loss_records,
                 (long long)grid + grid_c);
@@ -911,28 +688,9 @@ extern "C" int rgbx_supergat_aggregate_fwd_f32(const int32_t* rowptr, const int3
   if (int rc = make_layout(H, C, vec, &L, "supergat_fwd")) return rc;
   hipStream_t s = (hipStream_t)stream;
   float2* part = reinterpret_cast<float2*>(loss_records);
-#define RGBX_SGAT_FWD(V, T)                                                                                         \
-  do {                                                                                                              \
-    sgat_fwd_kernel<V, false, T><<<grid, 256, 0, s>>>(rowptr, col, hfeat, ldh, att_l, att_r, bias, out, ldo, m,     \
-                                                      rden, (int)N, slope, L, sd, rng, part);                       \
-    if (sd.threshold > 0) {                                                                                         \
-      sgat_fwd_kernel<V, true, T><<<grid_c, 256, 0, s>>>(rowptr, col, hfeat, ldh, att_l, att_r, bias, out, ldo, m,  \
-                                                         rden, split->n_chunks, slope, L, sd, rng,                  \
-                                                         T ? part + grid : part);                                   \
-      sgat_fwd_combine_kernel<V><<<gat_grid(split->n_long), 256, 0, s>>>(                                           \
-          split->n_long, split->long_row, split->long_chunk_ptr, bias, out, ldo, m, rden, L, sd);                   \
-    }                                                                                                               \
-  } while (0)
-  if (train) {
-    if (vec == 4) RGBX_SGAT_FWD(4, true);
-    else if (vec == 2) RGBX_SGAT_FWD(2, true);
-    else RGBX_SGAT_FWD(1, true);
-  } else {
-    if (vec == 4) RGBX_SGAT_FWD(4, false);
-    else if (vec == 2) RGBX_SGAT_FWD(2, false);
-    else RGBX_SGAT_FWD(1, false);
-  }
-#undef RGBX_SGAT_FWD
+  RGBX_ATTN_DISPATCH(sgat_fwd_kernel, row_grid, N, rowptr, col, hfeat, ldh, att_l, att_r, bias, out, ldo, m, rden,
+                     n_items, slope, L, sd, rng, part + (chunk_pass && train ? grid : 0));
+  if (sd.threshold > 0) RGBX_ATTN_FWD_COMBINE(true, bias, out, ldo, m, rden);
   RGBX_CHECK_LAUNCH("sgat_fwd_kernel");
   if (train) {
     sgat_loss_finish_kernel<<<1, 256, 0, s>>>(part, grid + grid_c, pos_stats);
@@ -957,39 +715,18 @@ extern "C" int rgbx_supergat_bwd_dst_f32(const int32_t* rowptr, const int32_t* c
   if (!aligned16(nodeq)) return fail(RGBX_E_ALIGN, "supergat_bwd_dst: nodeq must be 16-byte aligned");
   const bool train = seed != nullptr;
   if (train && !gl) return fail(RGBX_E_ARG, "supergat_bwd_dst: training mode needs the loss gradient scalar");
-  SgatSplit sd;
-  if (int rc = sgat_split_view(split, H, C, 1, &sd, "supergat_bwd_dst")) return rc;
+  AttnSplit sd;
+  if (int rc = split_view(split, H, C, 1, &sd, "supergat_bwd_dst")) return rc;
   SgatRng rng;
   if (int rc = sgat_rng(seed, p_drop, pos_ratio, train, &rng, "supergat_bwd_dst")) return rc;
   const int vec = pick_vec(C, {hfeat, out, gout, g_hfeat, att_l, att_r, bias, sd.pacc}, {ldh, ldo, ldg, ldgh});
   GatLayout L;
   if (int rc = make_layout(H, C, vec, &L, "supergat_bwd_dst")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = gat_grid(N);
   float4* nq = reinterpret_cast<float4*>(nodeq);
-#define RGBX_SGAT_BD(V, T)                                                                                          \
-  do {                                                                                                              \
-    sgat_bwd_dst_kernel<V, false, T><<<grid, 256, 0, s>>>(rowptr, col, hfeat, ldh, att_l, att_r, m, rden, out, ldo, \
-                                                          bias, gout, ldg, nq, g_hfeat, ldgh, g_ar, (int)N, slope,  \
-                                                          L, sd, rng, gl);                                          \
-    if (sd.threshold > 0) {                                                                                         \
-      sgat_bwd_dst_kernel<V, true, T><<<gat_grid(split->n_chunks), 256, 0, s>>>(                                    \
-          rowptr, col, hfeat, ldh, att_l, att_r, m, rden, out, ldo, bias, gout, ldg, nq, g_hfeat, ldgh, g_ar,       \
-          split->n_chunks, slope, L, sd, rng, gl);                                                                  \
-      sgat_bwd_combine_kernel<V><<<gat_grid(split->n_long), 256, 0, s>>>(                                           \
-          split->n_long, split->long_row, split->long_chunk_ptr, att_r, g_hfeat, ldgh, g_ar, 0, L, sd);             \
-    }                                                                                                               \
-  } while (0)
-  if (train) {
-    if (vec == 4) RGBX_SGAT_BD(4, true);
-    else if (vec == 2) RGBX_SGAT_BD(2, true);
-    else RGBX_SGAT_BD(1, true);
-  } else {
-    if (vec == 4) RGBX_SGAT_BD(4, false);
-    else if (vec == 2) RGBX_SGAT_BD(2, false);
-    else RGBX_SGAT_BD(1, false);
-  }
-#undef RGBX_SGAT_BD
+  RGBX_ATTN_DISPATCH(sgat_bwd_dst_kernel, row_grid, N, rowptr, col, hfeat, ldh, att_l, att_r, m, rden, out, ldo, bias,
+                     gout, ldg, nq, g_hfeat, ldgh, g_ar, n_items, slope, L, sd, rng, gl);
+  if (sd.threshold > 0) launch_sgat_bwd_combine(vec, split, att_r, g_hfeat, ldgh, g_ar, 0, L, sd, s);
   RGBX_CHECK_LAUNCH("sgat_bwd_dst_kernel");
   return RGBX_OK;
 }
@@ -1009,38 +746,18 @@ extern "C" int rgbx_supergat_bwd_src_f32(const int32_t* rowptr_t, const int32_t*
   if (!aligned16(nodeq)) return fail(RGBX_E_ALIGN, "supergat_bwd_src: nodeq must be 16-byte aligned");
   const bool train = seed != nullptr;
   if (train && (!gl || !t2f)) return fail(RGBX_E_ARG, "supergat_bwd_src: training mode needs gl and the slot map");
-  SgatSplit sd;
-  if (int rc = sgat_split_view(split, H, C, 1, &sd, "supergat_bwd_src")) return rc;
+  AttnSplit sd;
+  if (int rc = split_view(split, H, C, 1, &sd, "supergat_bwd_src")) return rc;
   SgatRng rng;
   if (int rc = sgat_rng(seed, p_drop, pos_ratio, train, &rng, "supergat_bwd_src")) return rc;
   const int vec = pick_vec(C, {hfeat, gout, g_hfeat, att_l, sd.pacc}, {ldh, ldg, ldgh});
   GatLayout L;
   if (int rc = make_layout(H, C, vec, &L, "supergat_bwd_src")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int grid = gat_grid(N);
   const float4* nq = reinterpret_cast<const float4*>(nodeq);
-#define RGBX_SGAT_BS(V, T)                                                                                           \
-  do {                                                                                                               \
-    sgat_bwd_src_kernel<V, false, T><<<grid, 256, 0, s>>>(rowptr_t, col_t, t2f, hfeat, ldh, att_l, nq, gout, ldg,    \
-                                                          g_hfeat, ldgh, g_al, (int)N, slope, L, sd, rng, gl);       \
-    if (sd.threshold > 0) {                                                                                          \
-      sgat_bwd_src_kernel<V, true, T><<<gat_grid(split->n_chunks), 256, 0, s>>>(                                     \
-          rowptr_t, col_t, t2f, hfeat, ldh, att_l, nq, gout, ldg, g_hfeat, ldgh, g_al, split->n_chunks, slope, L,    \
-          sd, rng, gl);                                                                                              \
-      sgat_bwd_combine_kernel<V><<<gat_grid(split->n_long), 256, 0, s>>>(                                            \
-          split->n_long, split->long_row, split->long_chunk_ptr, att_l, g_hfeat, ldgh, g_al, 1, L, sd);              \
-    }                                                                                                                \
-  } while (0)
-  if (train) {
-    if (vec == 4) RGBX_SGAT_BS(4, true);
-    else if (vec == 2) RGBX_SGAT_BS(2, true);
-    else RGBX_SGAT_BS(1, true);
-  } else {
-    if (vec == 4) RGBX_SGAT_BS(4, false);
-    else if (vec == 2) RGBX_SGAT_BS(2, false);
-    else RGBX_SGAT_BS(1, false);
-  }
-#undef RGBX_SGAT_BS
+  RGBX_ATTN_DISPATCH(sgat_bwd_src_kernel, row_grid, N, rowptr_t, col_t, t2f, hfeat, ldh, att_l, nq, gout, ldg, g_hfeat,
+                     ldgh, g_al, n_items, slope, L, sd, rng, gl);
+  if (sd.threshold > 0) launch_sgat_bwd_combine(vec, split, att_l, g_hfeat, ldgh, g_al, 1, L, sd, s);
   RGBX_CHECK_LAUNCH("sgat_bwd_src_kernel");
   return RGBX_OK;
 }
@@ -1053,8 +770,8 @@ extern "C" int rgbx_supergat_sample_negatives(const uint64_t* keys, int64_t n_ke
   if (N < 2) return fail(RGBX_E_ARG, "supergat_sample_negatives: a pair needs two nodes");
   if (N >= INT32_MAX || n_neg >= INT32_MAX) return fail(RGBX_E_RANGE, "supergat_sample_negatives: size exceeds int32");
   if ((n_keys > 0 && !keys) || !seed || !neg || !valid) return fail(RGBX_E_ARG, "supergat_sample_negatives: null pointer");
-  sgat_sample_neg_kernel<<<neg_grid(n_neg, 256), 256, 0, (hipStream_t)stream>>>(keys, n_keys, N, seed, n_neg, redraws,
-                                                                                neg, valid);
+  sgat_sample_neg_kernel<<<capped_grid(n_neg, 256), 256, 0, (hipStream_t)stream>>>(keys, n_keys, N, seed, n_neg,
+                                                                                   redraws, neg, valid);
   RGBX_CHECK_LAUNCH("sgat_sample_neg_kernel");
   return RGBX_OK;
 }
@@ -1082,16 +799,12 @@ extern "C" int rgbx_supergat_neg_loss_fwd_f32(const float* hfeat, int64_t ldh, c
   if (ldh < F) return fail(RGBX_E_ARG, "supergat_neg_loss_fwd: leading dimension < H*C");
   int vec, lp;
   neg_layout(hfeat, ldh, nullptr, 0, F, &vec, &lp);
-  const int grid = neg_grid(n_neg, 4 * (kWave / lp));
+  const int grid = capped_grid(n_neg, 4 * (kWave / lp));
   if (n_loss_records < grid)
     return fail(RGBX_E_WS, "supergat_neg_loss_fwd: %lld loss records < %d", (long long)n_loss_records, grid);
   float2* part = reinterpret_cast<float2*>(loss_records);
-#define RGBX_SGAT_NF(V) \
-  sgat_neg_kernel<V, false><<<grid, 256, 0, s>>>(hfeat, ldh, neg, valid, n_neg, (int)F, lp, 1.0f / H, part, nullptr, nullptr, 0)
-  if (vec == 4) RGBX_SGAT_NF(4);
-  else if (vec == 2) RGBX_SGAT_NF(2);
-  else RGBX_SGAT_NF(1);
-#undef RGBX_SGAT_NF
+  RGBX_VEC_SWITCH(vec, sgat_neg_kernel<V, false><<<grid, 256, 0, s>>>(hfeat, ldh, neg, valid, n_neg, (int)F, lp,
+                  1.0f / H, part, nullptr, nullptr, 0));
   RGBX_CHECK_LAUNCH("sgat_neg_kernel");
   sgat_loss_finish_kernel<<<1, 256, 0, s>>>(part, grid, neg_stats);
   RGBX_CHECK_LAUNCH("sgat_loss_finish_kernel");
@@ -1108,14 +821,10 @@ extern "C" int rgbx_supergat_neg_loss_bwd_f32(const float* hfeat, int64_t ldh, c
   if (ldh < F || ldgh < F) return fail(RGBX_E_ARG, "supergat_neg_loss_bwd: leading dimension < H*C");
   int vec, lp;
   neg_layout(hfeat, ldh, g_hfeat, ldgh, F, &vec, &lp);
-  const int grid = neg_grid(n_neg, 4 * (kWave / lp));
+  const int grid = capped_grid(n_neg, 4 * (kWave / lp));
   hipStream_t s = (hipStream_t)stream;
-#define RGBX_SGAT_NB(V) \
-  sgat_neg_kernel<V, true><<<grid, 256, 0, s>>>(hfeat, ldh, neg, valid, n_neg, (int)F, lp, 1.0f / H, nullptr, gl, g_hfeat, ldgh)
-  if (vec == 4) RGBX_SGAT_NB(4);
-  else if (vec == 2) RGBX_SGAT_NB(2);
-  else RGBX_SGAT_NB(1);
-#undef RGBX_SGAT_NB
+  RGBX_VEC_SWITCH(vec, sgat_neg_kernel<V, true><<<grid, 256, 0, s>>>(hfeat, ldh, neg, valid, n_neg, (int)F, lp,
+                  1.0f / H, nullptr, gl, g_hfeat, ldgh));
   RGBX_CHECK_LAUNCH("sgat_neg_kernel");
   return RGBX_OK;
 }
@@ -1126,7 +835,7 @@ extern "C" int rgbx_supergat_draws_u8(const uint32_t* seed, int64_t nnz, int H, 
   if (nnz == 0) return RGBX_OK;
   if (nnz >= INT32_MAX) return fail(RGBX_E_RANGE, "supergat_draws: E' exceeds int32");
   if (!seed || !pos || !drop) return fail(RGBX_E_ARG, "supergat_draws: null pointer");
-  sgat_draws_kernel<<<neg_grid(nnz, 256), 256, 0, (hipStream_t)stream>>>(seed, nnz, H, p_drop, pos_ratio, pos, drop);
+  sgat_draws_kernel<<<capped_grid(nnz, 256), 256, 0, (hipStream_t)stream>>>(seed, nnz, H, p_drop, pos_ratio, pos, drop);
   RGBX_CHECK_LAUNCH("sgat_draws_kernel");
   return RGBX_OK;
 }

@@ -2238,8 +2238,9 @@ def gat_attend_linear(x, weight, att_src, att_dst, graph, slope=0.2, bias=None, 
 SUPERGAT_REDRAWS = 8  # candidate pairs a negative slot may draw before it is dropped from the loss
 
 
-def _supergat_split(csr, H, C, scalars, dev):
-    split, scratch = csr.split_arg(H * C + scalars * H, dev)
+def _attn_split(csr, width, dev):
+    """The hub-row plan of `csr` with `width` scratch floats per chunk, as (argument, plan, scratch owner)."""
+    split, scratch = csr.split_arg(width, dev)
     return (None if split is None else ctypes.byref(split)), split, scratch
 
 
@@ -2298,7 +2299,7 @@ class _SuperGATAttend(torch.autograd.Function):
         rden = torch.empty_like(m)
         ph, ldh = _lib.mat(hfeat, "hfeat")
         po, ldo = _lib.mat(out, "out")
-        split_ref, split, _scratch = _supergat_split(csr, H, C, 2, dev)
+        split_ref, split, _scratch = _attn_split(csr, H * C + 2 * H, dev)
         seed = records = pos_stats = None
         n_rec = 0
         if train:
@@ -2371,7 +2372,7 @@ class _SuperGATAttend(torch.autograd.Function):
         po, ldo = _lib.mat(out, "out")
         pg, ldg = _lib.mat(gout, "gout")
         pgh, ldgh = _lib.mat(g_h, "g_hfeat")
-        split_ref, split, _scratch = _supergat_split(g.fwd, H, C, 1, dev)
+        split_ref, split, _scratch = _attn_split(g.fwd, H * C + H, dev)
         with _Timed("supergat_bwd_dst"):
             _lib.check(
                 lib.rgbx_supergat_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), ph, ldh, _lib.ptr(al),
@@ -2379,7 +2380,7 @@ class _SuperGATAttend(torch.autograd.Function):
                                               _lib.ptr(nodeq), pgh, ldgh, _lib.ptr(g_ar), N, H, C, float(slope),
                                               _lib.ptr(seed), p_drop, pos_ratio, _lib.ptr(gl), split_ref,
                                               _lib.stream_ptr()), "rgbx_supergat_bwd_dst_f32")
-        split_ref, split, _scratch2 = _supergat_split(g.bwd, H, C, 1, dev)
+        split_ref, split, _scratch2 = _attn_split(g.bwd, H * C + H, dev)
         with _Timed("supergat_bwd_src"):
             _lib.check(
                 lib.rgbx_supergat_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
@@ -2431,11 +2432,6 @@ def supergat_attend(h, att_l, att_r, graph, H, C, slope=0.2, bias=None, training
                                  neg_edge_index, record)
 
 
-def _gatv2_split(csr, width, dev):
-    split, scratch = csr.split_arg(width, dev)
-    return (None if split is None else ctypes.byref(split)), split, scratch
-
-
 def gatv2_random_choices(record, graph, H):
     """The attention-dropout decisions of the training forward that filled `record` (GATv2Conv keeps the record of its
     last forward): {'keep': bool [E', H] in forward CSR slot order (True = kept), 'src' / 'dst': int64 [E'] endpoints of
@@ -2484,7 +2480,7 @@ class _GATv2Attend(torch.autograd.Function):
         pl, ldl = _lib.mat(xl, "xl")
         pr, ldr = _lib.mat(xr, "xr")
         po, ldo = _lib.mat(out, "out")
-        split_ref, split, _scratch = _gatv2_split(csr, H * C + 2 * H, dev)
+        split_ref, split, _scratch = _attn_split(csr, H * C + 2 * H, dev)
         with _Timed("gatv2_fwd"):
             _lib.check(lib.rgbx_gatv2_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pl, ldl, pr, ldr, _lib.ptr(a),
                                               _lib.ptr(b), po, ldo, _lib.ptr(m), _lib.ptr(rden), N, H, C, float(slope),
@@ -2514,7 +2510,7 @@ class _GATv2Attend(torch.autograd.Function):
         pg, ldg = _lib.mat(gout, "gout")
         pgl, ldgl = _lib.mat(g_xl, "g_xl")
         pgr, ldgr = _lib.mat(g_xr, "g_xr")
-        split_ref, split, _scratch = _gatv2_split(g.fwd, F, dev)
+        split_ref, split, _scratch = _attn_split(g.fwd, F, dev)
         n_part = ctypes.c_int64(0)
         _lib.check(lib.rgbx_gatv2_att_partial_floats(N, H, C, split_ref, ctypes.byref(n_part)),
                    "rgbx_gatv2_att_partial_floats")
@@ -2526,7 +2522,7 @@ class _GATv2Attend(torch.autograd.Function):
                                            pgr, ldgr, _lib.ptr(g_att), _lib.ptr(part), n_part.value, N, H, C, slope,
                                            _lib.ptr(seed), p_drop, split_ref, _lib.stream_ptr()),
                 "rgbx_gatv2_bwd_dst_f32")
-        split_ref, split, _scratch2 = _gatv2_split(g.bwd, F, dev)
+        split_ref, split, _scratch2 = _attn_split(g.bwd, F, dev)
         with _Timed("gatv2_bwd_src"):
             _lib.check(
                 lib.rgbx_gatv2_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
@@ -2598,7 +2594,7 @@ class _TransformerAttend(torch.autograd.Function):
         pk, ldk = _lib.mat(k, "k")
         pv, ldv = _lib.mat(v, "v")
         po, ldo = _lib.mat(out, "out")
-        split_ref, _, _scratch = _gatv2_split(csr, H * C + 2 * H, dev)
+        split_ref, _, _scratch = _attn_split(csr, H * C + 2 * H, dev)
         with _Timed("transformer_fwd"):
             _lib.check(lib.rgbx_transformer_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pq, ldq, pk, ldk, pv, ldv,
                                                     po, ldo, _lib.ptr(m), _lib.ptr(rden), N, H, C, float(scale),
@@ -2629,14 +2625,14 @@ class _TransformerAttend(torch.autograd.Function):
         pgq, ldgq = _lib.mat(g_q, "g_q")
         pgk, ldgk = _lib.mat(g_k, "g_k")
         pgv, ldgv = _lib.mat(g_v, "g_v")
-        split_ref, _, _scratch = _gatv2_split(g.fwd, F, dev)
+        split_ref, _, _scratch = _attn_split(g.fwd, F, dev)
         with _Timed("transformer_bwd_dst"):
             _lib.check(
                 lib.rgbx_transformer_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pq, ldq, pk, ldk, pv, ldv,
                                                  _lib.ptr(m), _lib.ptr(rden), po, ldo, pg, ldg, _lib.ptr(nodeq), pgq,
                                                  ldgq, N, H, C, scale, _lib.ptr(seed), p_drop, split_ref,
                                                  _lib.stream_ptr()), "rgbx_transformer_bwd_dst_f32")
-        split_ref, _, _scratch2 = _gatv2_split(g.bwd, 2 * F, dev)
+        split_ref, _, _scratch2 = _attn_split(g.bwd, 2 * F, dev)
         with _Timed("transformer_bwd_src"):
             _lib.check(
                 lib.rgbx_transformer_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
