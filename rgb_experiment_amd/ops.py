@@ -156,6 +156,39 @@ def _rows_padded_readable(t):
     return last * 4 <= t.untyped_storage().nbytes()
 
 
+def _rows_on_grid(t, vec=4):
+    """`t` ([N, F] float32) as a matrix whose rows a kernel may read `vec` floats at a time: unit column stride, the first
+    element on a 4 * vec byte boundary and, above one row, a leading dimension that is a multiple of vec. A view that
+    meets this (a column block of a wider matrix, say) is handed on as it is; anything else is copied once into a fresh
+    allocation. .contiguous() alone does not do: a contiguous view that starts in the middle of an allocation (a one-row
+    block, a slice of a flat buffer) comes back unchanged, misaligned pointer included."""
+    ok = (t.dim() == 2 and (t.size(1) <= 1 or t.stride(1) == 1) and t.data_ptr() % (4 * vec) == 0
+          and (t.size(0) <= 1 or (t.stride(0) % vec == 0 and t.stride(0) >= t.size(1))))
+    return t if ok else t.clone(memory_format=torch.contiguous_format)
+
+
+def _head_vec(C):
+    """The narrowest vector width at which the 64 lanes of a wave still cover one head of C channels (attn_common.h:
+    pick_vec lowers the width to what the operands' pointers and leading dimensions allow, and make_layout refuses a
+    head that would then need more than 64 lanes)."""
+    return 1 if C <= 64 else (2 if C <= 128 else 4)
+
+
+def _width_vec(C):
+    """The widest vector (4, 2 or 1 floats) that divides a width of C channels."""
+    return 4 if C % 4 == 0 else (2 if C % 2 == 0 else 1)
+
+
+def _vec_on_grid(t, n):
+    """A parameter (attention vector, bias) as n contiguous floats on a 16-byte boundary, detached; None stays None. The
+    kernels read these `vec` floats at a time too, and pick_vec counts their pointers: a contiguous slice of a flat
+    parameter buffer keeps its pointer through .contiguous()."""
+    if t is None:
+        return None
+    t = t.detach().reshape(n).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _pad4(x):
     """Feature widths that are no multiple of 4 (C = 7 classes on Cora, 41 on Reddit, 47 on ogbn-products) run on
     zero-padded rows: 16-byte aligned rows take the float4 gather path and straddle fewer 128-byte lines. Measured at
@@ -193,8 +226,7 @@ def edge_dot_raw(csr, a, b, kind="edge_dot"):
     if a.size(1) % 4:
         pad = 4 - a.size(1) % 4
         a, b = torch.nn.functional.pad(a, (0, pad)), torch.nn.functional.pad(b, (0, pad))
-    vec_ok = lambda t: t.stride(-1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
-    a, b = (a if vec_ok(a) else a.contiguous()), (b if vec_ok(b) else b.contiguous())
+    a, b = _rows_on_grid(a), _rows_on_grid(b)
     d = a.size(1)
     g = torch.empty(max(csr.nnz, 1), dtype=torch.float32, device=a.device)
     total = None
@@ -278,12 +310,6 @@ def propagate_sum(x, graph):
 EXTREMUM_MODES = {"max": 0, "min": 1}  # RGBX_EXTREMUM_MAX / RGBX_EXTREMUM_MIN
 
 
-def _vec4_rows(t):
-    """`t` as a matrix the 16-byte row kernels can read: unit column stride, row stride % 4 == 0, 16-byte aligned."""
-    ok = t.stride(-1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.size(1) and t.data_ptr() % 16 == 0
-    return t if ok else t.contiguous()
-
-
 def spmm_extremum_raw(csr, x, mode, want_arg, kind=None):
     """(out [N, d], arg int32 [N, d] or None): out[i, c] = max / min over the slots p of row i of x[col[p], c], arg the
     slot that supplied it (lowest slot on ties; rows without slots: 0 / -1). No autograd; rgbx_spmm_csr_extremum_f32.
@@ -292,7 +318,7 @@ def spmm_extremum_raw(csr, x, mode, want_arg, kind=None):
     if mode not in EXTREMUM_MODES:
         raise ValueError(f"mode must be 'max' or 'min', got {mode!r}")
     _lib.require_device(x)
-    x = _vec4_rows(x)
+    x = _rows_on_grid(x)
     N, d = csr.N, x.size(1)
     if d % 4:
         raise RuntimeError(f"spmm_extremum_raw: width {d} is no multiple of 4 (pad the rows)")
@@ -322,7 +348,7 @@ def extremum_bwd_raw(graph, gout, arg, kind="extremum_bwd"):
     transposed CSR (rgbx_extremum_bwd_f32; fixed summation order, no atomics). No autograd."""
     _lib.require_device(gout, arg)
     csr, t2f = graph.bwd, graph.t2f
-    gout = _vec4_rows(gout)
+    gout = _rows_on_grid(gout)
     d = gout.size(1)
     gx = torch.empty((csr.N, d), dtype=torch.float32, device=gout.device)
     lib = _lib.load()
@@ -416,7 +442,7 @@ def spmm_multi_raw(csr, x, which, want_arg, keep=(), kind="multi_fwd"):
     d = x.size(1)
     if d % 4:
         x = torch.nn.functional.pad(x, (0, 4 - d % 4))
-    x = _vec4_rows(x)
+    x = _rows_on_grid(x)
     N, dp, k, dev = csr.N, x.size(1), len(names), x.device
     buf = torch.empty((N, k * dp), dtype=torch.float32, device=dev)
     dest = {a: buf[:, s * dp:(s + 1) * dp] for s, a in enumerate(names)}
@@ -470,7 +496,7 @@ def multi_bwd_raw(graph, a=None, b=None, x=None, gmax=None, argmax=None, gmin=No
     if d % 4:
         terms = {k: torch.nn.functional.pad(v, (0, 4 - d % 4), value=-1 if k.startswith("arg") else 0)
                  for k, v in terms.items()}
-    terms = {k: _vec4_rows(v) for k, v in terms.items()}
+    terms = {k: _rows_on_grid(v) for k, v in terms.items()}
     csr = graph.bwd
     t2f = graph.t2f if ("gmax" in terms or "gmin" in terms) else None
     dp, dev = (d + 3) // 4 * 4, next(iter(terms.values())).device
@@ -517,7 +543,7 @@ class _PropagateMulti(torch.autograd.Function):
     def backward(ctx, gy):
         x, out, kept_mean, amax, amin = ctx.saved_tensors
         names, g = ctx.names, ctx.graph
-        gy = _vec4_rows(gy)
+        gy = _rows_on_grid(gy)
         dp = gy.size(1) // len(names)
         blk = lambda t, a: t[:, names.index(a) * dp:(names.index(a) + 1) * dp]
         inv_n = g.inv_deg[:g.N, None]  # 1 / max(n, 1)
@@ -1819,7 +1845,7 @@ class _GRUStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, graph, weff, wroot, bias, form):
-        x = x.contiguous()
+        x = _rows_on_grid(x)
         want = any(ctx.needs_input_grad)
         out, z, pre = gru_step_raw(x, graph, weff, wroot, bias, form, want_saved=want)
         if want:
@@ -1830,7 +1856,7 @@ class _GRUStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         x, z, pre, weff, wroot = ctx.saved_tensors
-        dpre, dxd = gru_gate_bwd(pre, x, gout.contiguous())
+        dpre, dxd = gru_gate_bwd(pre, x, _rows_on_grid(gout))
         gw = gb = gwr = gx = None
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[4]:
             gw, gb = gemm_tn(dpre, z, colsum=True)  # dpre is read once for dWeff and dbias
@@ -2287,10 +2313,10 @@ class _SuperGATAttend(torch.autograd.Function):
                 record):
         _lib.require_device(hfeat, att_l, att_r, bias, neg_edge_index)
         lib = _lib.load()
-        hfeat = hfeat.contiguous()
-        b = None if bias is None else bias.detach().reshape(H * C).contiguous()
-        al = att_l.detach().reshape(H, C).contiguous()
-        ar = att_r.detach().reshape(H, C).contiguous()
+        hfeat = _rows_on_grid(hfeat.contiguous(), _head_vec(C))
+        b = _vec_on_grid(bias, H * C)
+        al = _vec_on_grid(att_l, H * C).view(H, C)
+        ar = _vec_on_grid(att_r, H * C).view(H, C)
         csr, N, dev = graph.fwd, graph.fwd.N, hfeat.device
         if hfeat.size(0) != N:
             raise RuntimeError(f"supergat_attend: {hfeat.size(0)} feature rows for a graph of {N} nodes")
@@ -2359,7 +2385,7 @@ class _SuperGATAttend(torch.autograd.Function):
         p_drop, pos_ratio = ctx.rng
         lib = _lib.load()
         N, dev = g.fwd.N, hfeat.device
-        gout = torch.zeros_like(out) if gout is None else gout.contiguous()
+        gout = torch.zeros_like(out) if gout is None else _rows_on_grid(gout.contiguous(), _head_vec(C))
         gl = None
         if train:
             gl = (torch.zeros((), device=dev) if g_loss is None else g_loss.to(torch.float64) / terms).to(
@@ -2458,10 +2484,10 @@ class _GATv2Attend(torch.autograd.Function):
     def forward(ctx, xl, xr, att, graph, H, C, slope, bias, train, p_drop, record, want_grad):
         _lib.require_device(xl, xr, att, bias)
         lib = _lib.load()
-        xl = xl if xl.dim() == 2 and xl.stride(1) == 1 else xl.contiguous()  # column blocks of one product stay views
-        xr = xr if xr.dim() == 2 and xr.stride(1) == 1 else xr.contiguous()
-        b = None if bias is None else bias.detach().reshape(H * C).contiguous()
-        a = att.detach().reshape(H * C).contiguous()
+        # column blocks of one product stay views, where the widest head still fits a wave at the vector width they allow
+        xl, xr = _rows_on_grid(xl, _head_vec(C)), _rows_on_grid(xr, _head_vec(C))
+        b = _vec_on_grid(bias, H * C)
+        a = _vec_on_grid(att, H * C)
         csr, N, dev = graph.fwd, graph.fwd.N, xl.device
         if xl.size(0) != N or xr.size(0) != N or xl.size(1) != H * C or xr.size(1) != H * C:
             raise RuntimeError(f"gatv2_attend: xl {tuple(xl.shape)} / xr {tuple(xr.shape)} for a graph of {N} nodes and "
@@ -2499,7 +2525,7 @@ class _GATv2Attend(torch.autograd.Function):
         lib = _lib.load()
         N, dev = g.fwd.N, xl.device
         F = H * C
-        gout = gout.contiguous()
+        gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
         nodeq = torch.empty((N, H, 2), dtype=torch.float32, device=dev)
         g_xl = torch.empty((N, F), dtype=torch.float32, device=dev)
         g_xr = torch.empty_like(g_xl)
@@ -2574,8 +2600,8 @@ class _TransformerAttend(torch.autograd.Function):
     def forward(ctx, q, k, v, graph, H, C, scale, train, p_drop, record, want_grad):
         _lib.require_device(q, k, v)
         lib = _lib.load()
-        # column blocks of one product stay views
-        q, k, v = (t if t.dim() == 2 and t.stride(1) == 1 else t.contiguous() for t in (q, k, v))
+        # column blocks of one product stay views, where the widest head still fits a wave at the vector width they allow
+        q, k, v = (_rows_on_grid(t, _head_vec(C)) for t in (q, k, v))
         csr, N, dev = graph.fwd, graph.fwd.N, q.device
         if any(t.size(0) != N or t.size(1) != H * C for t in (q, k, v)):
             raise RuntimeError(f"transformer_attend: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} for a "
@@ -2611,7 +2637,7 @@ class _TransformerAttend(torch.autograd.Function):
         lib = _lib.load()
         N, dev = g.fwd.N, q.device
         F = H * C
-        gout = gout.contiguous()
+        gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
         # every row of the four buffers is written by the kernels (rows without slots as zeros)
         nodeq = torch.empty((N, H, 2), dtype=torch.float32, device=dev)
         g_q = torch.empty((N, F), dtype=torch.float32, device=dev)
@@ -2735,12 +2761,13 @@ class _FAConv(torch.autograd.Function):
         _lib.require_device(x, x0, att_l, att_r)
         lib = _lib.load()
         csr, N, dev = graph.fwd, graph.fwd.N, x.device
-        x = x.contiguous()
         C = x.size(1)
+        vec = _width_vec(C)  # faconv.hip fa_vec: the kernels read rows that wide
+        x = _rows_on_grid(x.contiguous(), vec)
         if x.size(0) != N:
             raise RuntimeError(f"faconv: {x.size(0)} feature rows for a graph of {N} nodes")
         use_x0 = x0 is not None and eps != 0.0
-        x0c = x0.contiguous() if use_x0 else None
+        x0c = _rows_on_grid(x0.contiguous(), vec) if use_x0 else None
         att = torch.cat([att_l.detach().reshape(1, C), att_r.detach().reshape(1, C)]).contiguous()  # [2, C]
         seed = None
         if train and p_drop > 0.0:
@@ -2778,7 +2805,7 @@ class _FAConv(torch.autograd.Function):
         g, p_drop = ctx.graph, ctx.p_drop
         lib = _lib.load()
         N, C, dev = x.size(0), x.size(1), x.device
-        gout = gout.contiguous()
+        gout = _rows_on_grid(gout.contiguous(), _width_vec(C))
         g_alr = torch.empty((N, 2), dtype=torch.float32, device=dev)
         px, ldx = _lib.mat(x, "x")
         pg, ldg = _lib.mat(gout, "gout")
@@ -2828,7 +2855,7 @@ def _scores_in_kernel(C):
     """Forming <h_j, att_src> from the gathered row costs log2(lanes per head) cross-lane adds per
     neighbour and saves the a_src[j] cache-line request. Measured at |V|=2M, |E|=60M: 4 lanes per head
     (H=8, C=16) 6.20 -> 5.51 ms; 32 lanes per head (H=1, C=128) 5.71 -> 6.02 ms. Use it up to 8 lanes."""
-    vec = 4 if C % 4 == 0 else (2 if C % 2 == 0 else 1)
+    vec = _width_vec(C)
     lanes = 1
     while lanes * vec < C:
         lanes *= 2

@@ -42,6 +42,8 @@ def first_extremal_slot(rowptr, col, x, mode):
 def ref_extremum(rowptr, col, x, mode):
     """(out [n, d], arg): out[i, c] = x[col[arg[i, c]], c], 0 where arg = -1; differentiable in x through the gather."""
     arg = first_extremal_slot(rowptr, col, x.detach(), mode)
+    if not col.numel():  # a graph without edges: every row is empty
+        return x.new_zeros(arg.shape), arg
     src = col.long()[arg.clamp(min=0)]  # [n, d] source node per (row, channel)
     out = torch.gather(x, 0, src) if x.size(0) else x.new_zeros(arg.shape)
     return torch.where(arg >= 0, out, torch.zeros_like(out)), arg

@@ -4,7 +4,9 @@
 Usage: python tools/fuzz_soak.py first last            (conv layers: run_case)
        python tools/fuzz_soak.py --models first last   (whole models: run_model_case)
        python tools/fuzz_soak.py --fused first last    (rgbx_fused_layer_f32 by option: run_fused_layer_case)
-       python tools/fuzz_soak.py --ref64 seed [seed ...]   (the listed seeds against the oracle computing in float64)"""
+       python tools/fuzz_soak.py --ref64 seed [seed ...]   (the listed seeds against the oracle computing in float64)
+       python tools/fuzz_soak.py --families first last [--kind NAME]   (tests/test_gpu_fuzz_families.py: run_family_case;
+                                  with --kind every seed runs that kind, else a seed's kind is seed % 8; a HIP error ends the run)"""
 import os
 import sys
 import time
@@ -15,9 +17,17 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 
 import test_gpu_fuzz as F
+import test_gpu_fuzz_families as FF
 from conftest import usable_cpus
 
 torch.set_num_threads(min(torch.get_num_threads(), usable_cpus()))  # the oracle half: the cgroup's CPUs, not the host's
+
+
+def is_hip_error(exc):
+    """A failure of the runtime or of a launch (ops check(): 'hipError'; torch: 'HIP error'), not an argument the library
+    refused on the host."""
+    text = str(exc)
+    return isinstance(exc, RuntimeError) and ("hipError" in text or "HIP error" in text or "CUDA error" in text)
 
 
 def main():
@@ -36,7 +46,15 @@ def main():
     which = sys.argv[1] if sys.argv[1].startswith("--") else ""
     if which:
         sys.argv.pop(1)
+    family = None
+    if "--kind" in sys.argv:
+        at = sys.argv.index("--kind")
+        family = sys.argv[at + 1]
+        if which != "--families" or family not in FF.KINDS:
+            sys.exit(f"--kind goes with --families and names one of {FF.KINDS}")
+        del sys.argv[at:at + 2]
     run, kinds = {"--models": (F.run_model_case, F.MODEL_KINDS), "--fused": (F.run_fused_layer_case, ["fused_layer"]),
+                  "--families": (lambda d, seed: FF.run_family_case(d, seed, family), [family] if family else FF.KINDS),
                   "": (F.run_case, F.KINDS)}[which]
     first, last = int(sys.argv[1]), int(sys.argv[2])
     bad, t0, mark = [], time.time(), time.time()
@@ -44,8 +62,11 @@ def main():
         try:
             run(dev, seed)
         except Exception as exc:  # noqa: BLE001 - collected, reported below
-            bad.append((seed, kinds[seed % len(kinds)], repr(exc)[:300]))
+            bad.append((seed, kinds[seed % len(kinds)], repr(exc)[:300 if which != "--families" else 1200]))
             print("FAIL", bad[-1], flush=True)
+            if which == "--families" and is_hip_error(exc):  # the device is in an unknown state: nothing more runs on it
+                print(f"soak [{first}, {seed}]: ended by a HIP error after {seed - first + 1} cases, {len(bad)} failures", flush=True)
+                return 2
         if time.time() - mark > 30:
             mark = time.time()
             print(f"seed {seed} ({seed - first + 1} cases, {len(bad)} failures, {time.time() - t0:.0f} s)", flush=True)
