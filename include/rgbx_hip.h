@@ -373,7 +373,8 @@ typedef struct rgbx_ce_epilogue {
   const uint8_t* mask;     /* [N] or NULL = all rows */
   const float* grad_scale; /* device scalar or NULL */
   double* stats;           /* [3]; [6] with mask_groups == 2 */
-  double* scratch;         /* [(ceil(N / 32) + 64) * 3]; * 6 with mask_groups == 2 */
+  double* scratch;         /* [(ceil(N / 32) + 64) * 3]; * 6 with mask_groups == 2; with `rows` AND grad_scale:
+                            * rgbx_ce_rows_grad_scratch_doubles(N) = (ceil(N / 32) + 64) * 3 + ceil(N / 2) + ceil(N / 8) */
   /* 0 / 1: `mask` is a boolean. 2 (since 4.0.2; statistics only, mask required): bit 0 / bit 1 of mask[i] select row i
    * for statistics set 0 / set 1 — stats[0:3] and stats[3:6] — so that ONE eval forward serves the val and the test
    * metrics of an epoch (itexperiments.py:464-473 runs two identical forwards for them). */
@@ -381,11 +382,20 @@ typedef struct rgbx_ce_epilogue {
   /* Selected rows only (single-GPU callers; all zero = every row as before). A row is SELECTED when its mask bit(s) are
    * set (any of the two with mask_groups == 2) AND its label lies in [0, C): the epilogue's own predicate, which the
    * row list and rgbx_fused_layer_t.col_sel of the backward must restate exactly.
-   *   rows / n_rows: statistics only (grad_scale == NULL, no z_out), an aggregating launch of rgbx_spmm_linear_f32 /
-   *     rgbx_fused_layer_f32: the ascending int32 device list of the selected rows (with mask_groups == 2 those of the
-   *     union of both masks). Tile t aggregates rows[32 t .. 32 t + 31]; ceil(n_rows / 32) tiles, records and workgroups
-   *     instead of ceil(N / 32); unlisted rows are not gathered at all. Statistics as without the list (the nll sum up to
-   *     the order of its fp64 additions). Hub rows of `split` keep working for listed rows.
+   *   rows / n_rows: an aggregating launch of rgbx_spmm_linear_f32 / rgbx_fused_layer_f32 (not DENSE, no w_pos): the
+   *     ascending int32 device list of exactly the selected rows (with mask_groups == 2 those of the union of both masks),
+   *     0 <= n_rows <= N. Tile t aggregates rows[32 t .. 32 t + 31]: ceil(n_rows / 32) tiles and workgroups instead of
+   *     ceil(N / 32); unlisted rows are not gathered at all. Hub rows of `split` keep working for listed rows.
+   *     - statistics only (grad_scale == NULL, no z_out): one record per list tile; statistics as without the list (the
+   *       nll sum up to the order of its fp64 additions).
+   *     - with the loss gradient (grad_scale set, z_out optional, mask_groups != 2): `out`, z_out and the
+   *       statistics are those of skip_unselected BIT FOR BIT. Unlisted rows of `out` and z_out are written as 0: the wave
+   *       that takes list slot i zero-fills rows rows[i-1] + 1 .. rows[i] - 1 (from row 0 for i = 0; the last slot also
+   *       the rows behind it), which needs `out` 16-byte aligned with ldo % 4 == 0. The kernel writes per listed row its
+   *       fp32 nll term and arg-max hit into the tail of `scratch` (N floats, then N bytes, behind the records; never
+   *       read for a row the predicate does not select, so it needs no initialisation), and a small kernel forms the
+   *       ceil(N / 32) tile records of the unlisted form from them in that form's order of additions; `scratch` must
+   *       hold rgbx_ce_rows_grad_scratch_doubles(N) doubles. n_rows == 0 runs as skip_unselected.
    *   skip_unselected != 0: the tiles map to rows as without a list, but a row that is not selected issues no gather;
    *     its z_out row is written as 0 (pre_* not applied), its `out` row (loss gradient) is 0 as always. The gradient,
    *     the statistics and dW = dy^T z are unchanged (the gradient row is 0 there). Not with w_pos (ignored). */
@@ -395,6 +405,8 @@ typedef struct rgbx_ce_epilogue {
 } rgbx_ce_epilogue_t;
 
 int rgbx_spmm_linear_supported(int64_t K, int64_t Nout, int has_root);
+/* Doubles of rgbx_ce_epilogue_t.scratch a loss-gradient launch over a row list needs for N rows. */
+int rgbx_ce_rows_grad_scratch_doubles(int64_t N, int64_t* count);
 int rgbx_spmm_linear_stats_workspace_bytes(int64_t N, int64_t Nout, size_t* bytes);
 int rgbx_spmm_linear_f32(const int32_t* rowptr, const int32_t* col, const float* w, const float* rs,
                          const float* x, int64_t ldx, const float* wt, const float* x_root, int64_t ldr,

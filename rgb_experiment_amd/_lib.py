@@ -88,6 +88,7 @@ SIGNATURES = {
     "rgbx_spmm_csr_short_rows_supported": [_I64],
     "rgbx_spmm_csr_short_rows_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P],
     "rgbx_spmm_linear_supported": [_I64, _I64, _I],
+    "rgbx_ce_rows_grad_scratch_doubles": [_I64, ctypes.POINTER(ctypes.c_int64)],
     "rgbx_spmm_linear_stats_workspace_bytes": [_I64, _I64, ctypes.POINTER(ctypes.c_size_t)],
     "rgbx_spmm_linear_f32": [_P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P,
                              ctypes.c_size_t, _P, _I64, _I64, _I64, _P, _P],

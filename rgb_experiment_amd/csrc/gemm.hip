@@ -31,7 +31,8 @@
 //  - A_ROWS (rgbx_gemm_tn_rows_f32): only the rows of an ascending list are multiplied, for operands whose other rows
 //    are all zero (the loss gradient outside the rows the loss selects). Slab s takes the list entries inside its own
 //    row range [s * slab, (s + 1) * slab), in list order: the non-zero products meet the accumulators in the order of
-//    the full product, a skipped row only added zeros.
+//    the full product, a skipped row only added zeros. The list entries of a tile are fetched one tile ahead of its rows
+//    (10 more VGPRs; the workgroups per CU stay 3, and 4 for the 64-row tile).
 #include "rgbx_common.h"
 
 namespace rgbx {
@@ -120,18 +121,28 @@ __device__ __forceinline__ void put_tile_bn(float* __restrict__ lds, const float
   }
 }
 
-// A_ROWS: tile row r is row rows[j0 + r] of src; list entries >= j_end are zero-filled
+// A_ROWS: tile row r is row rows[j0 + r] of src; list entries >= j_end are zero-filled. A tile is reached through two
+// dependent loads (list entry, then row), so the entries travel ONE TILE AHEAD of the rows: fetch_row_ids reads the
+// entries this thread's float4s of a [KT x W] tile belong to (-1 past j_end), fetch_tile_rows starts the row loads from
+// entries that are already in registers.
 template <int W>
-__device__ __forceinline__ void fetch_tile_rows(float4 (&regs)[KT * (W / 4) / 256], const float* __restrict__ src,
-                                                int64_t ld, const int32_t* __restrict__ rows, int64_t j0, int64_t j_end,
-                                                int c0, int ncols) {
+__device__ __forceinline__ void fetch_row_ids(int32_t (&ids)[KT * (W / 4) / 256], const int32_t* __restrict__ rows,
+                                              int64_t j0, int64_t j_end) {
 #pragma unroll
   for (int p = 0; p < KT * (W / 4) / 256; ++p) {
-    const int idx = p * 256 + threadIdx.x;
-    const int r = idx / (W / 4), c = (idx % (W / 4)) * 4;
-    const int64_t j = j0 + r;
+    const int64_t j = j0 + (p * 256 + (int)threadIdx.x) / (W / 4);
+    ids[p] = j < j_end ? rows[j] : -1;
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void fetch_tile_rows(float4 (&regs)[KT * (W / 4) / 256], const float* __restrict__ src,
+                                                int64_t ld, const int32_t (&ids)[KT * (W / 4) / 256], int c0, int ncols) {
+#pragma unroll
+  for (int p = 0; p < KT * (W / 4) / 256; ++p) {
+    const int c = ((p * 256 + (int)threadIdx.x) % (W / 4)) * 4;
     regs[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < j_end && c0 + c < ncols) regs[p] = *reinterpret_cast<const float4*>(src + (int64_t)rows[j] * ld + c0 + c);
+    if (ids[p] >= 0 && c0 + c < ncols) regs[p] = *reinterpret_cast<const float4*>(src + (int64_t)ids[p] * ld + c0 + c);
   }
 }
 
@@ -223,16 +234,23 @@ gemm_tn_partial_kernel(const float* __restrict__ A, int64_t lda, const float* __
     const int64_t j_begin = lower_bound_rows(ex.rows, ex.n_rows, k_begin);
     const int64_t j_end = lower_bound_rows(ex.rows, ex.n_rows, k_end);
     float4 ra[KT * (MT / 4) / 256], rb[KT * 32 / 256];
-    fetch_tile_rows<MT>(ra, A, lda, ex.rows, j_begin, j_end, m0, M);
-    fetch_tile_rows<128>(rb, B, ldb, ex.rows, j_begin, j_end, n0, N);
+    int32_t ia[KT * (MT / 4) / 256], ib[KT * 32 / 256];  // list entries of the tile whose rows are fetched NEXT
+    fetch_row_ids<MT>(ia, ex.rows, j_begin, j_end);
+    fetch_row_ids<128>(ib, ex.rows, j_begin, j_end);
+    fetch_tile_rows<MT>(ra, A, lda, ia, m0, M);
+    fetch_tile_rows<128>(rb, B, ldb, ib, n0, N);
+    fetch_row_ids<MT>(ia, ex.rows, j_begin + KT, j_end);
+    fetch_row_ids<128>(ib, ex.rows, j_begin + KT, j_end);
     for (int64_t j0 = j_begin; j0 < j_end; j0 += KT) {
       __syncthreads();
       put_tile<MT>(la, ra);
       put_tile<128>(lb, rb);
       __syncthreads();
-      if (j0 + KT < j_end) {
-        fetch_tile_rows<MT>(ra, A, lda, ex.rows, j0 + KT, j_end, m0, M);
-        fetch_tile_rows<128>(rb, B, ldb, ex.rows, j0 + KT, j_end, n0, N);
+      if (j0 + KT < j_end) {  // the rows of tile j0 + KT from entries fetched a tile ago, then the entries of j0 + 2 KT
+        fetch_tile_rows<MT>(ra, A, lda, ia, m0, M);
+        fetch_tile_rows<128>(rb, B, ldb, ib, n0, N);
+        fetch_row_ids<MT>(ia, ex.rows, j0 + 2 * KT, j_end);
+        fetch_row_ids<128>(ib, ex.rows, j0 + 2 * KT, j_end);
       }
       consume();
     }

@@ -86,11 +86,16 @@ struct FusedArgs {
   float* zpos_out;
   const float* zlong_pos;
   // loss epilogue over selected rows only (rgbx_ce_epilogue_t.rows / skip_unselected; single-GPU callers):
-  // ce_rows: tile t aggregates rows ce_rows[32 t .. 32 t + 31] of an ascending list of ce_n_rows selected rows (statistics
-  // only); ce_skip: a row the epilogue does not select issues no gather, its aggregate (zt, z_out) is 0
+  // ce_rows: tile t aggregates rows ce_rows[32 t .. 32 t + 31] of an ascending list of ce_n_rows selected rows;
+  // ce_skip: a row the epilogue does not select issues no gather, its aggregate (zt, z_out) is 0
   const int* ce_rows;
   int ce_n_rows;
   int ce_skip;
+  // the loss GRADIENT over the row list (ce_rows with ce_scale; both set or both NULL): the epilogue writes no tile record
+  // but, per listed row, its fp32 nll term and arg-max hit; ce_row_records_kernel forms the ceil(N / 32) records of the
+  // unlisted form from them. The rows between two list entries are zero-filled (out, z_out) by the wave of the later one.
+  float* ce_term;    // [N]
+  uint8_t* ce_hit;   // [N]
   // column selection (rgbx_fused_layer_t.col_sel): a slot whose column is not selected is not gathered and adds 0
   const uint8_t* col_sel;
 };
@@ -277,7 +282,7 @@ __device__ __forceinline__ int ce_select(const FusedArgs& A, int row, int* t) {
   return *t >= 0 ? bits : 0;
 }
 
-// Row of slot r of the workgroup's tile: row_base + r, or with a row list (loss epilogue, statistics only) entry
+// Row of slot r of the workgroup's tile: row_base + r, or with a row list (loss epilogue) entry
 // row_base + r of it; A.N (= no row) past the end of the list or for an entry outside [0, N)
 template <bool CE>
 __device__ __forceinline__ int tile_row(const FusedArgs& A, int row_base, int r) {
@@ -289,6 +294,37 @@ __device__ __forceinline__ int tile_row(const FusedArgs& A, int row_base, int r)
     }
   }
   return row_base + r;
+}
+
+// Rows [lo, hi) of a row-major matrix of 4 q floats per row (q <= 64) := 0, by the whole wave in non-temporal 16-byte
+// stores: kWave / q rows per pass
+__device__ __forceinline__ void zero_rows(float* __restrict__ base, int64_t ld, int q, int lo, int hi, int lane) {
+  const int per = kWave / q, sub = lane / q;
+  const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+  if (sub < per)
+    for (int r = lo + sub; r < hi; r += per) nt_store4(base + (int64_t)r * ld + (lane - sub * q) * 4, zero);
+}
+
+// The loss gradient over the row list: no tile owns the rows the list leaves out, and their `out` (gradient) and z_out
+// rows must be 0 as ce_skip leaves them. The list is ascending, so the wave that takes list slot i fills the gap in front
+// of its row, rows[i - 1] + 1 .. rows[i] - 1 (from row 0 for i = 0), and the wave of the last slot also the rows behind
+// it: every unlisted row exactly once, no state, the bytes ce_skip writes. Bounds: 0 <= lo and hi <= N whatever the list
+// holds.
+__device__ __forceinline__ void ce_fill_gaps(const FusedArgs& A, int i, int row, int lane) {
+  if (i >= A.ce_n_rows || row >= A.N) return;  // wave-uniform; an entry outside [0, N) fills nothing
+  int lo = 0;
+  if (i > 0) {
+    const int prev = A.ce_rows[i - 1];
+    lo = (unsigned)prev < (unsigned)A.N ? prev + 1 : A.N;
+  }
+  if (lo < row) {  // row <= N (tile_row)
+    zero_rows(A.out, A.ldo, A.Nout >> 2, lo, row, lane);
+    if (A.z_out) zero_rows(A.z_out, A.ldz, A.K >> 2, lo, row, lane);
+  }
+  if (i == A.ce_n_rows - 1 && row + 1 < A.N) {
+    zero_rows(A.out, A.ldo, A.Nout >> 2, row + 1, A.N, lane);
+    if (A.z_out) zero_rows(A.z_out, A.ldz, A.K >> 2, row + 1, A.N, lane);
+  }
 }
 
 // Cross-entropy of the finished 32 x Nout tile (Nout <= 128), see FusedArgs::ce_part. The four waves park their 32 x 32
@@ -335,7 +371,12 @@ __device__ __forceinline__ void ce_epilogue(const FusedArgs& A, const f32x16& ac
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off);
     const float lse = best + logf(se);
-    if (t >= 0) {
+    if (t >= 0 && A.ce_term) {  // gradient over the row list: the record is formed by ce_row_records_kernel
+      if (lane == 0) {
+        A.ce_term[row] = lse - ot[rl * ldq + t];
+        A.ce_hit[row] = arg == t ? 1 : 0;
+      }
+    } else if (t >= 0) {
       const double term = (double)(lse - ot[rl * ldq + t]);
       const int h = arg == t ? 1 : 0;
       if (bits & 1) {
@@ -355,6 +396,7 @@ __device__ __forceinline__ void ce_epilogue(const FusedArgs& A, const f32x16& ac
       if (c1) nt_store1(&orow[lane + 64], t >= 0 ? sc * (expf(v1 - lse) - (lane + 64 == t ? 1.f : 0.f)) : 0.f);
     }
   }
+  if (A.ce_term) return;  // uniform over the workgroup
   __shared__ double cew[4][6];
   if (lane == 0) {
     cew[wave][0] = nll;
@@ -405,6 +447,38 @@ ce_tiles_finish_kernel(const double* __restrict__ part2, int n, double* __restri
   for (int k = 0; k < W; ++k) {
     const double v = block_tree_sum((int)threadIdx.x < n ? part2[threadIdx.x * W + k] : 0.0, sh);
     if (threadIdx.x == 0) stats[k] = v;
+  }
+}
+
+// The tile records of a loss-gradient launch over the row list, formed as ce_epilogue forms them WITHOUT a list, so that
+// reduce_ce_tiles adds the same ceil(N / 32) records in the same structure and the statistics keep every bit: record b
+// covers rows 32 b .. 32 b + 31; its four "wave" sums take 8 rows each in row order from 0.0 (skipping rows ce_select does
+// not select: their scratch is never read and need not be initialised), the record is (w0 + w1) + (w2 + w3). Four
+// adjacent threads per record, one per wave sum.
+__global__ void __launch_bounds__(256) ce_row_records_kernel(const FusedArgs A, int tiles) {
+  const int tid = blockIdx.x * 256 + threadIdx.x;
+  const int b = tid >> 2, w = tid & 3;
+  double v[3] = {0.0, 0.0, 0.0};
+  if (b < tiles) {
+    double nll = 0.0;
+    int cnt = 0, hit = 0;
+    for (int rr = 0; rr < TM / 4; ++rr) {
+      const int row = b * TM + w * (TM / 4) + rr;
+      if (row >= A.N) break;
+      int t;
+      if (ce_select(A, row, &t)) {
+        nll += (double)A.ce_term[row];
+        cnt += 1;
+        hit += A.ce_hit[row];
+      }
+    }
+    v[0] = nll, v[1] = (double)cnt, v[2] = (double)hit;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double pair = v[k] + __shfl_xor(v[k], 1);  // lanes w = 0, 1: w0 + w1; w = 2, 3: w2 + w3
+    const double rec = pair + __shfl_xor(pair, 2);   // lane w = 0: (w0 + w1) + (w2 + w3)
+    if (w == 0 && b < tiles) A.ce_part[(int64_t)b * 3 + k] = rec;
   }
 }
 
@@ -466,6 +540,9 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
     lr = __builtin_amdgcn_readfirstlane(lr);
     if (lr >= TM) break;
     const int row = tile_row<CE>(A, row_base, lr);
+    if constexpr (CE && !POS && !DENSE) {  // before the gather starts: nothing of it is live yet
+      if (A.ce_term) ce_fill_gaps(A, row_base + lr, row, lane);
+    }
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     float accp[4] = {0.f, 0.f, 0.f, 0.f};  // POS only
     // a row the loss epilogue does not select (the one predicate, ce_select) is not gathered: its aggregate is 0 — also
@@ -1057,14 +1134,22 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
     if (ce->grad_scale && !L.out) return fail(RGBX_E_ARG, "spmm_linear: the loss gradient needs `out`");
     if (ce->mask_groups < 0 || ce->mask_groups > 2)
       return fail(RGBX_E_ARG, "spmm_linear: mask_groups must be 0, 1 or 2 (got %d)", (int)ce->mask_groups);
+    if (ce->mask_groups == 2 && ce->grad_scale && (ce->rows || ce->n_rows))
+      return fail(RGBX_E_ARG, "spmm_linear: a row list with the loss gradient excludes two statistics sets (mask_groups == 2)");
     if (ce->mask_groups == 2 && (ce->grad_scale || !ce->mask))
       return fail(RGBX_E_ARG, "spmm_linear: two statistics sets (mask_groups == 2) need a mask and no loss gradient");
     if (ce->rows || ce->n_rows) {
       if (!ce->rows || ce->n_rows < 0 || ce->n_rows > N)
         return fail(RGBX_E_ARG, "spmm_linear: row list of %lld rows for N = %lld", (long long)ce->n_rows, (long long)N);
-      if (ce->grad_scale || dense || L.z_out || L.w_pos)
-        return fail(RGBX_E_ARG, "spmm_linear: a row list needs an aggregating statistics-only launch (no loss gradient, "
-                                "no z_out, no w_pos)");
+      if (dense || L.w_pos)
+        return fail(RGBX_E_ARG, "spmm_linear: a row list needs an aggregating launch (rowptr set) without w_pos");
+      if (!ce->grad_scale && L.z_out)
+        return fail(RGBX_E_ARG, "spmm_linear: a row list with z_out needs the loss gradient (grad_scale): the "
+                                "statistics-only form leaves unlisted rows unwritten");
+      // the gaps between listed rows are zero-filled in 16-byte stores
+      if (ce->grad_scale && (!aligned16(L.out) || L.ldo % 4))
+        return fail(RGBX_E_ALIGN, "spmm_linear: a row list with the loss gradient needs `out` 16-byte aligned with "
+                                  "ldo %% 4 == 0");
     }
   }
   if (L.col_sel && (dense || ce || L.w_pos || L.out_blk || (L.x_root && L.xr_blk_cols > 0)))
@@ -1151,8 +1236,21 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
     A.ce_rows = ce->rows;
     A.ce_n_rows = (int)ce->n_rows;
     A.ce_skip = ce->skip_unselected ? 1 : 0;
+    if (ce->rows && ce->grad_scale) {
+      if (ce->n_rows == 0) {  // nothing selected: every row is a gap — the in-place skip writes exactly those zeros
+        A.ce_rows = nullptr;
+        A.ce_skip = 1;
+      } else {  // per-row scratch behind the records and the gather sums (header: rgbx_ce_rows_grad_scratch_doubles)
+        double* behind = ce->scratch + (size_t)(cdiv(N, TM) + kCeGather) * 3;
+        A.ce_term = reinterpret_cast<float*>(behind);
+        A.ce_hit = reinterpret_cast<uint8_t*>(behind + cdiv(N, 2));
+        A.ce_skip = 0;
+      }
+    }
   }
-  const int64_t tiles = A.ce_rows ? cdiv(A.ce_n_rows, TM) : cdiv(N, TM);  // tile records of the loss epilogue
+  // tile records of the loss epilogue: the statistics-only list form writes one per list tile, every other form one per
+  // 32 rows (the gradient list form through ce_row_records_kernel)
+  const int64_t tiles = A.ce_rows && !A.ce_term ? cdiv(A.ce_n_rows, TM) : cdiv(N, TM);
   const int lanes = (int)(K / 4);
   int rc;
   if (dense) {  // the lane grouping of the gather is irrelevant: one instantiation per unrolled width
@@ -1174,11 +1272,22 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
   else if (lanes <= 32) rc = launch<32, 0>(A, s);
   else rc = launch<64, 0>(A, s);
   if (rc) return rc;
+  if (A.ce_term) {
+    ce_row_records_kernel<<<(int)cdiv(tiles * 4, 256), 256, 0, s>>>(A, (int)tiles);
+    RGBX_CHECK_LAUNCH("ce_row_records_kernel");
+  }
   if (ce) {
     if (int rc2 = reduce_ce_tiles(ce->scratch, (int)tiles, ce->stats, ce->mask_groups == 2 ? 6 : 3, s)) return rc2;
   }
   if (!L.out_colsums) return RGBX_OK;
   return reduce_tile_stats(stats_part, (int)cdiv(N, TM), (int)(2 * Nout), stats_part2, L.out_colsums, N, s);
+}
+
+extern "C" int rgbx_ce_rows_grad_scratch_doubles(int64_t N, int64_t* count) {
+  if (!count || N < 0) return fail(RGBX_E_ARG, "ce_rows_grad_scratch_doubles: bad argument");
+  // tile records and gather sums as always, then N floats (nll terms) and N bytes (arg-max hits)
+  *count = (cdiv(N, TM) + kCeGather) * 3 + cdiv(N, 2) + cdiv(N, 8);
+  return RGBX_OK;
 }
 
 extern "C" int rgbx_spmm_linear_stats_workspace_bytes(int64_t N, int64_t Nout, size_t* bytes) {

@@ -884,8 +884,9 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
     `w_pos` (second weight vector over the same slots; implies want_z): z_pos = sum_p w_pos_p x[col_p] is stored as well
     and the return value is (out, (z, z_pos), colsums or stats).
     `select_rows` (one-GPU callers, with `ce`): only the rows the loss selects are gathered — a statistics-only launch
-    runs over the cached list of those rows (selected_rows), a loss-gradient launch skips the others in place (their z
-    rows are 0, their gradient rows 0 as always); see rgbx_ce_epilogue_t.rows / skip_unselected.
+    runs over the cached list of those rows (selected_rows), and so does a loss-gradient launch (CE_GRAD_ROW_LIST; it
+    skips the others in place where there is no list): the z and gradient rows of the others are 0 either way; see
+    rgbx_ce_epilogue_t.rows / skip_unselected.
     `col_sel` (uint8 [n_src] or None): slots whose column has a 0 there are not gathered (rgbx_fused_layer_t.col_sel).
     Returns (out, z, colsums or stats)."""
     _lib.require_device(x, wt, bias, x_root, wt_root, out_blocked, col_sel)
@@ -956,17 +957,30 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
         y = y.contiguous()
         mask = None if mask is None else mask.contiguous()
         ce_stats = torch.empty(3 * groups, dtype=torch.float64, device=x.device)
-        ce_scratch = torch.empty(3 * groups * ((N + 31) // 32 + 64), dtype=torch.float64, device=x.device)
+        scratch_doubles = 3 * groups * ((N + 31) // 32 + 64)
+        rows = None
+        if select_rows and not dense and w_pos is None and mask is not None:
+            if grad_scale is not None:
+                # the gradient form tiles the list too (CE_GRAD_ROW_LIST), where the 16-byte zero fill of the unlisted
+                # rows applies; without a list (inside a capture before it exists) or with an empty one: the in-place skip
+                if CE_GRAD_ROW_LIST and (out is None or (out.data_ptr() % 16 == 0 and (N == 1 or out.stride(0) % 4 == 0))):
+                    rows = selected_rows(y, mask, n_out)
+                    if rows is not None and rows.numel() == 0:
+                        rows = None
+            elif not want_z and z is None:
+                rows = selected_rows(y, mask, n_out)  # None: inside a graph capture before the list exists (all tiles)
+        if rows is not None and grad_scale is not None:
+            count = ctypes.c_int64(0)
+            _lib.check(lib.rgbx_ce_rows_grad_scratch_doubles(N, ctypes.byref(count)), "rgbx_ce_rows_grad_scratch_doubles")
+            scratch_doubles = count.value
+        ce_scratch = torch.empty(scratch_doubles, dtype=torch.float64, device=x.device)
         ce_arg = _lib.CeEpilogue(_lib.ptr(y), _lib.ptr(mask), _lib.ptr(grad_scale), _lib.ptr(ce_stats),
                                  _lib.ptr(ce_scratch), groups)
-        if select_rows and not dense and w_pos is None:
-            if grad_scale is not None:
-                ce_arg.skip_unselected = 1
-            elif not want_z and z is None and mask is not None:
-                rows = selected_rows(y, mask, n_out)
-                if rows is not None:  # None: inside a graph capture before the list exists (all tiles, as before)
-                    ce_arg.rows, ce_arg.n_rows = rows.data_ptr(), rows.numel()
-                    keep.append(rows)
+        if rows is not None:
+            ce_arg.rows, ce_arg.n_rows = rows.data_ptr(), rows.numel()
+            keep.append(rows)
+        elif select_rows and not dense and w_pos is None and grad_scale is not None:
+            ce_arg.skip_unselected = 1
         keep += [y, mask, ce_scratch, ce_arg]
         L.ce = ctypes.addressof(ce_arg)
         want_out = grad_scale is not None  # statistics only: the logits are never written
@@ -1134,6 +1148,10 @@ def fold_bn_linear(weight, bias=None, bias2=None, root_weight=None, bn=None):
 #  - the last conv's weight gradient runs over the rows the loss selects (gemm_tn_rows).
 # Either way every result is the same, bit for bit.
 FUSE_DENSE_BACKWARD = True
+# The training form of the last layer (loss gradient, select_rows) tiles the list of the selected rows instead of keeping
+# every tile and skipping the deselected rows in place (rgbx_ce_epilogue_t.rows with grad_scale): the same gradient,
+# aggregate and statistics, bit for bit. False = the in-place skip (skip_unselected), for tests and A/B runs.
+CE_GRAD_ROW_LIST = True
 
 BN_HANDOVER = "_rgbx_bn_handover"  # attribute of a conv output whose node owns the backward of the BatchNorm behind it
 
