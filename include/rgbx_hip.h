@@ -29,6 +29,7 @@
  *   rgbx_supergat_*       SuperGATConv ('MX' attention, attention loss, negative sampling; models/supergat.py) [PyG].
  *   rgbx_gatv2_*          GATv2Conv (dynamic attention) [PyG]; not in the reference's zoo, shaped like models/gat.py.
  *   rgbx_transformer_*    TransformerConv (scaled dot-product attention) [PyG]; not in the reference's zoo.
+ *   rgbx_resgated_*       ResGatedGraphConv (per-channel sigmoid gate) [PyG]; not in the reference's zoo.
  *   rgbx_gemm_tn_f32      dW = dY^T X of the nn.Linear / conv.lin layers under loss.backward()
  *                         (itexperiments.py:439; layers at models/gcn.py:18-21, appnp_stack.py:19-20).
  *   rgbx_bn_* / rgbx_affine_cols_f32
@@ -837,6 +838,42 @@ int rgbx_transformer_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, 
                                  const float* nodeq, const float* gout, int64_t ldg, float* g_k, int64_t ldgk,
                                  float* g_v, int64_t ldgv, int64_t N, int H, int C, float scale, const uint32_t* seed,
                                  float p_drop, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* ---- ResGatedGraphConv: per-channel sigmoid gate over the in-edges ------------------------------------------------- */
+
+/* For an edge j -> i (p = its slot in the target-grouped CSR), with k, q, v [N, C] (each with its own pointer and
+ * leading dimension; column blocks of one wider matrix are taken as they are):
+ *   s_p      = sigmoid(k[i,:] + q[j,:])           (a vector per edge: one gate per channel)
+ *   out[i,:] = sum_p s_p (.) v[j,:]
+ * (ResGatedGraphConv.forward / message [PyG]; Bresson & Laurent, "Residual Gated Graph ConvNets". The reference's zoo
+ * has no ResGatedGraphConv.) No softmax and no normaliser: nothing is saved for the backward, and the two backward
+ * passes are independent of each other (each recomputes the gate from k and q). The sigmoid is evaluated through
+ * exp(-|z|): no intermediate overflows, a saturated gate is exactly 0 or 1. The edges are taken as they are
+ * (RGBX_LOOPS_KEEP): a row WITHOUT slots stores exact zeros in `out` and g_k; a source without out-edges gets zero g_q
+ * and g_v rows. Every output row is written. No entry point uses float atomics: two runs are bit-identical. */
+
+/* 1 if the kernels take C channels (the widths of rgbx_transformer_supported(1, C)), else 0. */
+int rgbx_resgated_supported(int C);
+
+/* Forward over the target-grouped CSR. `split`: hub rows as in rgbx_gatv2_fwd_f32; split->partial holds n_chunks * C
+ * floats, added in chunk order. */
+int rgbx_resgated_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* k, int64_t ldk, const float* q,
+                          int64_t ldq, const float* v, int64_t ldv, float* out, int64_t ldo, int64_t N, int C,
+                          const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward, target side, over the forward CSR:  g_k[i,:] = gout[i,:] (.) sum_p v[j,:] (.) s_p (1 - s_p).
+ * split->partial holds n_chunks * C floats. */
+int rgbx_resgated_bwd_dst_f32(const int32_t* rowptr, const int32_t* col, const float* k, int64_t ldk, const float* q,
+                              int64_t ldq, const float* v, int64_t ldv, const float* gout, int64_t ldg, float* g_k,
+                              int64_t ldgk, int64_t N, int C, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward, source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i), in any order with the target
+ * side:   g_q[j,:] = v[j,:] (.) sum_p gout[i,:] (.) s_p (1 - s_p),   g_v[j,:] = sum_p s_p (.) gout[i,:].
+ * split->partial holds n_chunks * 2*C floats (g_q | g_v per chunk). */
+int rgbx_resgated_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* k, int64_t ldk, const float* q,
+                              int64_t ldq, const float* v, int64_t ldv, const float* gout, int64_t ldg, float* g_q,
+                              int64_t ldgq, float* g_v, int64_t ldgv, int64_t N, int C, const rgbx_row_split_t* split,
+                              rgbx_stream_t stream);
 
 /* ---- dense layers on the MFMA units -------------------------------------------------------- */
 

@@ -140,6 +140,11 @@ SIGNATURES = {
                                      _I64, _I, _I, _F, _P, _F, _P, _P],
     "rgbx_transformer_bwd_src_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _I64,
                                      _I, _I, _F, _P, _F, _P, _P],
+    "rgbx_resgated_supported": [_I],
+    "rgbx_resgated_fwd_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
+    "rgbx_resgated_bwd_dst_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
+    "rgbx_resgated_bwd_src_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P,
+                                  _P],
     "rgbx_gemm_tn_workspace_bytes": [_I64, _I64, _I64, ctypes.POINTER(ctypes.c_size_t)],
     "rgbx_gemm_tn_f32": [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _F, _P, ctypes.c_size_t, _P],
     "rgbx_gemm_tn_bn_bwd_f32": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _F, _P,

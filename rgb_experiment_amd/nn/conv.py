@@ -993,6 +993,71 @@ class TransformerConv(nn.Module):
         return out
 
 
+class ResGatedGraphConv(nn.Module):
+    """The residual gated graph convolution [PyG ResGatedGraphConv; Bresson & Laurent, "Residual Gated Graph ConvNets";
+    GatedGCN in the benchmarking literature]: k = lin_key(x), q = lin_query(x), v = lin_value(x), all [N, C]; for an
+    edge j -> i the message is sigmoid(k_i + q_j) * v_j, elementwise over the C channels — a gate per channel, not a
+    scalar per head, and no normalisation; summed over the in-edges of i, the edges AS GIVEN (self-loops stay,
+    duplicates count twice, a node without in-edges aggregates zeros); + lin_skip(x) with root_weight; + bias.
+    Parameter names are PyG's (lin_key / lin_query / lin_value with bias, lin_skip without, present only with
+    root_weight; `bias` only with bias). The aggregation runs in the rgbx_resgated_* kernels (ops.resgated_aggregate);
+    the skip and bias adds are dense per-node work.
+
+    Out of scope: edge features (`edge_dim`), activations other than the sigmoid default (`act`), the node-partitioned
+    (distributed) route, and any kernel tuning beyond what the first measurement showed to be needed."""
+
+    def __init__(self, in_channels, out_channels, act=None, edge_dim=None, root_weight=True, bias=True):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("ResGatedGraphConv: edge features (edge_dim) are not built")
+        if not (act is None or act is torch.sigmoid or act is torch.nn.functional.sigmoid or isinstance(act, nn.Sigmoid)):
+            raise NotImplementedError("ResGatedGraphConv: act other than the sigmoid default is not built (the gate's "
+                                      "sigmoid lives in the kernels)")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.edge_dim, self.root_weight = edge_dim, root_weight
+        self.lin_key = nn.Linear(in_channels, out_channels)
+        self.lin_query = nn.Linear(in_channels, out_channels)
+        self.lin_value = nn.Linear(in_channels, out_channels)
+        self.lin_skip = nn.Linear(in_channels, out_channels, bias=False) if root_weight else None
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip):
+            if lin is not None:
+                lin.reset_parameters()  # the Linear's own default, as in PyG's layer
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def forward(self, x, edge_index):
+        _lib.require_device(x)
+        C = self.out_channels
+        Cp = GATConv.kernel_channels(C)  # other widths: zero weight rows and bias entries
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        pad = torch.nn.functional.pad
+        # one product over [W_k; W_q; W_v; W_skip]: the four projections are its column blocks, q and v of a source side
+        # by side. A padded channel has k = q = v = 0: sigmoid(0) * 0 = 0 forward and a zero gradient.
+        blocks = [(lin.weight, lin.bias) if Cp == C else (pad(lin.weight, (0, 0, 0, Cp - C)), pad(lin.bias, (0, Cp - C)))
+                  for lin in (self.lin_key, self.lin_query, self.lin_value)]
+        if self.root_weight:
+            # the skip block is padded to a multiple of 4 columns with zero weight rows: the product's leading dimension
+            # stays a multiple of 4, and with it the 16-byte alignment the wide widths (C > 128: 4 floats per lane) need
+            blocks.append((pad(self.lin_skip.weight, (0, 0, 0, -C % 4)),
+                           torch.zeros(C + -C % 4, dtype=x.dtype, device=x.device)))
+        h = ops.linear(x, torch.cat([w for w, _ in blocks]), torch.cat([b for _, b in blocks]))
+        out = ops.resgated_aggregate(h[:, :Cp], h[:, Cp:2 * Cp], h[:, 2 * Cp:3 * Cp], graph)
+        if Cp != C:
+            out = out[:, :C]
+        if self.root_weight:
+            out = out + h[:, 3 * Cp:3 * Cp + C]
+        if self.bias is not None:
+            out = out + self.bias
+        return out
+
+
 class FAConv(nn.Module):
     """FAGCN's layer [PyG FAConv; reference models/fagcn.py]: for an edge j -> i of the GCN-normalised graph (self-loops
     removed then re-added, w_ij = 1/sqrt(d_i d_j)), a_ij = tanh(<x_j, att_l> + <x_i, att_r>) — signed, no softmax —

@@ -2712,6 +2712,90 @@ def transformer_attend(q, k, v, graph, H, C, scale, training=False, p_drop=0.0, 
                                     want_grad)
 
 
+class _ResGatedAggregate(torch.autograd.Function):
+    """One ResGatedGraphConv aggregation as a single autograd node: fused per-channel gate sigmoid(k_i + q_j) and sum
+    of the gated value rows; backward = target-side pass (g_k) and source-side pass (g_q, g_v), independent of each
+    other and run only where a gradient is asked for. Saves k, q, v and nothing else: no output, no per-node state,
+    nothing per edge (both passes recompute the gate)."""
+
+    @staticmethod
+    def forward(ctx, k, q, v, graph):
+        _lib.require_device(k, q, v)
+        lib = _lib.load()
+        C = k.size(1)
+        # column blocks of one product stay views, where the row still fits a wave at the vector width they allow
+        k, q, v = (_rows_on_grid(t, _head_vec(C)) for t in (k, q, v))
+        csr, N, dev = graph.fwd, graph.fwd.N, k.device
+        if any(t.dim() != 2 or t.size(0) != N or t.size(1) != C for t in (k, q, v)):
+            raise RuntimeError(f"resgated_aggregate: k {tuple(k.shape)} / q {tuple(q.shape)} / v {tuple(v.shape)} for a "
+                               f"graph of {N} nodes")
+        out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: zeros)
+        pk, ldk = _lib.mat(k, "k")
+        pq, ldq = _lib.mat(q, "q")
+        pv, ldv = _lib.mat(v, "v")
+        po, ldo = _lib.mat(out, "out")
+        split_ref, _, _scratch = _attn_split(csr, C, dev)
+        with _Timed("resgated_fwd"):
+            _lib.check(lib.rgbx_resgated_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pk, ldk, pq, ldq, pv, ldv, po,
+                                                 ldo, N, C, split_ref, _lib.stream_ptr()), "rgbx_resgated_fwd_f32")
+        ctx.graph = graph
+        ctx.save_for_backward(k, q, v)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        k, q, v = ctx.saved_tensors
+        g = ctx.graph
+        lib = _lib.load()
+        N, C, dev = g.fwd.N, k.size(1), k.device
+        need = ctx.needs_input_grad
+        gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
+        pk, ldk = _lib.mat(k, "k")
+        pq, ldq = _lib.mat(q, "q")
+        pv, ldv = _lib.mat(v, "v")
+        pg, ldg = _lib.mat(gout, "gout")
+        g_k = g_q = g_v = None
+        if need[0]:
+            g_k = torch.empty((N, C), dtype=torch.float32, device=dev)
+            pgk, ldgk = _lib.mat(g_k, "g_k")
+            split_ref, _, _scratch = _attn_split(g.fwd, C, dev)
+            with _Timed("resgated_bwd_dst"):
+                _lib.check(
+                    lib.rgbx_resgated_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pk, ldk, pq, ldq, pv, ldv,
+                                                  pg, ldg, pgk, ldgk, N, C, split_ref, _lib.stream_ptr()),
+                    "rgbx_resgated_bwd_dst_f32")
+        if need[1] or need[2]:  # one pass forms both sums from the same two gathered rows
+            g_q = torch.empty((N, C), dtype=torch.float32, device=dev)
+            g_v = torch.empty_like(g_q)
+            pgq, ldgq = _lib.mat(g_q, "g_q")
+            pgv, ldgv = _lib.mat(g_v, "g_v")
+            split_ref, _, _scratch2 = _attn_split(g.bwd, 2 * C, dev)
+            with _Timed("resgated_bwd_src"):
+                _lib.check(
+                    lib.rgbx_resgated_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), pk, ldk, pq, ldq, pv, ldv,
+                                                  pg, ldg, pgq, ldgq, pgv, ldgv, N, C, split_ref, _lib.stream_ptr()),
+                    "rgbx_resgated_bwd_src_f32")
+        return g_k, g_q if need[1] else None, g_v if need[2] else None, None
+
+
+def resgated_supported(C):
+    return bool(_lib.load().rgbx_resgated_supported(C))
+
+
+def resgated_aggregate(k, q, v, graph):
+    """One ResGatedGraphConv aggregation on k, q, v [N, C] (rows contiguous; column blocks of one wider matrix are taken
+    as they are): out_i = sum_j sigmoid(k_i + q_j) * v_j, elementwise over the C channels, over the in-edges of i, the
+    graph in mode LOOPS_KEEP (edges as given: self-loops stay, duplicates count twice, a node without in-edges gets
+    zeros). No normalisation, no dropout, no random state."""
+    if _is_dist(graph):
+        raise RuntimeError("ResGatedGraphConv has no node-partitioned form: run it on one GPU")
+    _lib.require_device(k, q, v)
+    if k.dim() != 2 or not resgated_supported(k.size(1)):
+        raise RuntimeError(f"resgated_aggregate: k {tuple(k.shape)}: the kernels take [N, C] with any C <= 64, even "
+                           "C <= 128 or C % 4 == 0 up to 256; pad the width (ResGatedGraphConv does)")
+    return _ResGatedAggregate.apply(k, q, v, graph)
+
+
 FACONV_FORMS = ("fused", "composed")
 
 
