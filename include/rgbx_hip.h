@@ -30,6 +30,8 @@
  *   rgbx_gatv2_*          GATv2Conv (dynamic attention) [PyG]; not in the reference's zoo, shaped like models/gat.py.
  *   rgbx_transformer_*    TransformerConv (scaled dot-product attention) [PyG]; not in the reference's zoo.
  *   rgbx_resgated_*       ResGatedGraphConv (per-channel sigmoid gate) [PyG]; not in the reference's zoo.
+ *   rgbx_softmax_aggr_*   SoftmaxAggregation / GENConv(aggr="softmax") (per-channel softmax at a trained temperature)
+ *                         [PyG]; not in the reference's zoo.
  *   rgbx_gemm_tn_f32      dW = dY^T X of the nn.Linear / conv.lin layers under loss.backward()
  *                         (itexperiments.py:439; layers at models/gcn.py:18-21, appnp_stack.py:19-20).
  *   rgbx_bn_* / rgbx_affine_cols_f32
@@ -873,6 +875,46 @@ int rgbx_resgated_bwd_dst_f32(const int32_t* rowptr, const int32_t* col, const f
 int rgbx_resgated_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* k, int64_t ldk, const float* q,
                               int64_t ldq, const float* v, int64_t ldv, const float* gout, int64_t ldg, float* g_q,
                               int64_t ldgq, float* g_v, int64_t ldgv, int64_t N, int C, const rgbx_row_split_t* split,
+                              rgbx_stream_t stream);
+
+/* ---- Softmax aggregation (GENConv / DeeperGCN): per-channel softmax over the in-edges at a trained temperature ----- */
+
+/* For an edge j -> i (p = its slot in the target-grouped CSR), with messages m [N, C] (its own pointer and leading
+ * dimension) and a temperature t in DEVICE memory (t_stride = 0: one float for every channel; t_stride = 1: t [C]):
+ *   z_p[c]     = t[c] m[j,c]
+ *   alpha_p[c] = exp(z_p[c] - lse[i,c]),   lse[i,c] = log sum_p exp(z_p[c])
+ *   out[i,c]   = sum_p alpha_p[c] m[j,c]
+ * (SoftmaxAggregation / GENConv(aggr="softmax") [PyG]; Li et al., "DeeperGCN: All You Need to Train Deeper GCNs". The
+ * reference's zoo has no GENConv.) t = 0 gives the mean, t -> inf the maximum, t < 0 a soft minimum: the running
+ * maximum is taken of z, so no intermediate overflows whatever t m is. The temperature is read by the kernels, never by
+ * the host: a captured launch follows a parameter that an optimizer moves. The edges are taken as they are
+ * (RGBX_LOOPS_KEEP): a row WITHOUT slots stores exact zeros in `out` and 0 in `lse`; a source without out-edges gets a
+ * zero g_m row. Every output row is written. Nothing per edge is stored: the backward recomputes alpha from `lse`. No
+ * entry point uses float atomics: two runs are bit-identical. */
+
+/* 1 if the kernels take C channels (the widths of rgbx_resgated_supported), else 0. */
+int rgbx_softmax_aggr_supported(int C);
+
+/* Forward over the target-grouped CSR. `lse` ([N, C], leading dimension ldl) may be NULL (the inference form: the same
+ * bits in `out`). `split`: hub rows as in rgbx_gatv2_fwd_f32; split->partial holds n_chunks * 3*C floats (acc | max |
+ * den per chunk), merged in chunk order. */
+int rgbx_softmax_aggr_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* m, int64_t ldm, const float* t,
+                              int t_stride, float* out, int64_t ldo, float* lse, int64_t ldl, int64_t N, int C,
+                              const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Floats of caller scratch rgbx_softmax_aggr_bwd_f32 needs for its g_t records, for this N and split plan. */
+int rgbx_softmax_aggr_gt_partial_floats(int64_t N, int C, const rgbx_row_split_t* split, int64_t* count);
+
+/* Backward over the TRANSPOSED CSR (rows = sources j, col_t = targets i), with d = m[j,:] - out[i,:]:
+ *   g_m[j,c] = sum_p alpha_p gout[i,c] (1 + t[c] d[c]),    g_t[c] = sum over all edges of alpha gout[i,c] d[c]^2.
+ * g_m is always formed. g_t ([C], per channel whatever t_stride is; a scalar temperature's gradient is its sum) may be
+ * NULL: no record is then kept and no reduction runs. Otherwise `gt_partial` holds n_gt_partial >=
+ * rgbx_softmax_aggr_gt_partial_floats floats: one [C] record per workgroup, added in record order.
+ * split->partial holds n_chunks * C floats. */
+int rgbx_softmax_aggr_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const float* m, int64_t ldm, const float* t,
+                              int t_stride, const float* out, int64_t ldo, const float* lse, int64_t ldl,
+                              const float* gout, int64_t ldg, float* g_m, int64_t ldgm, float* g_t, float* gt_partial,
+                              int64_t n_gt_partial, int64_t N, int C, const rgbx_row_split_t* split,
                               rgbx_stream_t stream);
 
 /* ---- dense layers on the MFMA units -------------------------------------------------------- */

@@ -145,6 +145,11 @@ SIGNATURES = {
     "rgbx_resgated_bwd_dst_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
     "rgbx_resgated_bwd_src_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P,
                                   _P],
+    "rgbx_softmax_aggr_supported": [_I],
+    "rgbx_softmax_aggr_fwd_f32": [_P, _P, _P, _I64, _P, _I, _P, _I64, _P, _I64, _I64, _I, _P, _P],
+    "rgbx_softmax_aggr_gt_partial_floats": [_I64, _I, _P, ctypes.POINTER(ctypes.c_int64)],
+    "rgbx_softmax_aggr_bwd_f32": [_P, _P, _P, _I64, _P, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64,
+                                  _I, _P, _P],
     "rgbx_gemm_tn_workspace_bytes": [_I64, _I64, _I64, ctypes.POINTER(ctypes.c_size_t)],
     "rgbx_gemm_tn_f32": [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _F, _P, ctypes.c_size_t, _P],
     "rgbx_gemm_tn_bn_bwd_f32": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _F, _P,

@@ -19,6 +19,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
+from .batchnorm import BatchNorm1d
+from .linear import Linear
 from ..graph import LOOPS_ADD_REMAINING, LOOPS_KEEP, LOOPS_REMOVE_ADD, get_graph
 
 
@@ -1056,6 +1058,83 @@ class ResGatedGraphConv(nn.Module):
         if self.bias is not None:
             out = out + self.bias
         return out
+
+
+class GENConv(nn.Module):
+    """DeeperGCN's generalised graph convolution with the softmax aggregator [PyG GENConv(aggr="softmax"); Li et al.,
+    "DeeperGCN: All You Need to Train Deeper GCNs"]: with xs = lin_src(x) and xd = lin_dst(x) (both layers exist only
+    when in_channels != out_channels; otherwise xs = xd = x), the message of an edge j -> i is m_j = relu(xs_j) + eps,
+    aggregated per channel by a softmax over the in-edges of i at temperature t — out_i = sum_j softmax_j(t m_j) m_j,
+    the edges AS GIVEN (self-loops stay, duplicates count twice, a node without in-edges aggregates zeros) — then
+    h = out + xd and the result is mlp(h): Linear(C, expansion C) -> BatchNorm1d over the nodes -> ReLU -> (the middle
+    block again for num_layers > 2) -> Linear(expansion C, C). `t` is a Parameter with learn_t, a buffer otherwise; one
+    value, or one per channel with per_channel_t. The aggregation runs in the rgbx_softmax_aggr_* kernels
+    (ops.softmax_aggregate), which read t on the device; a width outside the kernels' set is padded with channels that
+    hold eps everywhere and sliced off again.
+
+    The layer follows the dataflow PyG documents for GENConv(aggr="softmax"); PyG is not a dependency here, so parity
+    with its implementation (parameter names included: PyG keeps t in aggr_module and builds its MLP class) is unpinned.
+
+    Out of scope: edge features (`edge_dim` / edge_attr), message normalisation (`msg_norm`), the power-mean and the
+    other aggregators (`aggr`), the node-partitioned (distributed) route."""
+
+    def __init__(self, in_channels, out_channels, t=1.0, learn_t=False, per_channel_t=False, eps=1e-7, num_layers=2,
+                 expansion=2, bias=True, aggr="softmax", msg_norm=False, edge_dim=None):
+        super().__init__()
+        if aggr != "softmax":
+            raise NotImplementedError(f"GENConv: aggr={aggr!r} is not built (softmax only)")
+        if msg_norm:
+            raise NotImplementedError("GENConv: msg_norm is not built")
+        if edge_dim is not None:
+            raise NotImplementedError("GENConv: edge features (edge_dim) are not built")
+        if num_layers < 2 or expansion < 1:
+            raise ValueError("GENConv: num_layers must be at least 2 and expansion at least 1")
+        self.in_channels, self.out_channels, self.eps = in_channels, out_channels, float(eps)
+        self.learn_t, self.per_channel_t, self.initial_t = learn_t, per_channel_t, float(t)
+        C = out_channels
+        if in_channels != out_channels:
+            self.lin_src = Linear(in_channels, C, bias=bias)
+            self.lin_dst = Linear(in_channels, C, bias=bias)
+        else:
+            self.lin_src = self.lin_dst = None
+        widths = [C] + [C * expansion] * (num_layers - 1) + [C]
+        layers = []
+        for i in range(num_layers):
+            layers.append(Linear(widths[i], widths[i + 1], bias=bias))
+            if i < num_layers - 1:
+                layers += [BatchNorm1d(widths[i + 1]), nn.ReLU()]
+        self.mlp = nn.Sequential(*layers)
+        temp = torch.full((C if per_channel_t else 1,), float(t))
+        if learn_t:
+            self.t = nn.Parameter(temp)
+        else:
+            self.register_buffer("t", temp)
+
+    def reset_parameters(self):
+        for mod in [self.lin_src, self.lin_dst] + list(self.mlp):
+            if hasattr(mod, "reset_parameters"):
+                mod.reset_parameters()
+        with torch.no_grad():
+            self.t.fill_(self.initial_t)
+
+    def forward(self, x, edge_index):
+        _lib.require_device(x)
+        C = self.out_channels
+        Cp = GATConv.kernel_channels(C)
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        xs = x if self.lin_src is None else self.lin_src(x)
+        xd = x if self.lin_dst is None else self.lin_dst(x)
+        m = torch.relu(xs) + self.eps
+        t = self.t
+        if Cp != C:  # a padded channel holds eps in every row: it aggregates to eps and is sliced off again
+            pad = torch.nn.functional.pad
+            m = pad(m, (0, Cp - C), value=self.eps)
+            if self.per_channel_t:
+                t = pad(t, (0, Cp - C))
+        out = ops.softmax_aggregate(m, t, graph)
+        if Cp != C:
+            out = out[:, :C]
+        return self.mlp(out + xd)
 
 
 class FAConv(nn.Module):

@@ -2796,6 +2796,94 @@ def resgated_aggregate(k, q, v, graph):
     return _ResGatedAggregate.apply(k, q, v, graph)
 
 
+class _SoftmaxAggregate(torch.autograd.Function):
+    """One softmax aggregation as a single autograd node: a softmax per channel over the in-edges at temperature t, fused
+    with the sum of the weighted message rows; backward = one pass over the transposed CSR (g_m, and the g_t records
+    plus their reduction only when t asks for a gradient). Saves m, t, out and lse [N, C]; nothing per edge (the
+    backward recomputes alpha = exp(t m_j - lse_i)). The kernels read t from device memory, so a captured launch
+    follows a temperature the optimizer moves."""
+
+    @staticmethod
+    def forward(ctx, m, t, graph, want_grad):
+        _lib.require_device(m, t)
+        lib = _lib.load()
+        C = m.size(1)
+        m = _rows_on_grid(m, _head_vec(C))
+        csr, N, dev = graph.fwd, graph.fwd.N, m.device
+        tv = t.detach().reshape(-1).contiguous()
+        out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: zeros)
+        # lse is the backward's; without one the kernel runs its inference form
+        lse = torch.empty((N, C), dtype=torch.float32, device=dev) if want_grad else None
+        pm, ldm = _lib.mat(m, "m")
+        po, ldo = _lib.mat(out, "out")
+        pl, ldl = _lib.mat(lse, "lse") if lse is not None else (None, 0)
+        split_ref, _, _scratch = _attn_split(csr, 3 * C, dev)
+        with _Timed("softmax_aggr_fwd"):
+            _lib.check(lib.rgbx_softmax_aggr_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pm, ldm, _lib.ptr(tv),
+                                                     int(tv.numel() > 1), po, ldo, pl, ldl, N, C, split_ref,
+                                                     _lib.stream_ptr()), "rgbx_softmax_aggr_fwd_f32")
+        ctx.graph, ctx.t_shape = graph, t.shape
+        ctx.save_for_backward(m, tv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        m, tv, out, lse = ctx.saved_tensors
+        g = ctx.graph
+        need = ctx.needs_input_grad
+        if not (need[0] or need[1]):
+            return None, None, None, None
+        lib = _lib.load()
+        N, C, dev = g.fwd.N, m.size(1), m.device
+        gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
+        g_m = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (sources without slots: zeros)
+        pm, ldm = _lib.mat(m, "m")
+        po, ldo = _lib.mat(out, "out")
+        pl, ldl = _lib.mat(lse, "lse")
+        pg, ldg = _lib.mat(gout, "gout")
+        pgm, ldgm = _lib.mat(g_m, "g_m")
+        split_ref, split, _scratch = _attn_split(g.bwd, C, dev)
+        g_t = part = None
+        n_part = ctypes.c_int64(0)
+        if need[1]:
+            _lib.check(lib.rgbx_softmax_aggr_gt_partial_floats(N, C, split_ref, ctypes.byref(n_part)),
+                       "rgbx_softmax_aggr_gt_partial_floats")
+            g_t = torch.empty(C, dtype=torch.float32, device=dev)
+            part = torch.empty(max(n_part.value, 1), dtype=torch.float32, device=dev)
+        with _Timed("softmax_aggr_bwd", variant="g_t" if need[1] else None):
+            _lib.check(
+                lib.rgbx_softmax_aggr_bwd_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), pm, ldm, _lib.ptr(tv),
+                                              int(tv.numel() > 1), po, ldo, pl, ldl, pg, ldg, pgm, ldgm, _lib.ptr(g_t),
+                                              _lib.ptr(part), n_part.value, N, C, split_ref, _lib.stream_ptr()),
+                "rgbx_softmax_aggr_bwd_f32")
+        if g_t is not None:  # the kernels leave g_t per channel: a scalar temperature's gradient is the sum
+            g_t = (g_t if tv.numel() > 1 else g_t.sum()).reshape(ctx.t_shape)
+        return g_m if need[0] else None, g_t, None, None
+
+
+def softmax_aggregate_supported(C):
+    return bool(_lib.load().rgbx_softmax_aggr_supported(C))
+
+
+def softmax_aggregate(m, t, graph):
+    """One softmax aggregation [PyG SoftmaxAggregation; DeeperGCN] of the messages m [N, C] (rows contiguous; a column
+    block of a wider matrix is taken as it is) at the temperature t (a tensor on m's device: one element, or one per
+    channel; it may take a gradient): out_i = sum_j softmax_j(t * m_j) * m_j, per channel, over the in-edges of i, the
+    graph in mode LOOPS_KEEP (edges as given: self-loops stay, duplicates count twice, a node without in-edges gets
+    zeros). t = 0 is the mean, large t the maximum, negative t a soft minimum. No dropout, no random state."""
+    if _is_dist(graph):
+        raise RuntimeError("GENConv has no node-partitioned form: run it on one GPU")
+    _lib.require_device(m, t)
+    if m.dim() != 2 or not softmax_aggregate_supported(m.size(1)):
+        raise RuntimeError(f"softmax_aggregate: m {tuple(m.shape)}: the kernels take [N, C] with any C <= 64, even "
+                           "C <= 128 or C % 4 == 0 up to 256; pad the width (GENConv does)")
+    if m.size(0) != graph.fwd.N or t.numel() not in (1, m.size(1)) or t.dtype != torch.float32:
+        raise RuntimeError(f"softmax_aggregate: m {tuple(m.shape)} / t {tuple(t.shape)} for a graph of {graph.fwd.N} "
+                           "nodes (t: one float32, or one per channel)")
+    want_grad = torch.is_grad_enabled() and (m.requires_grad or t.requires_grad)
+    return _SoftmaxAggregate.apply(m, t, graph, want_grad)
+
+
 FACONV_FORMS = ("fused", "composed")
 
 
