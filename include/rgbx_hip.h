@@ -30,6 +30,8 @@
  *   rgbx_gatv2_*          GATv2Conv (dynamic attention) [PyG]; not in the reference's zoo, shaped like models/gat.py.
  *   rgbx_transformer_*    TransformerConv (scaled dot-product attention) [PyG]; not in the reference's zoo.
  *   rgbx_resgated_*       ResGatedGraphConv (per-channel sigmoid gate) [PyG]; not in the reference's zoo.
+ *   rgbx_gine_*           GINEConv (GIN with a feature row per edge: relu(x_j + e_ji) summed) [PyG]; the zoo's
+ *                         models/gin.py is its sibling without edge features.
  *   rgbx_softmax_aggr_*   SoftmaxAggregation / GENConv(aggr="softmax") (per-channel softmax at a trained temperature)
  *                         [PyG]; not in the reference's zoo.
  *   rgbx_gemm_tn_f32      dW = dY^T X of the nn.Linear / conv.lin layers under loss.backward()
@@ -876,6 +878,46 @@ int rgbx_resgated_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, con
                               int64_t ldq, const float* v, int64_t ldv, const float* gout, int64_t ldg, float* g_q,
                               int64_t ldgq, float* g_v, int64_t ldgv, int64_t N, int C, const rgbx_row_split_t* split,
                               rgbx_stream_t stream);
+
+/* ---- GINEConv: relu(x_j + e_ji) summed over the in-edges, with a feature row per edge ------------------------------ */
+
+/* For an edge j -> i (p = its slot in the target-grouped CSR), with x [N, C] and e [nnz, C] — ONE ROW PER SLOT, in
+ * forward CSR slot order — each with its own pointer and leading dimension (column blocks of a wider matrix are taken
+ * as they are):
+ *   out[i,:] = (1 + eps) * x[i,:] + sum_p relu(x[j,:] + e[p,:])
+ * (GINEConv.forward / message [PyG]; Hu et al., "Strategies for Pre-training Graph Neural Networks". The reference's
+ * zoo has GIN, models/gin.py, and no GINEConv.) `eps` is ONE float in DEVICE memory, read by the kernels, never by the
+ * host: a captured launch follows a parameter that an optimizer moves; NULL = no root term. Nothing is saved for the
+ * backward: its two passes recompute the mask [x[j,:] + e[p,:] > 0] from the forward's own float32 add (relu'(0) = 0)
+ * and are independent of each other. The edges are taken as they are (RGBX_LOOPS_KEEP): a row WITHOUT slots stores the
+ * root term alone, a source without out-edges (1 + eps) gout[j,:]. Every output row is written, every slot row of g_e
+ * too. No entry point uses float atomics: two runs are bit-identical. */
+
+/* 1 if the kernels take C channels (the widths of rgbx_resgated_supported), else 0. */
+int rgbx_gine_supported(int C);
+
+/* Forward over the target-grouped CSR: x rows gathered, the e rows of a target read as a stream. `split`: hub rows as
+ * in rgbx_gatv2_fwd_f32; split->partial holds n_chunks * C floats, added in chunk order (the root term rides on the
+ * row's first chunk). */
+int rgbx_gine_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx, const float* e,
+                      int64_t lde, const float* eps, float* out, int64_t ldo, int64_t N, int C,
+                      const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward, edge side, over the forward CSR:  g_e[p,:] = gout[i,:] (.) [x[j,:] + e[p,:] > 0], one row per slot in
+ * forward slot order. No sum is formed: every value is a copy of gout or an exact zero. `split` only balances the hub
+ * rows (split->partial is not touched). */
+int rgbx_gine_bwd_edge_f32(const int32_t* rowptr, const int32_t* col, const float* x, int64_t ldx, const float* e,
+                           int64_t lde, const float* gout, int64_t ldg, float* g_e, int64_t ldge, int64_t N, int C,
+                           const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward, source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i, t2f [nnz] = the forward slot of
+ * every transposed slot), in any order with the edge side:
+ *   g_x[j,:] = (1 + eps) * gout[j,:] + sum_q gout[col_t[q],:] (.) [x[j,:] + e[t2f[q],:] > 0].
+ * split->partial holds n_chunks * C floats. */
+int rgbx_gine_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const float* x,
+                          int64_t ldx, const float* e, int64_t lde, const float* gout, int64_t ldg, const float* eps,
+                          float* g_x, int64_t ldgx, int64_t N, int C, const rgbx_row_split_t* split,
+                          rgbx_stream_t stream);
 
 /* ---- Softmax aggregation (GENConv / DeeperGCN): per-channel softmax over the in-edges at a trained temperature ----- */
 

@@ -145,6 +145,10 @@ SIGNATURES = {
     "rgbx_resgated_bwd_dst_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
     "rgbx_resgated_bwd_src_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P,
                                   _P],
+    "rgbx_gine_supported": [_I],
+    "rgbx_gine_fwd_f32": [_P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I, _P, _P],
+    "rgbx_gine_bwd_edge_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
+    "rgbx_gine_bwd_src_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I, _P, _P],
     "rgbx_softmax_aggr_supported": [_I],
     "rgbx_softmax_aggr_fwd_f32": [_P, _P, _P, _I64, _P, _I, _P, _I64, _P, _I64, _I64, _I, _P, _P],
     "rgbx_softmax_aggr_gt_partial_floats": [_I64, _I, _P, ctypes.POINTER(ctypes.c_int64)],

@@ -229,7 +229,8 @@ def experiment(model_init_param: dict, *,
                cache_input_aggregate="auto",
                distributed=None,
                task_split: str = "auto",
-               use_edge_weight: bool = False):
+               use_edge_weight: bool = False,
+               use_edge_attr: bool = False):
     """Train + evaluate one model on one graph; returns {'ACC', 'precision_score', 'recall_score',
     'f1_macro', 'f1_micro'} (reference :603-605). ``return_model=True`` (an addition) also returns
     the trained module and the per-epoch curves under 'model' / 'history'. ``use_hip_graph=True`` (an
@@ -269,7 +270,13 @@ def experiment(model_init_param: dict, *,
     (models/dagnn.py:12-31) — for the four routes that take weights: ``gcn``, ``appnpstack``, ``sgc`` and ``post_cs``
     (any other model_name: ValueError). Not with ``to_undirected_graph`` (the reference's to_undirected call carries no
     weights: ValueError) and not on the partitioned route (NotImplementedError). With the flag off a ``Data`` that
-    happens to carry an ``edge_weight`` attribute behaves exactly as one without."""
+    happens to carry an ``edge_weight`` attribute behaves exactly as one without. ``use_edge_attr=True`` (an addition, off by
+    default): ``data.edge_attr`` (float [E, D], one feature row per edge) goes to the device with the data and into the
+    forward arguments as ``edge_attr``, for ``model_name="gine"`` (models.GINE, built with ``edge_dim`` in
+    ``model_init_param``) and for a caller's ``model=`` whose forward takes ``edge_attr`` (any other model_name:
+    ValueError). Not with ``to_undirected_graph`` (that call carries no attributes: ValueError) and not on the partitioned
+    route (NotImplementedError). With the flag off a ``Data`` that happens to carry an ``edge_attr`` behaves exactly as
+    one without (``gine`` then fails at its forward, which needs the argument)."""
     say = print if print_print else (lambda *a, **k: None)
     say(f"running node classification: {'custom' if specify_data else dataset_name} data, model {model_name}")
 
@@ -291,6 +298,17 @@ def experiment(model_init_param: dict, *,
             raise ValueError("use_edge_weight=True cannot be combined with to_undirected_graph=True: the reference's "
                              "to_undirected call (:235-238) carries no weights")
 
+    if use_edge_attr:
+        if model is not None:
+            if not isinstance(model, nn.Module) or "edge_attr" not in inspect.signature(model.forward).parameters:
+                raise ValueError("use_edge_attr=True: the forward of the module passed as model= takes no edge_attr")
+        elif name != "gine":
+            raise ValueError(f"use_edge_attr=True: model_name={model_name!r} takes no edge attributes; the routes that do "
+                             "are gine and a model= whose forward takes edge_attr")
+        if to_undirected_graph:
+            raise ValueError("use_edge_attr=True cannot be combined with to_undirected_graph=True: the reference's "
+                             "to_undirected call (:235-238) carries no attributes")
+
     # ---- data (reference :179-229) ----------------------------------------------------------
     if not specify_data:
         data = RD2PD(dataset_root=dataset_root, dataset_name=dataset_name, split_method=dataset_split_mode,
@@ -304,6 +322,14 @@ def experiment(model_init_param: dict, *,
                 data.y.cpu(), dataset_split_mode, dataset_split_ratio, num_train_per_class, num_val, num_test,
                 dataset_split_seed)
 
+    if use_edge_attr:  # the contract of data.edge_attr, checked before any device is touched
+        edge_attr = getattr(data, "edge_attr", None)
+        if not torch.is_tensor(edge_attr) or not edge_attr.is_floating_point():
+            raise ValueError("use_edge_attr=True needs data.edge_attr: a float tensor of shape [E, D]")
+        if edge_attr.dim() != 2 or edge_attr.size(0) != data.edge_index.size(1):
+            raise ValueError(f"data.edge_attr must have shape [E, D] = [{data.edge_index.size(1)}, D], got "
+                             f"{tuple(edge_attr.shape)}")
+
     # ---- device (reference :246-258): the message-passing path is HIP-only -------------------
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if distributed is None:  # one of several ranks a launcher started, and a model with a node-partitioned form
@@ -312,6 +338,8 @@ def experiment(model_init_param: dict, *,
     dist_ctx = None
     if distributed and use_edge_weight:
         raise NotImplementedError("use_edge_weight=True is not implemented on the partitioned (distributed) route")
+    if distributed and use_edge_attr:
+        raise NotImplementedError("use_edge_attr=True is not implemented on the partitioned (distributed) route")
     if distributed and model is None and (model_init_param or {}).get("aggr", "mean") != "mean":
         raise NotImplementedError(f"aggr={model_init_param['aggr']!r} is not implemented on the partitioned (distributed) "
                                   "route: its exchange carries sums")
@@ -336,6 +364,9 @@ def experiment(model_init_param: dict, *,
             raise ValueError(f"data.edge_weight must have shape [E] = [{data.edge_index.size(1)}], got "
                              f"{tuple(edge_weight.shape)}")
         edge_weight = edge_weight.detach().to(torch.float32).contiguous()
+    edge_attr = None
+    if use_edge_attr:
+        edge_attr = data.edge_attr.detach().to(torch.float32).contiguous()
     features = data.x
     if normalize_feature in ("row", "col", "all"):
         features = _normalize_features(features, normalize_feature, normalize_feature_method)
@@ -374,6 +405,8 @@ def experiment(model_init_param: dict, *,
         params = inspect.signature(net.forward).parameters
         takes_edges = "edge_index" in params or any(p.kind is p.VAR_KEYWORD for p in params.values())
         fwd = {"x": features, "edge_index": data.edge_index} if takes_edges else {"x": features}
+        if edge_attr is not None:
+            fwd["edge_attr"] = edge_attr
     elif is_pta:  # reference :351-374
         adj = normalized_adjacency(data.edge_index, data.num_nodes)
         idx = [m.nonzero(as_tuple=True)[0] for m in (train_mask, val_mask, test_mask)]
@@ -386,6 +419,8 @@ def experiment(model_init_param: dict, *,
         fwd = {"x": features} if name == "mlp" else {"x": features, "edge_index": data.edge_index}
         if edge_weight is not None:
             fwd["edge_weight"] = edge_weight
+        if edge_attr is not None:
+            fwd["edge_attr"] = edge_attr
     net.to(device)
     uses_graph = name != "mlp" if model is None else "edge_index" in fwd
     if model is not None:  # one eval-mode forward before the loop: the contract of the returned mapping

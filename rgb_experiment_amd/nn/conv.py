@@ -709,6 +709,73 @@ class GINConv(nn.Module):
         return self.nn(ops.propagate_sum(x, graph) + (1 + self.eps) * x)
 
 
+class GINEConv(nn.Module):
+    """GIN with edge features [PyG GINEConv; Hu et al., "Strategies for Pre-training Graph Neural Networks"; the layer
+    of the OGB baselines]: out = nn((1 + eps) * x_i + sum_{j -> i} relu(x_j + e_ji)), the edges AS GIVEN (self-loops
+    stay, duplicates count twice, a node without in-edges aggregates zeros, so nn sees (1 + eps) x_i). `edge_attr`
+    [E, D] holds one row per input edge. With edge_dim=D, e = lin(edge_attr), lin = Linear(D, in_channels) with bias and
+    in_channels read from the first Linear of `nn_module`; with edge_dim=None edge_attr must already be in_channels
+    wide (ValueError before any launch otherwise). eps is a Parameter with train_eps, a buffer otherwise, as in GINConv.
+    Parameter names are PyG's (nn.*, eps, lin.*).
+
+    The attribute rows are permuted into CSR slot order once, at their raw width (ops.edge_rows_to_slots), so lin yields
+    the per-slot rows directly and dW_lin comes out of the Linear's own backward; message, sum and root term run in the
+    rgbx_gine_* kernels (ops.gine_aggregate), which read eps on the device. A width outside the kernels' set is
+    zero-padded in x and in lin's rows (a padded channel contributes relu(0 + 0) = 0) and sliced off again.
+
+    Out of scope: the node-partitioned (distributed) route, edge attributes through to_undirected / coalesce."""
+
+    def __init__(self, nn_module, eps=0.0, train_eps=False, edge_dim=None):
+        super().__init__()
+        self.nn = nn_module
+        self.initial_eps = eps
+        if train_eps:
+            self.eps = nn.Parameter(torch.tensor([float(eps)]))
+        else:
+            self.register_buffer("eps", torch.tensor([float(eps)]))
+        first = next((m for m in nn_module.modules() if isinstance(m, nn.Linear)), None)
+        self.in_channels = None if first is None else first.in_features
+        self.edge_dim = edge_dim
+        if edge_dim is not None:
+            if self.in_channels is None:
+                raise ValueError("GINEConv: edge_dim needs the input width, read from the first Linear of nn; it has none")
+            self.lin = Linear(edge_dim, self.in_channels)
+        else:
+            self.lin = None
+
+    @staticmethod
+    def kernel_channels(C):
+        """The width the aggregation runs at: C where the kernels take it (their set up to 256, and column blocks of
+        256 above it whose last block is in the set), else the next multiple of 4."""
+        last = C if C <= ops.GINE_BLOCK else (C % ops.GINE_BLOCK or ops.GINE_BLOCK)
+        return C if GATConv.kernel_channels(last) == last else (C + 3) // 4 * 4
+
+    def forward(self, x, edge_index, edge_attr):
+        C = x.size(1)
+        want = C if self.lin is None else self.edge_dim
+        if not torch.is_tensor(edge_attr) or edge_attr.dim() != 2 or edge_attr.size(1) != want \
+                or edge_attr.size(0) != edge_index.size(1) or not edge_attr.is_floating_point():
+            got = tuple(edge_attr.shape) if torch.is_tensor(edge_attr) else type(edge_attr).__name__
+            raise ValueError(f"GINEConv: edge_attr must be float [E, {want}] = [{edge_index.size(1)}, {want}] "
+                             f"({'edge_dim' if self.lin is not None else 'the node width: edge_dim=None'}), got {got}")
+        if self.in_channels is not None and C != self.in_channels:
+            raise ValueError(f"GINEConv: x has {C} channels, nn's first Linear takes {self.in_channels}")
+        _lib.require_device(x, edge_attr)
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        ea = ops.edge_rows_to_slots(edge_attr.to(torch.float32), graph)
+        Cp = self.kernel_channels(C)
+        pad = torch.nn.functional.pad
+        if edge_index.size(1) == 0:  # no slot, no product
+            e = x.new_zeros((0, Cp))
+        elif self.lin is not None:
+            w, b = self.lin.weight, self.lin.bias
+            e = ops.linear(ea, w, b) if Cp == C else ops.linear(ea, pad(w, (0, 0, 0, Cp - C)), pad(b, (0, Cp - C)))
+        else:
+            e = ea if Cp == C else pad(ea, (0, Cp - C))
+        out = ops.gine_aggregate(x if Cp == C else pad(x, (0, Cp - C)), e, graph, self.eps)
+        return self.nn(out if Cp == C else out[:, :C])
+
+
 class GatedGraphConv(nn.Module):
     """Gated graph convolution: the input (zero-padded to out_channels columns; wider inputs raise) runs through
     num_layers steps of m = x weight[i], agg_i = sum_{j -> i} m_j (edges as given, duplicates counted, no loops added,

@@ -2796,6 +2796,168 @@ def resgated_aggregate(k, q, v, graph):
     return _ResGatedAggregate.apply(k, q, v, graph)
 
 
+_EDGE_SLOTS_MAX = 4  # cached slot-ordered copies per graph (each is an [E, D] matrix)
+
+
+def _slot_to_edge(graph):
+    """(perm, inv) of a LOOPS_KEEP graph: perm [E] the input edge of every forward CSR slot, inv [E] the slot of every
+    input edge (perm is a permutation there: nothing is added, nothing coalesced). Built once per graph."""
+    cached = graph.__dict__.get("_slot_to_edge")
+    if cached is None:
+        perm = graph.fwd.perm[:graph.fwd.nnz]
+        inv = torch.empty_like(perm)
+        inv[perm.long()] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
+        cached = graph._slot_to_edge = (perm.contiguous(), inv)
+    return cached
+
+
+class _EdgeRowsToSlots(torch.autograd.Function):
+    """edge_attr[perm] through rgbx_gather_rows_f32; the backward is the gather through the inverse permutation (every
+    input edge owns exactly one slot, so nothing is added: no atomics)."""
+
+    @staticmethod
+    def forward(ctx, edge_attr, graph):
+        ctx.graph = graph
+        return gather_rows(edge_attr.contiguous(), _slot_to_edge(graph)[0])
+
+    @staticmethod
+    def backward(ctx, gout):
+        return gather_rows(gout.contiguous(), _slot_to_edge(ctx.graph)[1]), None
+
+
+def edge_rows_to_slots(edge_attr, graph):
+    """edge_attr [E, D] (one row per INPUT edge, float32) as [E, D] in forward CSR slot order: row p is the attribute row
+    of the edge in slot p, edge_attr[perm[p]]. Only for graphs in mode LOOPS_KEEP, where every input edge owns exactly one
+    slot (nnz == E, perm a permutation); any other mode raises. An attribute matrix that does not require grad is
+    permuted once per (storage, shape, in-place version) and the result kept on the graph; one that does is permuted by a
+    differentiable gather on every call (backward: the gather through the inverse permutation, no atomics). The
+    permutation happens at the raw width D: a layer's Linear over the result yields its per-slot rows directly."""
+    from .graph import LOOPS_KEEP
+    if _is_dist(graph):
+        raise RuntimeError("edge attributes have no node-partitioned form: run it on one GPU")
+    if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
+        raise RuntimeError("edge_rows_to_slots: only a graph in mode LOOPS_KEEP maps every input edge to exactly one CSR "
+                           f"slot (got loops_mode={getattr(graph, 'loops_mode', None)!r})")
+    if edge_attr.dim() != 2 or edge_attr.size(0) != graph.E or edge_attr.dtype != torch.float32:
+        raise RuntimeError(f"edge_rows_to_slots: edge_attr {edge_attr.dtype} {tuple(edge_attr.shape)} for a graph of "
+                           f"{graph.E} edges (float32 [E, D])")
+    if graph.fwd.nnz != graph.E:
+        raise RuntimeError(f"edge_rows_to_slots: {graph.fwd.nnz} CSR slots for {graph.E} input edges")
+    if graph.E == 0:
+        return edge_attr[:0]
+    if edge_attr.requires_grad and torch.is_grad_enabled():
+        return _EdgeRowsToSlots.apply(edge_attr, graph)
+    cache = graph.__dict__.setdefault("_edge_slots", {})
+    key = (edge_attr.data_ptr(), tuple(edge_attr.shape), edge_attr._version)
+    hit = cache.get(key)
+    if hit is None:
+        # the key holds the attribute's data_ptr: keep its storage alive beside the permuted copy
+        hit = cache[key] = (edge_attr, gather_rows(edge_attr.detach().contiguous(), _slot_to_edge(graph)[0]))
+        while len(cache) > _EDGE_SLOTS_MAX:
+            cache.pop(next(iter(cache)))
+    return hit[1]
+
+
+class _GINEAggregate(torch.autograd.Function):
+    """One GINEConv aggregation as a single autograd node: fused message relu(x_j + e_p), sum over the in-edges and root
+    term (1 + eps) x_i; backward = edge-side pass (g_e, one row per slot), source-side pass (g_x) and, for a trained
+    eps, g_eps = sum_i <gout_i, x_i> (dense per-node work, on torch), each run only where a gradient is asked for. Saves
+    x, e and eps and nothing else: every pass recomputes the mask from the forward's own add. The kernels read eps from
+    device memory, so a captured launch follows an eps the optimizer moves."""
+
+    @staticmethod
+    def forward(ctx, x, e_slot, eps, graph):
+        _lib.require_device(x, e_slot, eps)
+        lib = _lib.load()
+        C = x.size(1)
+        # column blocks of a wider matrix stay views, where the row still fits a wave at the vector width they allow
+        x, e = (_rows_on_grid(t, _head_vec(C)) for t in (x, e_slot))
+        csr, N, dev = graph.fwd, graph.fwd.N, x.device
+        epsv = None if eps is None else eps.detach().reshape(-1).contiguous()
+        if csr.nnz == 0:  # no slot row is ever read: a pointer the entry point accepts
+            e = torch.empty((1, C), dtype=torch.float32, device=dev)
+        out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: the root)
+        px, ldx = _lib.mat(x, "x")
+        pe, lde = _lib.mat(e, "e_slot")
+        po, ldo = _lib.mat(out, "out")
+        split_ref, _, _scratch = _attn_split(csr, C, dev)
+        with _Timed("gine_fwd"):
+            _lib.check(lib.rgbx_gine_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), px, ldx, pe, lde, _lib.ptr(epsv),
+                                             po, ldo, N, C, split_ref, _lib.stream_ptr()), "rgbx_gine_fwd_f32")
+        ctx.graph, ctx.eps_shape = graph, None if eps is None else eps.shape
+        ctx.save_for_backward(x, e, epsv)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, e, epsv = ctx.saved_tensors
+        g = ctx.graph
+        lib = _lib.load()
+        N, C, dev = g.fwd.N, x.size(1), x.device
+        need = ctx.needs_input_grad
+        gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
+        px, ldx = _lib.mat(x, "x")
+        pe, lde = _lib.mat(e, "e_slot")
+        pg, ldg = _lib.mat(gout, "gout")
+        g_x = g_e = g_eps = None
+        if need[1]:
+            nnz = g.fwd.nnz
+            g_e = torch.empty((nnz, C), dtype=torch.float32, device=dev)  # every slot row is written
+            if nnz:
+                pge, ldge = _lib.mat(g_e, "g_e")
+                split_ref, _, _scratch = _attn_split(g.fwd, 1, dev)  # the plan only: this pass leaves no chunk record
+                with _Timed("gine_bwd_edge"):
+                    _lib.check(
+                        lib.rgbx_gine_bwd_edge_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), px, ldx, pe, lde, pg, ldg,
+                                                   pge, ldge, N, C, split_ref, _lib.stream_ptr()),
+                        "rgbx_gine_bwd_edge_f32")
+        if need[0]:
+            g_x = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (no out-edge: the root)
+            pgx, ldgx = _lib.mat(g_x, "g_x")
+            split_ref, _, _scratch2 = _attn_split(g.bwd, C, dev)
+            with _Timed("gine_bwd_src"):
+                _lib.check(
+                    lib.rgbx_gine_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(g.t2f), px, ldx, pe,
+                                              lde, pg, ldg, _lib.ptr(epsv), pgx, ldgx, N, C, split_ref,
+                                              _lib.stream_ptr()), "rgbx_gine_bwd_src_f32")
+        if epsv is not None and need[2]:
+            g_eps = (gout * x).sum().reshape(ctx.eps_shape)
+        return g_x, g_e, g_eps, None
+
+
+def gine_supported(C):
+    return bool(_lib.load().rgbx_gine_supported(C))
+
+
+GINE_BLOCK = 256  # wider inputs run as column blocks of this many channels
+
+
+def gine_aggregate(x, e_slot, graph, eps=None):
+    """One GINEConv aggregation on x [N, C] and e_slot [nnz, C], one row per forward CSR slot (edge_rows_to_slots gives
+    the order; rows contiguous, column blocks of a wider matrix are taken as they are):
+    out_i = (1 + eps) x_i + sum_p relu(x_j + e_p) over the in-edges of i, the graph in mode LOOPS_KEEP (edges as given:
+    self-loops stay, duplicates count twice, a node without in-edges gets the root term alone). `eps`: a one-element
+    float32 tensor on x's device (it may take a gradient), or None for no root term. relu'(0) = 0. Widths above 256 run
+    as column blocks of 256: the message is per channel, so nothing couples columns. No dropout, no random state."""
+    if _is_dist(graph):
+        raise RuntimeError("GINEConv has no node-partitioned form: run it on one GPU")
+    _lib.require_device(x, e_slot, eps)
+    N, nnz = graph.fwd.N, graph.fwd.nnz
+    if x.dim() != 2 or e_slot.dim() != 2 or x.size(0) != N or tuple(e_slot.shape) != (nnz, x.size(1)):
+        raise RuntimeError(f"gine_aggregate: x {tuple(x.shape)} / e_slot {tuple(e_slot.shape)} for a graph of {N} nodes "
+                           f"and {nnz} slots (x [N, C], e_slot [nnz, C])")
+    if eps is not None and (eps.numel() != 1 or eps.dtype != torch.float32):
+        raise RuntimeError(f"gine_aggregate: eps {eps.dtype} {tuple(eps.shape)} (one float32)")
+    C = x.size(1)
+    if C > GINE_BLOCK and gine_supported(C % GINE_BLOCK or GINE_BLOCK):  # (else: refused below, before any launch)
+        return torch.cat([_GINEAggregate.apply(x[:, a:a + GINE_BLOCK], e_slot[:, a:a + GINE_BLOCK], eps, graph)
+                          for a in range(0, C, GINE_BLOCK)], dim=1)
+    if not gine_supported(C):
+        raise RuntimeError(f"gine_aggregate: x {tuple(x.shape)}: the kernels take [N, C] with any C <= 64, even "
+                           "C <= 128 or C % 4 == 0 up to 256 (and blocks of 256 above); pad the width (GINEConv does)")
+    return _GINEAggregate.apply(x, e_slot, eps, graph)
+
+
 class _SoftmaxAggregate(torch.autograd.Function):
     """One softmax aggregation as a single autograd node: a softmax per channel over the in-edges at temperature t, fused
     with the sum of the weighted message rows; backward = one pass over the transposed CSR (g_m, and the g_t records
