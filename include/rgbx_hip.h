@@ -407,6 +407,13 @@ typedef struct rgbx_ce_epilogue {
   const int32_t* rows;
   int64_t n_rows;
   int32_t skip_unselected;
+  /* no_fill != 0 (default 0 = fill as described above): the loss gradient over a row list leaves the unlisted rows of `out`
+   * and z_out UNWRITTEN instead of writing them as 0 — whatever the buffers held stays there and may be NaN. Listed rows
+   * and the statistics keep every bit. For callers all of whose readers of the two matrices walk the same list or honour
+   * the same selection (rgbx_gemm_tn_rows_f32; rgbx_fused_layer_t.col_sel on a transposed CSR without hub rows): the
+   * zeros are then bytes nobody reads. Ignored by every other form (no list, statistics only, n_rows == 0: those write
+   * what they always wrote). */
+  int32_t no_fill;
 } rgbx_ce_epilogue_t;
 
 int rgbx_spmm_linear_supported(int64_t K, int64_t Nout, int has_root);
@@ -480,9 +487,22 @@ typedef struct rgbx_fused_layer {
    * have an entry for every column of the CSR. Honoured for K in {64, 128, 256} and Nout <= 128 without blocked layouts;
    * elsewhere, and for the hub rows of `split`, every slot is gathered (the same result). */
   const uint8_t* col_sel;
+  /* The same selection carried in the column stream (optional, only together with col_sel and under its conditions; NULL =
+   * col_sel is looked up per slot as before): [nnz] entries made by rgbx_col_tag_i32 from `col` and col_sel,
+   * col_tag[p] = col[p] if col_sel[col[p]] else ~col[p]. Where col_sel is honoured the launch reads a slot's entry from
+   * col_tag instead of `col`: a negative entry is a hole (no gather, no load of w[p], adds 0 in its place), col_sel itself
+   * is not touched. `col` stays as it is and must still be passed: the hub rows of `split` and every launch that does not
+   * honour col_sel read it, and ignore col_tag. Same result as col_sel alone, bit for bit. */
+  const int32_t* col_tag;
 } rgbx_fused_layer_t;
 
 int rgbx_fused_layer_f32(const rgbx_fused_layer_t* layer, rgbx_stream_t stream);
+
+/* col_tag[p] = sel[col[p]] ? col[p] : ~col[p] for p < nnz: rgbx_fused_layer_t.col_tag of a CSR's `col` [nnz] under the
+ * selection `sel` (uint8 [n_cols]). A deselected slot is negative and keeps its column recoverable (~col_tag[p]); a
+ * column outside [0, n_cols) is tagged as deselected. Made once per (CSR, selection); nnz == 0 does nothing. */
+int rgbx_col_tag_i32(const int32_t* col, const uint8_t* sel, int64_t nnz, int64_t n_cols, int32_t* col_tag,
+                     rgbx_stream_t stream);
 
 /* dst[i, c] (row-major, ldd) = src (blocked as above: blk_cols, blk_stride)[i, c] (+ bias[c], bias optional) for
  * i < n, c < d: the unpack of received column slices where a consumer wants plain rows (BatchNorm's backward kernels; the

@@ -41,7 +41,8 @@ class CeEpilogue(ctypes.Structure):
     """rgbx_ce_epilogue_t"""
     _fields_ = [("y", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("grad_scale", ctypes.c_void_p),
                 ("stats", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("mask_groups", ctypes.c_int32),
-                ("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int64), ("skip_unselected", ctypes.c_int32)]
+                ("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int64), ("skip_unselected", ctypes.c_int32),
+                ("no_fill", ctypes.c_int32)]
 
 
 class SpmmEpilogue(ctypes.Structure):
@@ -58,7 +59,7 @@ class FusedLayer(ctypes.Structure):
                 ("ldo", _I64), ("out_blk", _P), ("ob_cols", _I64), ("ob_stride", _I64), ("z_out", _P), ("ldz", _I64),
                 ("pre_scale", _P), ("pre_shift", _P), ("pre_rowsum", _P), ("out_colsums", _P), ("stats_ws", _P),
                 ("stats_ws_bytes", ctypes.c_size_t), ("ce", _P), ("N", _I64), ("K", _I64), ("Nout", _I64),
-                ("split", _P), ("w_pos", _P), ("z_pos_out", _P), ("col_sel", _P)]
+                ("split", _P), ("w_pos", _P), ("z_pos_out", _P), ("col_sel", _P), ("col_tag", _P)]
 
 
 # name -> argtypes, exactly the declarations of include/rgbx_hip.h
@@ -93,6 +94,7 @@ SIGNATURES = {
     "rgbx_spmm_linear_f32": [_P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P,
                              ctypes.c_size_t, _P, _I64, _I64, _I64, _P, _P],
     "rgbx_fused_layer_f32": [_P, _P],
+    "rgbx_col_tag_i32": [_P, _P, _I64, _I64, _P, _P],
     "rgbx_blocked_to_rows_f32": [_P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P],
     "rgbx_appnp_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I, _F, _P, _P],
     "rgbx_dagnn_gate_fwd_f32": [_P, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I, _P],

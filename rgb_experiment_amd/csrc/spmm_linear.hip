@@ -98,6 +98,12 @@ struct FusedArgs {
   uint8_t* ce_hit;   // [N]
   // column selection (rgbx_fused_layer_t.col_sel): a slot whose column is not selected is not gathered and adds 0
   const uint8_t* col_sel;
+  // the same selection carried in the column stream (rgbx_fused_layer_t.col_tag, with col_sel only): entry p is col[p] for a
+  // selected column and ~col[p] (negative) for a hole, so the slot's selection costs no load of its own
+  const int* col_tag;
+  // the loss gradient over the row list leaves the unlisted rows of out / z_out unwritten (rgbx_ce_epilogue_t.no_fill):
+  // read by launch() only, which then takes the NOFILL instantiation
+  int ce_no_fill;
 };
 
 __device__ __forceinline__ const float* blocked_at(const float* base, int64_t bc, int64_t bs, int64_t ld, int row,
@@ -494,9 +500,15 @@ __global__ void __launch_bounds__(256) ce_row_records_kernel(const FusedArgs A, 
 // accumulator per lane: 7 waves per SIMD instead of 8.
 // SEL: slots whose column is not selected are not gathered (FusedArgs::col_sel); its own instantiation, so that the
 // plain kernel's scalar registers are what they were.
+// TAG (with SEL): the selection is read from the column stream itself (FusedArgs::col_tag) instead of looked up per slot.
+// NOFILL (with CE): the row-list gradient form leaves the rows between two list entries unwritten
+// (rgbx_ce_epilogue_t.no_fill). Both are instantiations of their own, so that every instantiation that was there before
+// is compiled from the code it was compiled from before (same registers, same schedule).
 template <int G, bool HAS_W, int KC, int NT, bool CE = false, bool DENSE = false, bool BLK = false, bool POS = false,
-          bool SEL = false>
+          bool SEL = false, bool TAG = false, bool NOFILL = false>
 __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_kernel(const FusedArgs A) {
+  static_assert(!TAG || SEL, "TAG is a form of SEL");
+  static_assert(!NOFILL || (CE && !POS && !DENSE), "NOFILL is a form of the loss epilogue over a row list");
   constexpr int NG = kWave / G;
   constexpr int U = 4;
   extern __shared__ float zt[];  // [TM][K + 4]
@@ -541,7 +553,9 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
     if (lr >= TM) break;
     const int row = tile_row<CE>(A, row_base, lr);
     if constexpr (CE && !POS && !DENSE) {  // before the gather starts: nothing of it is live yet
-      if (A.ce_term) ce_fill_gaps(A, row_base + lr, row, lane);
+      if constexpr (!NOFILL) {
+        if (A.ce_term) ce_fill_gaps(A, row_base + lr, row, lane);
+      }
     }
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     float accp[4] = {0.f, 0.f, 0.f, 0.f};  // POS only
@@ -577,13 +591,20 @@ __global__ void __launch_bounds__(256, POS ? 7 : (NT == 2 ? 5 : 8)) spmm_linear_
           int mycol = 0;
           float myw = 0.f, mywp = 0.f;
           if (lane < n) {
-            mycol = A.col[base + lane];
-            if constexpr (HAS_W) myw = A.w[base + lane];
-            if constexpr (POS) mywp = A.w2[base + lane];
             // a column the loss does not select (the ce_select predicate, restated by ops.ce_selection) has a zero row:
             // not gathered, the slot adds fmaf(0, 0, acc) = acc + 0 where the full gather adds fmaf(w >= 0, +0, acc) —
             // same place in the sum, same bits
-            if constexpr (SEL) { if (!A.col_sel[mycol]) mycol = -1; }
+            if constexpr (TAG) {
+              // the selection rides in the entry itself: negative = hole (~col), which `ok` below keeps away from every
+              // address; no look-up in col_sel, and no weight is loaded for a hole
+              mycol = A.col_tag[base + lane];
+              if constexpr (HAS_W) { if (mycol >= 0) myw = A.w[base + lane]; }
+            } else {
+              mycol = A.col[base + lane];
+              if constexpr (HAS_W) myw = A.w[base + lane];
+              if constexpr (POS) mywp = A.w2[base + lane];
+              if constexpr (SEL) { if (!A.col_sel[mycol]) mycol = -1; }
+            }
           }
           for (int k = 0; k < n; k += NG * U) {
             float v[U][4];
@@ -1043,9 +1064,27 @@ int launch(const FusedArgs& A, hipStream_t s) {
     // column selection: the transposed launch of a last layer (Nout <= 128). Elsewhere col_sel is not honoured and every
     // slot is gathered — the same result, as a deselected column's row is 0
     if (A.col_sel && !blk && nt == 1) {
+      if (A.col_tag) {
+        if (A.w) spmm_linear_kernel<G, true, KC, 1, false, false, false, false, true, true><<<(int)blocks, 256, lds, s>>>(A);
+        else spmm_linear_kernel<G, false, KC, 1, false, false, false, false, true, true><<<(int)blocks, 256, lds, s>>>(A);
+        RGBX_CHECK_LAUNCH("spmm_linear_kernel (tagged column selection)");
+        return RGBX_OK;
+      }
       if (A.w) spmm_linear_kernel<G, true, KC, 1, false, false, false, false, true><<<(int)blocks, 256, lds, s>>>(A);
       else spmm_linear_kernel<G, false, KC, 1, false, false, false, false, true><<<(int)blocks, 256, lds, s>>>(A);
       RGBX_CHECK_LAUNCH("spmm_linear_kernel (column selection)");
+      return RGBX_OK;
+    }
+  }
+  if constexpr (!DENSE) {
+    // the row-list gradient form (ce_term: never DENSE, never with w_pos) asked not to fill the gaps of the list; root rows
+    // are row-major here (the entry point refuses blocked ones with w; without w the filling BLK form takes them)
+    if (A.ce_part && A.ce_term && A.ce_no_fill && !blk) {
+      if (A.w)
+        spmm_linear_kernel<G, true, KC, 1, true, false, false, false, false, false, true><<<(int)blocks, 256, lds, s>>>(A);
+      else
+        spmm_linear_kernel<G, false, KC, 1, true, false, false, false, false, false, true><<<(int)blocks, 256, lds, s>>>(A);
+      RGBX_CHECK_LAUNCH("spmm_linear_kernel (cross-entropy epilogue, no fill)");
       return RGBX_OK;
     }
   }
@@ -1154,6 +1193,7 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
   }
   if (L.col_sel && (dense || ce || L.w_pos || L.out_blk || (L.x_root && L.xr_blk_cols > 0)))
     return fail(RGBX_E_ARG, "fused_layer: col_sel needs an aggregating launch without ce, w_pos or blocked layouts");
+  if (L.col_tag && !L.col_sel) return fail(RGBX_E_ARG, "fused_layer: col_tag goes with the col_sel it was made from");
   if ((L.w_pos != nullptr) != (L.z_pos_out != nullptr))
     return fail(RGBX_E_ARG, "fused_layer: w_pos and z_pos_out go together");
   if (L.w_pos) {
@@ -1232,10 +1272,12 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
               x_blk ? L.x_blk_cols : 0, L.x_blk_stride, xr_blk ? L.xr_blk_cols : 0, L.xr_blk_stride,
               L.out_blk, L.ob_cols, L.ob_stride, L.w_pos, L.z_pos_out, zlong_pos};
   A.col_sel = L.col_sel;
+  A.col_tag = L.col_tag;  // read by the column-selection instantiations only (launch()), where col_sel is honoured
   if (ce) {
     A.ce_rows = ce->rows;
     A.ce_n_rows = (int)ce->n_rows;
     A.ce_skip = ce->skip_unselected ? 1 : 0;
+    A.ce_no_fill = ce->no_fill ? 1 : 0;  // only the row-list gradient form has gaps to fill (ce_term below)
     if (ce->rows && ce->grad_scale) {
       if (ce->n_rows == 0) {  // nothing selected: every row is a gap — the in-place skip writes exactly those zeros
         A.ce_rows = nullptr;
@@ -1281,6 +1323,39 @@ extern "C" int rgbx_fused_layer_f32(const rgbx_fused_layer_t* Lp, rgbx_stream_t 
   }
   if (!L.out_colsums) return RGBX_OK;
   return reduce_tile_stats(stats_part, (int)cdiv(N, TM), (int)(2 * Nout), stats_part2, L.out_colsums, N, s);
+}
+
+namespace rgbx {
+namespace {
+
+// rgbx_fused_layer_t.col_tag from a CSR's columns and the selection: the column itself where it is selected, its
+// complement (negative, the column recoverable) where not. A column outside [0, n_cols) counts as not selected and
+// comes out negative either way, so that nothing made here can reach an address.
+__global__ void __launch_bounds__(256)
+col_tag_kernel(const int* __restrict__ col, const uint8_t* __restrict__ sel, int64_t nnz, int n_cols,
+               int* __restrict__ tag) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < nnz; p += stride) {
+    const int c = col[p];
+    const bool in = c >= 0 && c < n_cols;
+    tag[p] = in && sel[c] ? c : (c >= 0 ? ~c : c);
+  }
+}
+
+}  // namespace
+}  // namespace rgbx
+
+extern "C" int rgbx_col_tag_i32(const int32_t* col, const uint8_t* sel, int64_t nnz, int64_t n_cols, int32_t* col_tag,
+                                rgbx_stream_t stream) {
+  if (nnz < 0 || n_cols < 0) return fail(RGBX_E_ARG, "col_tag: bad size");
+  if (nnz == 0) return RGBX_OK;
+  if (!col || !sel || !col_tag) return fail(RGBX_E_ARG, "col_tag: null pointer");
+  if (nnz >= INT32_MAX || n_cols >= INT32_MAX) return fail(RGBX_E_RANGE, "col_tag: nnz / n_cols exceed int32");
+  const int64_t blocks = cdiv(nnz, 256);
+  col_tag_kernel<<<(int)(blocks < 8192 ? blocks : 8192), 256, 0, (hipStream_t)stream>>>(col, sel, nnz, (int)n_cols,
+                                                                                       col_tag);
+  RGBX_CHECK_LAUNCH("col_tag_kernel");
+  return RGBX_OK;
 }
 
 extern "C" int rgbx_ce_rows_grad_scratch_doubles(int64_t N, int64_t* count) {

@@ -869,7 +869,7 @@ def _blocked(t, what):
 
 def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_root=None, pre=None, want_out=True,
                 out_blocked=None, want_z=False, want_colsums=False, ce=None, kind="linear", out=None, z=None, w_pos=None,
-                select_rows=False, col_sel=None):
+                select_rows=False, col_sel=None, ce_fill=True):
     """One conv layer's arithmetic on rgbx_fused_layer_f32 (no autograd):
         z   = rs * sum_p w_p x[col_p]   over `csr`            (csr given: aggregate)
             = x                                                 (csr None: DENSE mode, the rows are loaded)
@@ -887,7 +887,11 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
     runs over the cached list of those rows (selected_rows), and so does a loss-gradient launch (CE_GRAD_ROW_LIST; it
     skips the others in place where there is no list): the z and gradient rows of the others are 0 either way; see
     rgbx_ce_epilogue_t.rows / skip_unselected.
+    `ce_fill=False` (with `select_rows` and a loss gradient): where the launch tiles the row list, the unlisted rows of
+    out and z are left UNWRITTEN (rgbx_ce_epilogue_t.no_fill) — garbage, possibly NaN — instead of 0; for a caller whose
+    every reader of the two walks that list or honours that selection. The other forms write what they always write.
     `col_sel` (uint8 [n_src] or None): slots whose column has a 0 there are not gathered (rgbx_fused_layer_t.col_sel).
+    A vector that came from selected_cols is also carried in the column stream (col_tags, rgbx_fused_layer_t.col_tag).
     Returns (out, z, colsums or stats)."""
     _lib.require_device(x, wt, bias, x_root, wt_root, out_blocked, col_sel)
     lib = _lib.load()
@@ -915,9 +919,13 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
             if col_sel.dtype != torch.uint8 or col_sel.numel() < x.size(0):
                 raise RuntimeError(f"fused_layer: col_sel must be uint8 with an entry per input row, got {col_sel.dtype} "
                                    f"{tuple(col_sel.shape)} for {x.size(0)} rows")
+            tag = col_tags(csr, col_sel)  # a selection of selected_cols: carried in the column stream (None: looked up)
             col_sel = col_sel.contiguous()
             keep.append(col_sel)
             L.col_sel = col_sel.data_ptr()
+            if tag is not None:
+                keep.append(tag)
+                L.col_tag = tag.data_ptr()
         split, _scratch = csr.split_arg(K, x.device, hub_rows=2 if w_pos is not None else 1)
         keep.append(_scratch)
         if split is not None:
@@ -978,6 +986,7 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
                                  _lib.ptr(ce_scratch), groups)
         if rows is not None:
             ce_arg.rows, ce_arg.n_rows = rows.data_ptr(), rows.numel()
+            ce_arg.no_fill = int(not ce_fill and grad_scale is not None)
             keep.append(rows)
         elif select_rows and not dense and w_pos is None and grad_scale is not None:
             ce_arg.skip_unselected = 1
@@ -1050,7 +1059,7 @@ def blocked_to_rows(src, out=None, bias=None):
 
 
 def spmm_linear_raw(csr, w, rs, x, wt, bias=None, want_z=False, x_root=None, wt_root=None, kind="linear", pre=None,
-                    want_colsums=False, ce=None, select_rows=False):
+                    want_colsums=False, ce=None, select_rows=False, ce_fill=True):
     """out = (rs * sum_p w_p x[col_p]) wt + bias (+ x_root wt_root) on the fused aggregate+transform kernel; `wt` /
     `wt_root` are [K, Nout] row-major. Returns (out, z) with z the stored aggregate [N, K] if `want_z`. `pre` = (scale
     [K], shift [K], rowsum [N]): the gathered matrix (and the root rows) stand for x * scale + shift. `want_colsums`:
@@ -1058,10 +1067,10 @@ def spmm_linear_raw(csr, w, rs, x, wt, bias=None, want_z=False, x_root=None, wt_
     `ce` = (y, mask, grad_scale): the layer is the model's last and its logits go straight into the masked
     cross-entropy (rgbx_ce_epilogue_t): returns (out, z, stats) with stats [3] float64 = (nll sum, selected rows,
     correct); out = the loss gradient grad_scale * (softmax - onehot) when grad_scale is a device scalar, None (nothing
-    written) when it is None. `select_rows`: see fused_layer."""
+    written) when it is None. `select_rows`, `ce_fill`: see fused_layer."""
     out, z, extra = fused_layer(x, wt, csr=csr, w=w, rs=rs, bias=bias, x_root=x_root if wt_root is not None else None,
                                 wt_root=wt_root, pre=pre, want_z=want_z, want_colsums=want_colsums, ce=ce, kind=kind,
-                                select_rows=select_rows)
+                                select_rows=select_rows, ce_fill=ce_fill)
     if ce is not None or want_colsums:
         return out, z, extra
     return out, z
@@ -1250,21 +1259,40 @@ class _PropagateLinear(torch.autograd.Function):
         return gx, None, None, gw, gb, None, gwr, None, None, g_bnw, g_bnb, None
 
 
-def _propagate_linear_input_grad(g, kind, gy, weight, root_weight, ce_sel=None):
+def _input_grad_is_fused(weight, root_weight):
+    """The transposed launch of a conv with this weight runs on the fused kernel (_propagate_linear_input_grad)."""
+    n_out, n_in = weight.shape
+    return n_out <= n_in and bool(_lib.load().rgbx_spmm_linear_supported(n_out, n_in, int(root_weight is not None)))
+
+
+def _input_grad_skips_deselected(g, weight, root_weight):
+    """Every slot the transposed launch gathers of dy is a selected one when it is given a col_sel: the fused kernel takes
+    the launch and honours col_sel there (rgbx_fused_layer_t.col_sel: K = the weight's rows in {64, 128, 256}, Nout = its
+    columns <= 128), and the transposed CSR has no hub rows, which gather every slot."""
+    n_out, n_in = weight.shape
+    return (_input_grad_is_fused(weight, root_weight) and n_out in (64, 128, 256) and n_in <= 128
+            and g.bwd.split is None)
+
+
+def _propagate_linear_input_grad(g, kind, gy, weight, root_weight, ce_sel=None, sparse_gy=False):
     """dx = P^T (dy W) + dy Wr = (P^T dy) W + dy Wr: the fused kernel on the transposed CSR (W as stored is already
     the [K, Nout] operand) when in == out, else GEMMs and the transposed SpMM with the root part as its additive
     term. `ce_sel` = (y, mask, C): dy is the loss gradient of the masked cross-entropy, zero outside the rows that loss
     selects; the fused kernel then does not gather those rows (selected_cols; every slot keeps its place in the sum, so
-    the result is the full gather's, bit for bit)."""
+    the result is the full gather's, bit for bit). `sparse_gy`: those rows of dy were never written (the forward ran with
+    ce_fill=False) and MUST not be read: any route that would read them raises."""
     csr = g.bwd
     wt = {"gcn": lambda: g.w_t, "mean": lambda: g.w_mean_t, "sum": lambda: None}[kind]()
     prefix = getattr(g, "event_prefix", "")
-    n_out, n_in = weight.shape
-    if n_out <= n_in and _lib.load().rgbx_spmm_linear_supported(n_out, n_in, int(root_weight is not None)):
+    col_sel = None if ce_sel is None else selected_cols(*ce_sel)
+    if sparse_gy and (col_sel is None or not _input_grad_skips_deselected(g, weight, root_weight)):
+        raise RuntimeError("propagate_linear_ce: the loss gradient was stored without its zero rows, and the transposed "
+                           "launch can no longer skip them (the column selection or the fused route is gone)")
+    if _input_grad_is_fused(weight, root_weight):
         gx, _, _ = fused_layer(gy, weight.detach().contiguous(), csr=csr, w=wt,
                                x_root=gy if root_weight is not None else None,
                                wt_root=None if root_weight is None else root_weight.detach().contiguous(),
-                               col_sel=None if ce_sel is None else selected_cols(*ce_sel), kind=f"{prefix}{kind}_linear_bwd")
+                               col_sel=col_sel, kind=f"{prefix}{kind}_linear_bwd")
         return gx
     gz = gy @ weight
     gr = gy @ root_weight if root_weight is not None else None
@@ -1422,6 +1450,33 @@ def selected_cols(y, mask, C):
     return hit[0].get()
 
 
+_COL_TAGS = {}
+
+
+def col_tags(csr, col_sel):
+    """int32 [nnz] device vector col_sel[col[p]] ? col[p] : ~col[p] (rgbx_col_tag_i32) for a `col_sel` that selected_cols
+    handed out: the selection carried in the column stream of the transposed gather (rgbx_fused_layer_t.col_tag), so that
+    the launch has no per-slot look-up in col_sel. Built once per (the CSR's `col`, selection key) and kept with the
+    tensors it was keyed on, like _SEL_COLS; two entries at most, each 4 * nnz bytes (248 MB at workload L: a run has one
+    training graph and one mask). None — the launch then looks col_sel up per slot, the same result — for any other
+    vector, for an empty CSR, and inside a graph capture where the array does not exist yet."""
+    key = next((k for k, hit in _SEL_COLS.items() if hit[0].value is col_sel), None)
+    if key is None or csr.nnz <= 0:
+        return None
+    key = (csr.col.data_ptr(), csr.nnz, key)
+    hit = _COL_TAGS.get(key)
+    if hit is None or hit[2] is not col_sel:  # (a selection evicted from _SEL_COLS and made again is a new vector)
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        tag = torch.empty(csr.nnz, dtype=torch.int32, device=csr.col.device)
+        _lib.check(_lib.load().rgbx_col_tag_i32(csr.col.data_ptr(), col_sel.data_ptr(), csr.nnz, col_sel.numel(),
+                                                tag.data_ptr(), _lib.stream_ptr()), "rgbx_col_tag_i32")
+        hit = (_MadeOn(tag), csr.col, col_sel)  # the tensors stay alive with their addresses
+        _COL_TAGS[key] = hit
+        while len(_COL_TAGS) > 2:
+            _COL_TAGS.pop(next(iter(_COL_TAGS)))
+    return hit[0].get()
+
 
 def ce_from_logits(logits, y, mask):
     """(loss, stats) of the masked cross-entropy taken from materialised logits: the unfused route of the *_ce
@@ -1463,11 +1518,24 @@ class _PropagateLinearCE(torch.autograd.Function):
         ctx.handed_over = bn_weight is not None and bn_args[4] is not None
         w, rs = (graph.w, None) if kind == "gcn" else (None, graph.inv_deg)
         grad_scale = mask_scale(y, mask, weight.size(0)) if want_grad else None
+        # The zero rows of dlogits and z (0.8 GB per step at workload L) are written only where somebody reads them. Nobody
+        # does when every reader in this node's backward is driven by the row list or the selection: dW / db walk the list
+        # (gemm_tn_rows: the weight wants a gradient, FUSE_DENSE_BACKWARD), there is no root weight (its dWr = dy^T x and
+        # root term read every row of dy), and the transposed launch, if one will run, skips the deselected slots
+        # (_input_grad_skips_deselected) with a selection that exists now. Neither tensor leaves this Function.
+        need_h = ctx.needs_input_grad[0] or (bn_weight is not None and (ctx.needs_input_grad[9] or ctx.needs_input_grad[10]))
+        ce_sel = (y, mask, weight.size(0))
+        no_fill = bool(want_grad and CE_GRAD_ROW_LIST and FUSE_DENSE_BACKWARD and root_weight is None and mask is not None
+                       and ctx.needs_input_grad[3] and selected_rows(*ce_sel) is not None
+                       and selected_rows(*ce_sel).numel() > 0
+                       and (not need_h or (selected_cols(*ce_sel) is not None
+                                           and _input_grad_skips_deselected(graph, weight, None))))
+        ctx.ce_no_fill = no_fill  # the backward holds itself to it
         dlogits, z, stats = spmm_linear_raw(
             graph.fwd, w, rs, x, weight_t(weight), None if bias is None else bias.detach(),
             want_grad and weight.requires_grad, x if root_weight is not None else None,
             None if root_weight is None else weight_t(root_weight), kind=f"{kind}_linear_fwd", pre=pre,
-            ce=(y, mask, grad_scale), select_rows=True)
+            ce=(y, mask, grad_scale), select_rows=True, ce_fill=not no_fill)
         ctx.graph, ctx.kind, ctx.has_bias, ctx.has_bn = graph, kind, bias is not None, bn_weight is not None
         # the saved dy is the loss gradient: zero outside the selected rows, so the backward's transposed gather may skip
         # the rows of those slots (selected_cols)
@@ -1495,10 +1563,17 @@ class _PropagateLinearCE(torch.autograd.Function):
         g = g.reshape(()).float()
         gw = gb = gwr = gx = g_bnw = g_bnb = None
         gcol = None
+        sparse = ctx.ce_no_fill  # the unlisted rows of gy and z were never written: every reader below must skip them
         if ctx.needs_input_grad[3]:  # z was stored by the forward exactly when the weight wants a gradient
             # gy is zero outside the rows the loss selects: the product runs over the list of those rows where it exists
             rows = selected_rows(*ctx.ce_sel) if FUSE_DENSE_BACKWARD else None
-            gw, gcol = gemm_tn_rows(gy, z, rows, colsum=True)
+            if sparse and rows is None:
+                raise RuntimeError("propagate_linear_ce: the loss gradient was stored without its zero rows, and the row "
+                                   "list its weight gradient walks is gone (FUSE_DENSE_BACKWARD switched off since?)")
+            gw, gcol = gemm_tn_rows(gy, z, rows, colsum=True, rows_only=sparse)
+        if sparse and (gcol is None or root_weight is not None):
+            raise RuntimeError("propagate_linear_ce: the loss gradient was stored without its zero rows, but a full pass "
+                               "over it is wanted")
         if ctx.has_bias and ctx.needs_input_grad[4]:
             gb = gcol if gcol is not None else gy.sum(0)
         if root_weight is not None and ctx.needs_input_grad[5]:
@@ -1517,7 +1592,7 @@ class _PropagateLinearCE(torch.autograd.Function):
         sc = dict(zip((k for k, _ in items), torch._foreach_mul([t for _, t in items], g))) if items else {}
         gw, gb, gwr = sc.get("gw"), sc.get("gb"), sc.get("gwr")
         if need_h:
-            g_h = _propagate_linear_input_grad(graph, kind, gy, sc["w"], sc.get("wr"), ce_sel=ctx.ce_sel)
+            g_h = _propagate_linear_input_grad(graph, kind, gy, sc["w"], sc.get("wr"), ce_sel=ctx.ce_sel, sparse_gy=sparse)
             if ctx.has_bn and not ctx.handed_over:
                 gx, g_bnw, g_bnb = B.train_backward(g_h, x, bn_weight, mean, rstd, n, ctx.reduce)
             else:
@@ -3309,13 +3384,16 @@ def gemm_tn_bn_bwd(g, x, mean, rstd, ca, cb, ck, b, colsum=False):
     return out, sums
 
 
-def gemm_tn_rows(a, b, rows, colsum=False):
+def gemm_tn_rows(a, b, rows, colsum=False, rows_only=False):
     """gemm_tn(a, b, colsum=colsum) for an `a` that is zero outside the rows of the ascending int32 device list `rows`
     (selected_rows): only those rows of a and b are read (rgbx_gemm_tn_rows_f32), every non-zero product is added where
     the full product adds it: same result, bit for bit. rows = None, or operands off the 16-byte path: the full
-    product."""
+    product — an error with `rows_only` (the other rows of a and b were never written)."""
     _lib.require_device(a, b)
     if rows is None or not _gemm_tn_v4(a, b) or a.size(0) != b.size(0) or a.size(0) >= 2**31:
+        if rows_only:
+            raise RuntimeError("gemm_tn_rows: the row-list form cannot take these operands and the full product may not "
+                               "read them")
         return gemm_tn(a, b, colsum=colsum)
     K, M, N = a.size(0), a.size(1), b.size(1)
     ws, out, sums = _gemm_tn_buffers(K, M, N, a.device, colsum)
