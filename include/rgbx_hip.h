@@ -32,6 +32,8 @@
  *   rgbx_resgated_*       ResGatedGraphConv (per-channel sigmoid gate) [PyG]; not in the reference's zoo.
  *   rgbx_gine_*           GINEConv (GIN with a feature row per edge: relu(x_j + e_ji) summed) [PyG]; the zoo's
  *                         models/gin.py is its sibling without edge features.
+ *   rgbx_rgcn_*           RGCNConv (a relation per edge: mean per (target, relation), basis decomposition) [PyG]; not
+ *                         in the reference's zoo.
  *   rgbx_softmax_aggr_*   SoftmaxAggregation / GENConv(aggr="softmax") (per-channel softmax at a trained temperature)
  *                         [PyG]; not in the reference's zoo.
  *   rgbx_gemm_tn_f32      dW = dY^T X of the nn.Linear / conv.lin layers under loss.backward()
@@ -938,6 +940,59 @@ int rgbx_gine_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const i
                           int64_t ldx, const float* e, int64_t lde, const float* gout, int64_t ldg, const float* eps,
                           float* g_x, int64_t ldgx, int64_t N, int C, const rgbx_row_split_t* split,
                           rgbx_stream_t stream);
+
+/* ---- RGCNConv: a relation per edge; mean per (target, relation), basis decomposition ------------------------------- */
+
+/* Every edge j -> i carries a category, its relation etype in [0, R) (int32, one per CSR slot; the range is the
+ * caller's contract, checked once when the typed view of a graph is built). RGCNConv.forward [PyG] loops over the
+ * relations, masks the edge list and propagates once per relation (`for i in range(self.num_relations): tmp =
+ * masked_edge_index(edge_index, edge_type == i); h = self.propagate(tmp, x=x_l); out += h @ weight[i]`), with
+ * `weight = (self.comp @ weight.view(num_bases, -1))` in front of the loop under a basis decomposition
+ * (Schlichtkrull et al., "Modeling Relational Data with Graph Convolutional Networks"). The reference's zoo has no
+ * relational layer. Here the dense products come first (h = x @ [V_0 | ... | V_{B-1}], viewed as [N, B, C]) and ONE
+ * pass over the edges mixes the B basis rows of every source with a per-slot, per-basis coefficient
+ *   a[p, b] = w[p] * comp[etype[p], b]
+ * which is neither a softmax nor saved anywhere: `comp` [R, B] (row-major, contiguous) is DEVICE memory read by the
+ * kernels, so a captured launch follows a table that an optimizer moves. The edges are taken as they are
+ * (RGBX_LOOPS_KEEP). No entry point uses float atomics, scratch or LDS; every sum runs in a fixed order (slots of a
+ * lane group in slot order, lane groups, heads of a group, head chunks ascending, hub-row chunks in chunk order): two
+ * runs are bit-identical. Nothing per edge passes between forward and backward. */
+
+/* Slot weights of aggr="mean" per (target, relation):  w[p] = 1.0f / (float)#{p' in the row of p : etype[p'] ==
+ * etype[p]}  (the `aggr='mean'` of the masked propagate above). The count is integer arithmetic and exact; no [N, R]
+ * table is formed, R > 0 is only validated. `split`: hub rows are cut into the plan's chunks, each of which is counted
+ * against its whole row (split->partial is not touched). The same call on the transposed CSR gives no meaningful
+ * weights: take w_t[q] = w[t2f[q]]. */
+int rgbx_rgcn_slot_norm_f32(const int32_t* rowptr, const int32_t* etype, float* w, int64_t N, int R,
+                            const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* 1 if the mix kernels take B bases of C channels (1 <= B <= 64; C as rgbx_gine_supported), else 0. */
+int rgbx_rgcn_mix_supported(int B, int C);
+
+/* Forward over the target-grouped CSR, h [N_src, B*C], out [N, C]:
+ *   out[i,:] = y0[i,:] + sum_p sum_b a[p,b] * h[col[p], b, :]
+ * y0 [N, C] is optional (NULL: zeros) and carries the dense root + bias term, so that out is written once; out must
+ * alias neither h nor y0. A row without slots stores y0 (or zeros). `w` [nnz] is required (ones: aggr="add").
+ * split->partial holds n_chunks * C floats; y0 rides on a row's first chunk. */
+int rgbx_rgcn_mix_fwd_f32(const int32_t* rowptr, const int32_t* col, const int32_t* etype, const float* w,
+                          const float* comp, const float* h, int64_t ldh, const float* y0, int64_t ldy, float* out,
+                          int64_t ldo, int64_t N, int R, int B, int C, const rgbx_row_split_t* split,
+                          rgbx_stream_t stream);
+
+/* Backward, source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i; etype_t / w_t per transposed
+ * slot):  g_h[j,b,:] = sum_q a[q,b] * gout[col_t[q],:],  g_h [N, B*C]. A source without out-edges stores zeros.
+ * split->partial holds n_chunks * B * C floats. */
+int rgbx_rgcn_mix_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* etype_t, const float* w_t,
+                              const float* comp, const float* gout, int64_t ldg, float* g_h, int64_t ldgh, int64_t N,
+                              int R, int B, int C, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward, coefficient side, over the forward CSR:  d[p,b] = w[p] * <h[col[p],b,:], gout[i,:]>,  d [nnz, B]
+ * contiguous, one store per (slot, head) and no sum over slots; g_comp[r,:] is the sum of d[p,:] over the slots of
+ * relation r, which the caller takes with rgbx_spmm_csr_f32 over the slots grouped by relation (a fixed-order sum).
+ * `split` only balances the hub rows (split->partial is not touched). */
+int rgbx_rgcn_mix_bwd_coef_f32(const int32_t* rowptr, const int32_t* col, const float* w, const float* h, int64_t ldh,
+                               const float* gout, int64_t ldg, float* d, int64_t N, int R, int B, int C,
+                               const rgbx_row_split_t* split, rgbx_stream_t stream);
 
 /* ---- Softmax aggregation (GENConv / DeeperGCN): per-channel softmax over the in-edges at a trained temperature ----- */
 

@@ -230,7 +230,8 @@ def experiment(model_init_param: dict, *,
                distributed=None,
                task_split: str = "auto",
                use_edge_weight: bool = False,
-               use_edge_attr: bool = False):
+               use_edge_attr: bool = False,
+               use_edge_type: bool = False):
     """Train + evaluate one model on one graph; returns {'ACC', 'precision_score', 'recall_score',
     'f1_macro', 'f1_micro'} (reference :603-605). ``return_model=True`` (an addition) also returns
     the trained module and the per-epoch curves under 'model' / 'history'. ``use_hip_graph=True`` (an
@@ -276,7 +277,13 @@ def experiment(model_init_param: dict, *,
     ``model_init_param``) and for a caller's ``model=`` whose forward takes ``edge_attr`` (any other model_name:
     ValueError). Not with ``to_undirected_graph`` (that call carries no attributes: ValueError) and not on the partitioned
     route (NotImplementedError). With the flag off a ``Data`` that happens to carry an ``edge_attr`` behaves exactly as
-    one without (``gine`` then fails at its forward, which needs the argument)."""
+    one without (``gine`` then fails at its forward, which needs the argument). ``use_edge_type=True`` (an addition, off by
+    default): ``data.edge_type`` (int64 [E], one relation per edge) goes to the device with the data and into the forward
+    arguments as ``edge_type``, for ``model_name="rgcn"`` (models.RGCN, built with ``num_relations`` and optionally
+    ``num_bases`` in ``model_init_param``) and for a caller's ``model=`` whose forward takes ``edge_type`` (any other
+    model_name: ValueError). Not with ``to_undirected_graph`` (that call carries no types: ValueError) and not on the
+    partitioned route (NotImplementedError). With the flag off a ``Data`` that happens to carry an ``edge_type`` behaves
+    exactly as one without."""
     say = print if print_print else (lambda *a, **k: None)
     say(f"running node classification: {'custom' if specify_data else dataset_name} data, model {model_name}")
 
@@ -309,6 +316,17 @@ def experiment(model_init_param: dict, *,
             raise ValueError("use_edge_attr=True cannot be combined with to_undirected_graph=True: the reference's "
                              "to_undirected call (:235-238) carries no attributes")
 
+    if use_edge_type:
+        if model is not None:
+            if not isinstance(model, nn.Module) or "edge_type" not in inspect.signature(model.forward).parameters:
+                raise ValueError("use_edge_type=True: the forward of the module passed as model= takes no edge_type")
+        elif name != "rgcn":
+            raise ValueError(f"use_edge_type=True: model_name={model_name!r} takes no edge types; the routes that do "
+                             "are rgcn and a model= whose forward takes edge_type")
+        if to_undirected_graph:
+            raise ValueError("use_edge_type=True cannot be combined with to_undirected_graph=True: the reference's "
+                             "to_undirected call (:235-238) carries no types")
+
     # ---- data (reference :179-229) ----------------------------------------------------------
     if not specify_data:
         data = RD2PD(dataset_root=dataset_root, dataset_name=dataset_name, split_method=dataset_split_mode,
@@ -330,6 +348,14 @@ def experiment(model_init_param: dict, *,
             raise ValueError(f"data.edge_attr must have shape [E, D] = [{data.edge_index.size(1)}, D], got "
                              f"{tuple(edge_attr.shape)}")
 
+    if use_edge_type:  # the contract of data.edge_type, checked before any device is touched
+        edge_type = getattr(data, "edge_type", None)
+        if not torch.is_tensor(edge_type) or edge_type.dtype != torch.int64:
+            raise ValueError("use_edge_type=True needs data.edge_type: an int64 tensor of shape [E]")
+        if edge_type.dim() != 1 or edge_type.numel() != data.edge_index.size(1):
+            raise ValueError(f"data.edge_type must have shape [E] = [{data.edge_index.size(1)}], got "
+                             f"{tuple(edge_type.shape)}")
+
     # ---- device (reference :246-258): the message-passing path is HIP-only -------------------
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if distributed is None:  # one of several ranks a launcher started, and a model with a node-partitioned form
@@ -340,6 +366,8 @@ def experiment(model_init_param: dict, *,
         raise NotImplementedError("use_edge_weight=True is not implemented on the partitioned (distributed) route")
     if distributed and use_edge_attr:
         raise NotImplementedError("use_edge_attr=True is not implemented on the partitioned (distributed) route")
+    if distributed and use_edge_type:
+        raise NotImplementedError("use_edge_type=True is not implemented on the partitioned (distributed) route")
     if distributed and model is None and (model_init_param or {}).get("aggr", "mean") != "mean":
         raise NotImplementedError(f"aggr={model_init_param['aggr']!r} is not implemented on the partitioned (distributed) "
                                   "route: its exchange carries sums")
@@ -367,6 +395,7 @@ def experiment(model_init_param: dict, *,
     edge_attr = None
     if use_edge_attr:
         edge_attr = data.edge_attr.detach().to(torch.float32).contiguous()
+    edge_type = data.edge_type.detach().contiguous() if use_edge_type else None
     features = data.x
     if normalize_feature in ("row", "col", "all"):
         features = _normalize_features(features, normalize_feature, normalize_feature_method)
@@ -407,6 +436,8 @@ def experiment(model_init_param: dict, *,
         fwd = {"x": features, "edge_index": data.edge_index} if takes_edges else {"x": features}
         if edge_attr is not None:
             fwd["edge_attr"] = edge_attr
+        if edge_type is not None:
+            fwd["edge_type"] = edge_type
     elif is_pta:  # reference :351-374
         adj = normalized_adjacency(data.edge_index, data.num_nodes)
         idx = [m.nonzero(as_tuple=True)[0] for m in (train_mask, val_mask, test_mask)]
@@ -421,6 +452,8 @@ def experiment(model_init_param: dict, *,
             fwd["edge_weight"] = edge_weight
         if edge_attr is not None:
             fwd["edge_attr"] = edge_attr
+        if edge_type is not None:
+            fwd["edge_type"] = edge_type
     net.to(device)
     uses_graph = name != "mlp" if model is None else "edge_index" in fwd
     if model is not None:  # one eval-mode forward before the loop: the contract of the returned mapping

@@ -776,6 +776,107 @@ class GINEConv(nn.Module):
         return self.nn(out if Cp == C else out[:, :C])
 
 
+class RGCNConv(nn.Module):
+    """Relational graph convolution [PyG RGCNConv; Schlichtkrull et al., "Modeling Relational Data with Graph
+    Convolutional Networks"]: every edge carries a relation, edge_type[e] in [0, num_relations), and
+        out_i = x_i @ root + bias + sum_r AGG_{j : (j -> i) has relation r} x_j @ W_r
+    with AGG the mean per (target, relation) over the edges AS GIVEN (duplicates count twice, self-loops are ordinary
+    edges; a (target, relation) pair without an edge contributes 0, a node without in-edges gets the root term alone), or
+    the sum with aggr="add" / "sum". W_r = weight[r], or sum_b comp[r, b] weight[b] with num_bases=B. Parameter names and
+    shapes are PyG's: weight [num_bases or num_relations, in, out], comp [num_relations, num_bases] (only with
+    num_bases), root [in, out] (root_weight), bias [out]; glorot, bias zeros.
+
+    Both forms run the dense products first and touch the edges once (ops.rgcn_aggregate). Without a basis, the SELECT
+    form: h = x @ [W_0 | ... | W_{R-1}] and the weighted SpMM picks column block type(p) of the source's row. IT
+    MATERIALISES N * R * out FLOATS; num_bases is the answer for large R. With a basis, the MIX form: h = x @ [V_0 | ... |
+    V_{B-1}] and the rgbx_rgcn_mix_* kernels mix the B rows of a source with comp[type(p), :], read on the device. An
+    output width outside the kernels' set is zero-padded and sliced off again; a basis the kernels do not take (more than
+    64 bases, more than 256 channels) composes W_r and runs the select form.
+
+    Refused: num_blocks (NotImplementedError), x=None (featureless input), a tuple in_channels, any other aggr.
+    Out of scope: FastRGCNConv, heterogeneous node types, the node-partitioned (distributed) route."""
+
+    def __init__(self, in_channels, out_channels, num_relations, num_bases=None, *, num_blocks=None, aggr="mean",
+                 root_weight=True, bias=True):
+        super().__init__()
+        if num_blocks is not None:
+            raise NotImplementedError("RGCNConv: num_blocks (the block-diagonal decomposition) is not implemented; "
+                                      "num_bases is")
+        if not isinstance(in_channels, int) or isinstance(in_channels, bool):
+            raise ValueError(f"RGCNConv: in_channels must be one int (got {in_channels!r}): bipartite and featureless "
+                             "inputs are not implemented")
+        if aggr not in ("mean", "add", "sum"):
+            raise ValueError(f"RGCNConv: aggr={aggr!r} (mean, add or sum)")
+        if num_relations < 1 or (num_bases is not None and num_bases < 1):
+            raise ValueError("RGCNConv: num_relations and num_bases must be at least 1")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.num_relations, self.num_bases, self.aggr = num_relations, num_bases, aggr
+        self.weight = nn.Parameter(torch.empty(num_bases or num_relations, in_channels, out_channels))
+        if num_bases is not None:
+            self.comp = nn.Parameter(torch.empty(num_relations, num_bases))
+        else:
+            self.register_parameter("comp", None)
+        if root_weight:
+            self.root = nn.Parameter(torch.empty(in_channels, out_channels))
+        else:
+            self.register_parameter("root", None)
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot_(self.weight)
+        if self.comp is not None:
+            glorot_(self.comp)
+        if self.root is not None:
+            glorot_(self.root)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def mix_channels(self):
+        """The width the mix kernels run at for this layer (out_channels, or the next multiple of 4 where the layout
+        does not take it), or None where the layer runs the select form."""
+        C, B = self.out_channels, self.num_bases
+        if B is None or C > 256:
+            return None
+        Cp = GATConv.kernel_channels(C)
+        return Cp if ops.rgcn_mix_supported(B, Cp) else None
+
+    def forward(self, x, edge_index, edge_type):
+        if x is None:
+            raise ValueError("RGCNConv: x=None (a featureless input) is not implemented")
+        if not torch.is_tensor(edge_type) or edge_type.dtype != torch.int64 or edge_type.dim() != 1 \
+                or edge_type.numel() != edge_index.size(1):
+            got = f"{edge_type.dtype} {tuple(edge_type.shape)}" if torch.is_tensor(edge_type) else type(edge_type).__name__
+            raise ValueError(f"RGCNConv: edge_type must be int64 [E] = [{edge_index.size(1)}], got {got}")
+        if x.dim() != 2 or x.size(1) != self.in_channels:
+            raise ValueError(f"RGCNConv: x {tuple(x.shape)} for in_channels={self.in_channels}")
+        _lib.require_device(x, edge_type)
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        C, R, B = self.out_channels, self.num_relations, self.num_bases
+        pad = torch.nn.functional.pad
+        Cp = self.mix_channels()
+        if Cp is None:
+            w = self.weight if B is None else (self.comp @ self.weight.view(B, -1)).view(R, self.in_channels, C)
+            comp, heads, Cp = None, R, C
+        else:
+            w = self.weight if Cp == C else pad(self.weight, (0, Cp - C))
+            comp, heads = self.comp, B
+        # [in, heads * Cp]: column block k is the k-th matrix
+        h = ops.linear(x, w.permute(0, 2, 1).reshape(heads * Cp, self.in_channels))
+        y0 = None
+        if self.root is not None:
+            y0 = ops.linear(x, self.root.t(), self.bias)
+            y0 = y0 if Cp == C else pad(y0, (0, Cp - C))
+        out = ops.rgcn_aggregate(h, graph, edge_type, R, comp=comp, aggr=self.aggr, y0=y0)
+        out = out if Cp == C else out[:, :C]
+        if self.root is None and self.bias is not None:
+            out = out + self.bias
+        return out
+
+
 class GatedGraphConv(nn.Module):
     """Gated graph convolution: the input (zero-padded to out_channels columns; wider inputs raise) runs through
     num_layers steps of m = x weight[i], agg_i = sum_{j -> i} m_j (edges as given, duplicates counted, no loops added,

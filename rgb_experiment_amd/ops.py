@@ -3033,6 +3033,263 @@ def gine_aggregate(x, e_slot, graph, eps=None):
     return _GINEAggregate.apply(x, e_slot, eps, graph)
 
 
+_TYPED_VIEWS_MAX = 4  # cached typed views per graph (each holds a handful of [E] vectors)
+
+
+class TypedView:
+    """What a relation per edge adds to a LOOPS_KEEP graph (typed_view builds it): `etype_f` / `etype_t` int32, the
+    relation of every forward / transposed CSR slot; `w_f` / `w_t` float32, the slot weights of the mean per (target,
+    relation), w_f[p] = 1 / #{p' in the row of p with p's relation} (rgbx_rgcn_slot_norm_f32) and w_t = w_f[t2f];
+    `ones` for aggr="add"; `rel`, the forward slots grouped by relation as a CSR of R rows (rel_ptr [R + 1], rel_slots
+    [E], a stable grouping: slot order inside a relation), which the reduction of g_comp walks. `select` holds the index
+    sets of the select form and is built on first use."""
+
+    def __init__(self, graph, R, etype_f, etype_t, w_f, w_t, rel, etype_edge):
+        self.graph, self.R = graph, R
+        self.etype_f, self.etype_t, self.w_f, self.w_t, self.rel = etype_f, etype_t, w_f, w_t, rel
+        self.ones = torch.ones_like(w_f)
+        self._etype_edge = etype_edge  # int64 [E], per input edge
+        self._select = None
+
+    def weights(self, aggr, transposed=False):
+        if aggr != "mean":
+            return self.ones
+        return self.w_t if transposed else self.w_f
+
+    @property
+    def select(self):
+        """(fwd, bwd, w_bwd) of the select form. fwd: the forward CSR with col'[p] = col[p] * R + type(p), which reads
+        row (j, r) of h viewed as [N * R, C]. bwd: the relation-expanded transposed CSR of N * R rows, row j * R + r
+        holding the out-edges of j with relation r (rgbx_csr_build on the keys j * R + r, with its own hub plan); w_bwd:
+        the mean weights in its slot order. Built on first use, once per view (a CSR build: its read-backs of the slot count
+        and the longest row happen here, not in a step)."""
+        if self._select is None:
+            from .graph import CSR, LOOPS_KEEP, build_csr
+            g, R = self.graph, self.R
+            E = g.fwd.nnz
+            col = (g.fwd.col[:max(E, 1)].long() * R + self.etype_f.long()).to(torch.int32).contiguous()
+            fwd = CSR(g.fwd.rowptr, col, None, g.fwd.N, E, g.fwd.split)
+            bwd = build_csr(g._src * R + self._etype_edge, g._dst, g.N * R, LOOPS_KEEP)
+            if E:
+                w_bwd = self.w_f[_slot_to_edge(g)[1][bwd.perm[:E].long()].long()].contiguous()
+            else:
+                w_bwd = self.w_f
+            self._select = (fwd, bwd, w_bwd)
+        return self._select
+
+
+def typed_view(graph, edge_type, num_relations):
+    """The TypedView of `graph` under `edge_type` (int64 [E], one relation in [0, num_relations) per INPUT edge), cached on
+    the graph per (storage, shape, in-place version, R), at most 4 entries. Only for graphs in mode LOOPS_KEEP, where every
+    input edge owns exactly one slot; other modes and the partitioned graph raise, as edge_rows_to_slots does. A relation
+    outside the range is refused here, once: the one device synchronisation of the typed path, paid per cache entry (the
+    same read-back brings the slot count of every relation, from which the hub plan of `rel` is laid out on the host)."""
+    from .graph import CSR, LOOPS_KEEP, make_row_split
+    if _is_dist(graph):
+        raise RuntimeError("edge types have no node-partitioned form: run it on one GPU")
+    if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
+        raise RuntimeError("typed_view: only a graph in mode LOOPS_KEEP maps every input edge to exactly one CSR slot "
+                           f"(got loops_mode={getattr(graph, 'loops_mode', None)!r})")
+    R = int(num_relations)
+    if R <= 0:
+        raise ValueError(f"typed_view: num_relations must be positive, got {num_relations}")
+    if not torch.is_tensor(edge_type) or edge_type.dtype != torch.int64 or edge_type.dim() != 1 \
+            or edge_type.numel() != graph.E:
+        got = f"{edge_type.dtype} {tuple(edge_type.shape)}" if torch.is_tensor(edge_type) else type(edge_type).__name__
+        raise ValueError(f"typed_view: edge_type must be int64 [E] = [{graph.E}], got {got}")
+    _lib.require_device(edge_type)
+    if graph.fwd.nnz != graph.E:
+        raise RuntimeError(f"typed_view: {graph.fwd.nnz} CSR slots for {graph.E} input edges")
+    cache = graph.__dict__.setdefault("_typed_views", {})
+    key = (edge_type.data_ptr(), tuple(edge_type.shape), edge_type._version, R)
+    hit = cache.get(key)
+    if hit is not None:
+        return hit[1]
+    dev, E = graph.fwd.rowptr.device, graph.E
+    if E:
+        et = edge_type.detach().contiguous()
+        counts = torch.bincount(et.clamp(0, R - 1), minlength=R)
+        host = torch.cat([et.min().reshape(1), et.max().reshape(1), counts]).cpu()  # the one synchronisation
+        lo, hi = int(host[0]), int(host[1])
+        if lo < 0 or hi >= R:
+            raise ValueError(f"edge_type values [{lo}, {hi}] outside [0, num_relations) = [0, {R})")
+        t2f = graph.t2f.long()
+        etype_f = et[_slot_to_edge(graph)[0].long()].to(torch.int32).contiguous()
+        etype_t = etype_f[t2f].contiguous()
+        w_f = torch.empty(E, dtype=torch.float32, device=dev)
+        split_ref, _, _scratch = _attn_split(graph.fwd, 1, dev)  # the plan only: the count leaves no chunk record
+        with _Timed("rgcn_slot_norm"):
+            _lib.check(_lib.load().rgbx_rgcn_slot_norm_f32(_lib.ptr(graph.fwd.rowptr), _lib.ptr(etype_f), _lib.ptr(w_f),
+                                                           graph.fwd.N, R, split_ref, _lib.stream_ptr()),
+                       "rgbx_rgcn_slot_norm_f32")
+        w_t = w_f[t2f].contiguous()
+        rel_ptr = torch.zeros(R + 1, dtype=torch.int64)
+        rel_ptr[1:] = torch.cumsum(host[2:], 0)
+        plan = make_row_split(rel_ptr)  # on the host: no further read-back
+        if plan is not None:
+            plan = {k: v.to(dev) if torch.is_tensor(v) else v for k, v in plan.items()}
+        rel_slots = torch.sort(etype_f, stable=True)[1].to(torch.int32).contiguous()
+        rel = CSR(rel_ptr.to(torch.int32).to(dev), rel_slots, None, R, E, plan)
+    else:  # no slot is ever read: one-element placeholders the entry points accept
+        et = edge_type.detach()
+        etype_f = etype_t = torch.zeros(1, dtype=torch.int32, device=dev)
+        w_f = w_t = torch.ones(1, dtype=torch.float32, device=dev)
+        rel = CSR(torch.zeros(R + 1, dtype=torch.int32, device=dev), etype_f, None, R, 0, None)
+    view = TypedView(graph, R, etype_f, etype_t, w_f, w_t, rel, et)
+    cache[key] = (edge_type, view)  # the key holds the tensor's data_ptr: keep its storage alive beside the view
+    while len(cache) > _TYPED_VIEWS_MAX:
+        cache.pop(next(iter(cache)))
+    return view
+
+
+class _RGCNSelect(torch.autograd.Function):
+    """RGCNConv's aggregation without a basis: h = x @ [W_0 | ... | W_{R-1}] viewed as [N * R, C], and the existing
+    weighted SpMM with col' = col * R + type; backward = the same SpMM over the relation-expanded transposed CSR."""
+
+    @staticmethod
+    def forward(ctx, h, y0, view, aggr):
+        N, R = view.graph.fwd.N, view.R
+        C = h.size(1) // R
+        fwd = view.select[0]
+        hv = h.contiguous().view(N * R, C)
+        w = view.w_f if aggr == "mean" else None
+        ctx.view, ctx.aggr, ctx.C = view, aggr, C
+        if y0 is None:
+            return spmm_raw(fwd, w, None, hv, kind="rgcn_select_fwd")
+        return spmm_raw(fwd, w, None, hv, y=y0.contiguous(), a=1.0, b=1.0, kind="rgcn_select_fwd")
+
+    @staticmethod
+    def backward(ctx, gout):
+        view, need = ctx.view, ctx.needs_input_grad
+        g_h = None
+        if need[0]:
+            _, bwd, w_bwd = view.select
+            g_h = spmm_raw(bwd, w_bwd if ctx.aggr == "mean" else None, None, gout.contiguous(), kind="rgcn_select_bwd")
+            g_h = g_h.view(view.graph.fwd.N, view.R * ctx.C)
+        return g_h, (gout if need[1] else None), None, None
+
+
+class _RGCNMix(torch.autograd.Function):
+    """RGCNConv's aggregation under a basis decomposition as one autograd node: out = y0 + sum_p sum_b w[p]
+    comp[type(p), b] h[col[p], b, :] in rgbx_rgcn_mix_fwd_f32; backward = the source pass over the transposed CSR (g_h,
+    only when h asks), the coefficient pass over the forward CSR plus the fixed-order reduction by relation (g_comp, only
+    when comp asks), g_y0 = gout. Saves h and comp and nothing per edge; the kernels read comp on the device."""
+
+    @staticmethod
+    def forward(ctx, h, comp, y0, view, aggr):
+        _lib.require_device(h, comp, y0)
+        lib = _lib.load()
+        R, B = comp.shape
+        C = h.size(1) // B
+        g = view.graph
+        csr, N, dev = g.fwd, g.fwd.N, h.device
+        vec = _head_vec(C)
+        h = _rows_on_grid(h, vec)
+        compv = comp.detach().contiguous()  # a contiguous parameter's own storage: a captured launch follows it
+        y = None if y0 is None else _rows_on_grid(y0, vec)
+        out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written
+        ph, ldh = _lib.mat(h, "h")
+        py, ldy = (0, 0) if y is None else _lib.mat(y, "y0")
+        po, ldo = _lib.mat(out, "out")
+        split_ref, _, _scratch = _attn_split(csr, C, dev)
+        with _Timed("rgcn_mix_fwd"):
+            _lib.check(lib.rgbx_rgcn_mix_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(view.etype_f),
+                                                 _lib.ptr(view.weights(aggr)), _lib.ptr(compv), ph, ldh, py, ldy, po, ldo,
+                                                 N, R, B, C, split_ref, _lib.stream_ptr()), "rgbx_rgcn_mix_fwd_f32")
+        ctx.view, ctx.aggr, ctx.dims = view, aggr, (R, B, C)
+        ctx.save_for_backward(h, compv)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, compv = ctx.saved_tensors
+        view, aggr, (R, B, C) = ctx.view, ctx.aggr, ctx.dims
+        g = view.graph
+        lib = _lib.load()
+        N, dev = g.fwd.N, h.device
+        need = ctx.needs_input_grad
+        gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
+        pg, ldg = _lib.mat(gout, "gout")
+        g_h = g_comp = None
+        if need[0]:
+            g_h = torch.empty((N, B * C), dtype=torch.float32, device=dev)  # every row is written (no out-edge: zeros)
+            pgh, ldgh = _lib.mat(g_h, "g_h")
+            split_ref, _, _scratch = _attn_split(g.bwd, B * C, dev)
+            with _Timed("rgcn_mix_bwd_src"):
+                _lib.check(
+                    lib.rgbx_rgcn_mix_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(view.etype_t),
+                                                  _lib.ptr(view.weights(aggr, True)), _lib.ptr(compv), pg, ldg, pgh, ldgh,
+                                                  N, R, B, C, split_ref, _lib.stream_ptr()), "rgbx_rgcn_mix_bwd_src_f32")
+        if need[1]:
+            nnz = g.fwd.nnz
+            if nnz:
+                d = torch.empty((nnz, B), dtype=torch.float32, device=dev)  # every (slot, head) is written
+                ph, ldh = _lib.mat(h, "h")
+                split_ref, _, _scratch2 = _attn_split(g.fwd, 1, dev)  # the plan only: this pass leaves no chunk record
+                with _Timed("rgcn_mix_bwd_coef"):
+                    _lib.check(
+                        lib.rgbx_rgcn_mix_bwd_coef_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col),
+                                                       _lib.ptr(view.weights(aggr)), ph, ldh, pg, ldg, _lib.ptr(d), N, R,
+                                                       B, C, split_ref, _lib.stream_ptr()), "rgbx_rgcn_mix_bwd_coef_f32")
+                g_comp = spmm_raw(view.rel, None, None, d, kind="rgcn_comp_reduce")  # a relation without slots: zeros
+            else:
+                g_comp = torch.zeros((R, B), dtype=torch.float32, device=dev)
+        return g_h, g_comp, (gout if need[2] else None), None, None
+
+
+def rgcn_mix_supported(B, C):
+    return bool(_lib.load().rgbx_rgcn_mix_supported(B, C))
+
+
+_RGCN_AGGRS = {"mean": "mean", "add": "add", "sum": "add"}
+
+
+def rgcn_aggregate(h, graph, edge_type, num_relations, comp=None, aggr="mean", y0=None):
+    """RGCNConv's aggregation over a LOOPS_KEEP graph whose input edge e has relation edge_type[e] (int64 [E], values in
+    [0, num_relations)); the edges as given: duplicates count twice, self-loops are ordinary edges, a (target, relation)
+    pair without an edge contributes 0. `aggr` "mean" is the mean per (target, relation), "add" / "sum" the sum. `y0`
+    [N, C] (optional) is added to every row: the layer's dense root + bias term, so that the output is written once.
+
+    Select form (comp=None): h [N, R * C] = x @ [W_0 | ... | W_{R-1}]; out_i = y0_i + sum_p w[p] h[col[p], type(p), :]
+    through the weighted SpMM with col' = col * R + type, its gradient through the same SpMM over the relation-expanded
+    transposed CSR. IT MATERIALISES N * R * C FLOATS (h, and as many again for its gradient); a basis decomposition is the
+    answer for large R. N * R >= 2^31 is refused before any launch.
+
+    Mix form (comp [R, B], float32, on the device; it may take a gradient): h [N, B * C] = x @ [V_0 | ... | V_{B-1}];
+    out_i = y0_i + sum_p sum_b w[p] comp[type(p), b] h[col[p], b, :] in the rgbx_rgcn_mix_* kernels, which read comp from
+    device memory. Gradients for h, comp and y0, each pass only when asked for; nothing per edge is saved. No float
+    atomics in either form: two runs are bit-identical. Timing names: rgcn_select_fwd / rgcn_select_bwd; rgcn_mix_fwd,
+    rgcn_mix_bwd_src, rgcn_mix_bwd_coef, rgcn_comp_reduce."""
+    if _is_dist(graph):
+        raise RuntimeError("RGCNConv has no node-partitioned form: run it on one GPU")
+    if aggr not in _RGCN_AGGRS:
+        raise ValueError(f"rgcn_aggregate: aggr={aggr!r} (mean, add or sum)")
+    aggr = _RGCN_AGGRS[aggr]
+    R = int(num_relations)
+    N = graph.fwd.N
+    heads = R if comp is None else (comp.size(1) if comp.dim() == 2 else -1)
+    if comp is not None and (comp.dim() != 2 or comp.size(0) != R or comp.dtype != torch.float32):
+        raise RuntimeError(f"rgcn_aggregate: comp {comp.dtype} {tuple(comp.shape)} (float32 [num_relations, num_bases] = "
+                           f"[{R}, B])")
+    if h.dim() != 2 or h.size(0) != N or heads <= 0 or h.size(1) % heads or h.size(1) == 0 or h.dtype != torch.float32:
+        raise RuntimeError(f"rgcn_aggregate: h {h.dtype} {tuple(h.shape)} for a graph of {N} nodes and {heads} "
+                           f"{'relations' if comp is None else 'bases'} (float32 [N, {heads} * C])")
+    C = h.size(1) // heads
+    if y0 is not None and (tuple(y0.shape) != (N, C) or y0.dtype != torch.float32):
+        raise RuntimeError(f"rgcn_aggregate: y0 {y0.dtype} {tuple(y0.shape)} (float32 [N, C] = [{N}, {C}])")
+    if comp is None and N * R >= 2 ** 31:
+        raise RuntimeError(f"rgcn_aggregate: the select form indexes N * R = {N} * {R} rows, beyond int32; use a basis "
+                           "decomposition (num_bases)")
+    _lib.require_device(h, comp, y0)
+    if comp is not None and not rgcn_mix_supported(heads, C):
+        raise RuntimeError(f"rgcn_aggregate: {heads} bases of {C} channels: the kernels take 1 <= B <= 64 and any "
+                           "C <= 64, even C <= 128 or C % 4 == 0 up to 256; pad the width (RGCNConv does)")
+    view = typed_view(graph, edge_type, R)
+    if comp is None:
+        return _RGCNSelect.apply(h, y0, view, aggr)
+    return _RGCNMix.apply(h, comp, y0, view, aggr)
+
+
 class _SoftmaxAggregate(torch.autograd.Function):
     """One softmax aggregation as a single autograd node: a softmax per channel over the in-edges at temperature t, fused
     with the sum of the weighted message rows; backward = one pass over the transposed CSR (g_m, and the g_t records
