@@ -994,6 +994,74 @@ int rgbx_rgcn_mix_bwd_coef_f32(const int32_t* rowptr, const int32_t* col, const 
                                const float* gout, int64_t ldg, float* d, int64_t N, int R, int B, int C,
                                const rgbx_row_split_t* split, rgbx_stream_t stream);
 
+/* ---- GMMConv / MoNet: a trained Gaussian mixture over the pseudo-coordinates of every edge --------------------------- */
+
+/* Every edge j -> i carries D pseudo-coordinates, e [nnz, D] with one row PER SLOT of the target-grouped CSR (its own
+ * pointer and leading dimension). GMMConv.message [PyG] (separate_gaussians=False) forms, per edge,
+ * `gaussian = -0.5 * (edge_attr.view(E, 1, D) - self.mu.view(1, K, D)).pow(2)`,
+ * `gaussian = gaussian / (EPS + self.sigma.view(1, K, D).pow(2))`, `gaussian = torch.exp(gaussian.sum(dim=-1))` and
+ * returns `(x_j.view(E, K, M) * gaussian.view(E, K, 1)).sum(dim=-2)`: an [E, K, D] and an [E, K, M] tensor (Monti et al.,
+ * "Geometric deep learning on graphs and manifolds using mixture model CNNs"). The reference's zoo has no such layer.
+ * Here the dense product comes first (h = x @ g viewed as [N, K, M], k-major columns) and ONE pass over the edges
+ * evaluates, in registers,
+ *   gauss[p, k] = exp(-0.5 * sum_d (e[p,d] - mu[k,d])^2 * inv[k,d]),   inv[k,d] = 1 / (1e-15 + sigma[k,d]^2)
+ * from `mu` and `sigma` [K, D] (row-major, contiguous) in DEVICE memory, so a captured launch follows the parameters an
+ * optimizer moves; no [nnz, K] coefficient table passes from forward to backward. The edges are taken as they are
+ * (RGBX_LOOPS_KEEP). No entry point uses float atomics, scratch or LDS; every sum runs in a fixed order (slots of a lane
+ * group in slot order, lane groups, heads of a group, head chunks ascending, hub-row chunks in chunk order; the parameter
+ * gradients over slot ranges of a fixed length, the ranges in ascending order): two runs are bit-identical. */
+
+/* 1 if the kernels take K Gaussian kernels of M channels over D coordinates (1 <= K <= 64; M as rgbx_gine_supported;
+ * 1 <= D <= 8), else 0. Anything else is refused with RGBX_E_SHAPE before any launch. */
+int rgbx_gmm_supported(int K, int M, int D);
+
+/* Forward over the target-grouped CSR, h [N_src, K*M], out [N, M]:
+ *   out[i,:] = y0[i,:] + rs[i] * sum_p sum_k gauss[p,k] * h[col[p], k, :]
+ * `rs` [N] is optional: 1 / max(indeg, 1) gives aggr="mean", NULL the sum. y0 [N, M] is optional (NULL: zeros) and
+ * carries the dense root + bias term, so that out is written once; out must alias none of h, y0, e. A row without slots
+ * stores y0 (or zeros). split->partial holds n_chunks * M floats; y0 rides on a row's first chunk. */
+int rgbx_gmm_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* e, int64_t lde, const float* mu,
+                     const float* sigma, const float* rs, const float* h, int64_t ldh, const float* y0, int64_t ldy,
+                     float* out, int64_t ldo, int64_t N, int K, int M, int D, const rgbx_row_split_t* split,
+                     rgbx_stream_t stream);
+
+/* Backward, source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i, t2f [nnz] = the forward slot of
+ * every transposed slot, through which the e row is gathered; w_t [nnz] = rs[col_t[q]] for the mean, NULL for the sum):
+ *   g_h[j,k,:] = sum_q w_t[q] * gauss[t2f[q], k] * gout[col_t[q], :],  g_h [N, K*M].
+ * A source without out-edges stores zeros. split->partial holds n_chunks * K * M floats. */
+int rgbx_gmm_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const float* w_t,
+                         const float* e, int64_t lde, const float* mu, const float* sigma, const float* gout,
+                         int64_t ldg, float* g_h, int64_t ldgh, int64_t N, int K, int M, int D,
+                         const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Bytes of workspace rgbx_gmm_bwd_edge_f32 needs: the table s [nnz, K] and one record of 2 K D floats per slot range of
+ * the parameter reduction. */
+int rgbx_gmm_bwd_edge_workspace_bytes(int64_t nnz, int K, int D, size_t* bytes);
+
+/* Backward, edge side, over the forward CSR. With s[p,k] = rs[i] * gauss[p,k] * <h[col[p],k,:], gout[i,:]> (stored per
+ * (slot, head) in the workspace) and t[p,k,d] = (e[p,d] - mu[k,d]) * inv[k,d]:
+ *   g_e[p,d]     = -sum_k s[p,k] * t[p,k,d]                     one row per slot, [nnz, D] with leading dimension ldge
+ *   g_mu[k,d]    =  sum_p s[p,k] * t[p,k,d]                     [K, D] contiguous
+ *   g_sigma[k,d] =  sum_p s[p,k] * t[p,k,d]^2 * sigma[k,d]      [K, D] contiguous
+ * g_e NULL skips the first, g_mu and g_sigma NULL (both or neither) the other two; all three NULL launches nothing. The
+ * sums over p run per slot range (a fixed number of consecutive slots, a function of nnz alone), per lane in slot
+ * order, and the ranges are added in ascending order. `split` only balances the hub rows (split->partial is not
+ * touched). `workspace`: rgbx_gmm_bwd_edge_workspace_bytes(nnz, K, D) bytes, 4-byte aligned. nnz = 0 stores zeros in
+ * g_mu and g_sigma. */
+int rgbx_gmm_bwd_edge_f32(const int32_t* rowptr, const int32_t* col, const float* e, int64_t lde, const float* mu,
+                          const float* sigma, const float* rs, const float* h, int64_t ldh, const float* gout,
+                          int64_t ldg, float* g_e, int64_t ldge, float* g_mu, float* g_sigma, void* workspace,
+                          size_t workspace_bytes, int64_t N, int64_t nnz, int K, int M, int D,
+                          const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* The MoNet paper's pseudo-coordinates of a graph without edge attributes, u [nnz, 2] contiguous in forward slot order:
+ *   u[p] = (1 / sqrt(1 + indeg(col[p])), 1 / sqrt(1 + indeg(i)))  for slot p of row i, indeg(v) = rowptr[v+1] - rowptr[v]
+ * (the paper's `deg^-1/2` coordinates, for which PyG's examples apply `T.Cartesian` / a degree transform on the host).
+ * The + 1 keeps a source without in-edges finite. Needs a square CSR (every col[p] < N). `split`: hub rows are cut
+ * into the plan's chunks (split->partial is not touched). */
+int rgbx_gmm_degree_pseudo_f32(const int32_t* rowptr, const int32_t* col, float* u, int64_t N,
+                               const rgbx_row_split_t* split, rgbx_stream_t stream);
+
 /* ---- Softmax aggregation (GENConv / DeeperGCN): per-channel softmax over the in-edges at a trained temperature ----- */
 
 /* For an edge j -> i (p = its slot in the target-grouped CSR), with messages m [N, C] (its own pointer and leading

@@ -156,6 +156,13 @@ SIGNATURES = {
     "rgbx_rgcn_mix_fwd_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],
     "rgbx_rgcn_mix_bwd_src_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],
     "rgbx_rgcn_mix_bwd_coef_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _P, _P],
+    "rgbx_gmm_supported": [_I, _I, _I],
+    "rgbx_gmm_fwd_f32": [_P, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],
+    "rgbx_gmm_bwd_src_f32": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],
+    "rgbx_gmm_bwd_edge_workspace_bytes": [_I64, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
+    "rgbx_gmm_bwd_edge_f32": [_P, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, ctypes.c_size_t,
+                              _I64, _I64, _I, _I, _I, _P, _P],
+    "rgbx_gmm_degree_pseudo_f32": [_P, _P, _P, _I64, _P, _P],
     "rgbx_softmax_aggr_supported": [_I],
     "rgbx_softmax_aggr_fwd_f32": [_P, _P, _P, _I64, _P, _I, _P, _I64, _P, _I64, _I64, _I, _P, _P],
     "rgbx_softmax_aggr_gt_partial_floats": [_I64, _I, _P, ctypes.POINTER(ctypes.c_int64)],

@@ -877,6 +877,107 @@ class RGCNConv(nn.Module):
         return out
 
 
+class GMMConv(nn.Module):
+    """Gaussian mixture model convolution [PyG GMMConv; Monti et al., "Geometric deep learning on graphs and manifolds
+    using mixture model CNNs" (MoNet)]: every edge carries `dim` pseudo-coordinates, edge_attr [E, dim], and
+        gauss[e, k] = exp(sum_d -0.5 (edge_attr[e, d] - mu[k, d])^2 / (1e-15 + sigma[k, d]^2))
+        out_i       = root(x_i) + bias + AGG_{j -> i} sum_k gauss[e, k] (x_j @ g)[k, :]
+    with x @ g viewed as [N, kernel_size, out_channels] (k-major columns, PyG's x_j.view(E, K, M)) and AGG the mean
+    (PyG's default) or the sum ("add" / "sum") over the edges AS GIVEN: self-loops stay, duplicates count twice, a node
+    without in-edges gets the root term alone. Parameter names and shapes are PyG's: g [in, out * kernel_size], mu and
+    sigma [kernel_size, dim], root.weight [out, in] (a bias-free Linear, with root_weight), bias [out]; glorot, bias
+    zeros.
+
+    The dense product runs first, the root term and the bias are folded into the aggregation's output (y0), the attribute
+    rows are permuted into CSR slot order once at their raw width (ops.edge_rows_to_slots), and the mixture itself runs in
+    the rgbx_gmm_* kernels (ops.gmm_aggregate), which read mu and sigma on the device: no [E, K, dim] or [E, K, out]
+    tensor exists. An out_channels outside the kernels' widths is zero-padded and sliced off again.
+
+    Refused: separate_gaussians=True (NotImplementedError); a tuple in_channels, an aggr other than mean / add / sum,
+    dim > 8, kernel_size > 64, out_channels > 256, an edge_attr that is not float32 [E, dim] (ValueError).
+    Out of scope: bipartite inputs, the node-partitioned (distributed) route."""
+
+    def __init__(self, in_channels, out_channels, dim, kernel_size, separate_gaussians=False, aggr="mean",
+                 root_weight=True, bias=True):
+        super().__init__()
+        if separate_gaussians:
+            raise NotImplementedError("GMMConv: separate_gaussians=True (one mixture per input channel) is not "
+                                      "implemented")
+        if not isinstance(in_channels, int) or isinstance(in_channels, bool):
+            raise ValueError(f"GMMConv: in_channels must be one int (got {in_channels!r}): bipartite inputs are not "
+                             "implemented")
+        if aggr not in ("mean", "add", "sum"):
+            raise ValueError(f"GMMConv: aggr={aggr!r} (mean, add or sum)")
+        if not 1 <= dim <= 8:
+            raise ValueError(f"GMMConv: dim={dim}: the kernels take 1 to 8 pseudo-coordinates per edge")
+        if not 1 <= kernel_size <= 64:
+            raise ValueError(f"GMMConv: kernel_size={kernel_size}: the kernels take 1 to 64 Gaussian kernels")
+        if not 1 <= out_channels <= 256:
+            raise ValueError(f"GMMConv: out_channels={out_channels}: the kernels take 1 to 256 channels per kernel")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.dim, self.kernel_size, self.separate_gaussians, self.aggr = dim, kernel_size, False, aggr
+        self.g = nn.Parameter(torch.empty(in_channels, out_channels * kernel_size))
+        self.mu = nn.Parameter(torch.empty(kernel_size, dim))
+        self.sigma = nn.Parameter(torch.empty(kernel_size, dim))
+        if root_weight:
+            self.root = Linear(in_channels, out_channels, bias=False)
+        else:
+            self.register_parameter("root", None)
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot_(self.g)
+        glorot_(self.mu)
+        glorot_(self.sigma)
+        if self.root is not None:
+            glorot_(self.root.weight)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def kernel_channels(self):
+        """The width per Gaussian kernel the aggregation runs at: out_channels, or the next multiple of 4 where the lane
+        layout does not take it."""
+        return GATConv.kernel_channels(self.out_channels)
+
+    def forward(self, x, edge_index, edge_attr):
+        E = edge_index.size(1)
+        if not torch.is_tensor(edge_attr) or edge_attr.dim() != 2 or tuple(edge_attr.shape) != (E, self.dim) \
+                or edge_attr.dtype != torch.float32:
+            got = f"{edge_attr.dtype} {tuple(edge_attr.shape)}" if torch.is_tensor(edge_attr) else type(edge_attr).__name__
+            raise ValueError(f"GMMConv: edge_attr must be float32 [E, dim] = [{E}, {self.dim}], got {got}")
+        if x.dim() != 2 or x.size(1) != self.in_channels:
+            raise ValueError(f"GMMConv: x {tuple(x.shape)} for in_channels={self.in_channels}")
+        _lib.require_device(x, edge_attr)
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        e_slot = ops.edge_rows_to_slots(edge_attr, graph)
+        return self.forward_slots(x, graph, e_slot)
+
+    def forward_slots(self, x, graph, e_slot):
+        """The layer on pseudo-coordinates that are already in the forward CSR slot order of `graph` (a LOOPS_KEEP
+        graph): e_slot [nnz, dim] float32, what ops.edge_rows_to_slots or ops.degree_pseudo return."""
+        if x.dim() != 2 or x.size(1) != self.in_channels:
+            raise ValueError(f"GMMConv: x {tuple(x.shape)} for in_channels={self.in_channels}")
+        _lib.require_device(x, e_slot)
+        M, K = self.out_channels, self.kernel_size
+        Mp = self.kernel_channels()
+        pad = torch.nn.functional.pad
+        g = self.g if Mp == M else pad(self.g.view(self.in_channels, K, M), (0, Mp - M)).reshape(self.in_channels, K * Mp)
+        h = ops.linear(x, g.t())  # [N, K * Mp]: column block k is the k-th kernel's product
+        y0 = None
+        if self.root is not None:
+            y0 = ops.linear(x, self.root.weight, self.bias)
+            y0 = y0 if Mp == M else pad(y0, (0, Mp - M))
+        out = ops.gmm_aggregate(h, e_slot, self.mu, self.sigma, graph, aggr=self.aggr, y0=y0)
+        out = out if Mp == M else out[:, :M]
+        if self.root is None and self.bias is not None:
+            out = out + self.bias
+        return out
+
+
 class GatedGraphConv(nn.Module):
     """Gated graph convolution: the input (zero-padded to out_channels columns; wider inputs raise) runs through
     num_layers steps of m = x weight[i], agg_i = sum_{j -> i} m_j (edges as given, duplicates counted, no loops added,

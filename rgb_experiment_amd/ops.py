@@ -3290,6 +3290,164 @@ def rgcn_aggregate(h, graph, edge_type, num_relations, comp=None, aggr="mean", y
     return _RGCNMix.apply(h, comp, y0, view, aggr)
 
 
+class _GMMAggregate(torch.autograd.Function):
+    """GMMConv's aggregation as one autograd node: out = y0 + rs * sum_p sum_k gauss[p, k] h[col[p], k, :] in
+    rgbx_gmm_fwd_f32, gauss evaluated in registers from mu and sigma on the device; backward = the source pass over the
+    transposed CSR (g_h, only when h asks) and the edge pass over the forward CSR (g_e when e_slot asks, g_mu and g_sigma
+    when either parameter asks), g_y0 = gout. Saves h, e_slot, mu and sigma and nothing per edge beyond them."""
+
+    @staticmethod
+    def forward(ctx, h, e_slot, mu, sigma, y0, graph, aggr):
+        _lib.require_device(h, e_slot, mu, sigma, y0)
+        lib = _lib.load()
+        K, D = mu.shape
+        M = h.size(1) // K
+        csr, N, dev = graph.fwd, graph.fwd.N, h.device
+        vec = _head_vec(M)
+        h = _rows_on_grid(h, vec)
+        e = _rows_on_grid(e_slot, 1)
+        if csr.nnz == 0:  # no slot row is ever read: a pointer the entry points accept
+            e = torch.empty((1, D), dtype=torch.float32, device=dev)
+        # a contiguous parameter's own storage: a captured launch follows it
+        muv, sigv = mu.detach().contiguous(), sigma.detach().contiguous()
+        y = None if y0 is None else _rows_on_grid(y0, vec)
+        rs = graph.inv_deg if aggr == "mean" else None
+        out = torch.empty((N, M), dtype=torch.float32, device=dev)  # every row is written
+        ph, ldh = _lib.mat(h, "h")
+        pe, lde = _lib.mat(e, "e_slot")
+        py, ldy = (0, 0) if y is None else _lib.mat(y, "y0")
+        po, ldo = _lib.mat(out, "out")
+        split_ref, _, _scratch = _attn_split(csr, M, dev)
+        with _Timed("gmm_fwd"):
+            _lib.check(lib.rgbx_gmm_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pe, lde, _lib.ptr(muv),
+                                            _lib.ptr(sigv), _lib.ptr(rs), ph, ldh, py, ldy, po, ldo, N, K, M, D,
+                                            split_ref, _lib.stream_ptr()), "rgbx_gmm_fwd_f32")
+        ctx.graph, ctx.aggr, ctx.dims = graph, aggr, (K, M, D)
+        ctx.save_for_backward(h, e, muv, sigv)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, e, muv, sigv = ctx.saved_tensors
+        g, aggr, (K, M, D) = ctx.graph, ctx.aggr, ctx.dims
+        lib = _lib.load()
+        N, nnz, dev = g.fwd.N, g.fwd.nnz, h.device
+        need = ctx.needs_input_grad
+        gout = _rows_on_grid(gout.contiguous(), _head_vec(M))
+        pg, ldg = _lib.mat(gout, "gout")
+        pe, lde = _lib.mat(e, "e_slot")
+        g_h = g_e = g_mu = g_sigma = None
+        if need[0]:
+            g_h = torch.empty((N, K * M), dtype=torch.float32, device=dev)  # every row is written (no out-edge: zeros)
+            pgh, ldgh = _lib.mat(g_h, "g_h")
+            w_t = g.w_mean_t if aggr == "mean" else None
+            split_ref, _, _scratch = _attn_split(g.bwd, K * M, dev)
+            with _Timed("gmm_bwd_src"):
+                _lib.check(
+                    lib.rgbx_gmm_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(g.t2f), _lib.ptr(w_t),
+                                             pe, lde, _lib.ptr(muv), _lib.ptr(sigv), pg, ldg, pgh, ldgh, N, K, M, D,
+                                             split_ref, _lib.stream_ptr()), "rgbx_gmm_bwd_src_f32")
+        want_e, want_p = need[1], need[2] or need[3]
+        if want_e:
+            g_e = torch.empty((nnz, D), dtype=torch.float32, device=dev)  # every slot row is written
+        if want_p:
+            g_mu, g_sigma = (torch.zeros((K, D), dtype=torch.float32, device=dev) if nnz == 0 else
+                             torch.empty((K, D), dtype=torch.float32, device=dev) for _ in range(2))
+        if nnz and (want_e or want_p):
+            nbytes = ctypes.c_size_t(0)
+            _lib.check(lib.rgbx_gmm_bwd_edge_workspace_bytes(nnz, K, D, ctypes.byref(nbytes)),
+                       "rgbx_gmm_bwd_edge_workspace_bytes")
+            ws = torch.empty(max(nbytes.value // 4, 1), dtype=torch.float32, device=dev)
+            ph, ldh = _lib.mat(h, "h")
+            pge, ldge = _lib.mat(g_e, "g_e") if want_e else (0, 0)
+            rs = g.inv_deg if aggr == "mean" else None
+            split_ref, _, _scratch2 = _attn_split(g.fwd, 1, dev)  # the plan only: this pass leaves no chunk record
+            with _Timed("gmm_bwd_edge"):
+                _lib.check(
+                    lib.rgbx_gmm_bwd_edge_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pe, lde, _lib.ptr(muv),
+                                              _lib.ptr(sigv), _lib.ptr(rs), ph, ldh, pg, ldg, pge, ldge, _lib.ptr(g_mu),
+                                              _lib.ptr(g_sigma), _lib.ptr(ws), ws.numel() * 4, N, nnz, K, M, D,
+                                              split_ref, _lib.stream_ptr()), "rgbx_gmm_bwd_edge_f32")
+        return (g_h, g_e, g_mu if need[2] else None, g_sigma if need[3] else None, gout if need[4] else None, None,
+                None)
+
+
+def gmm_supported(K, M, D):
+    return bool(_lib.load().rgbx_gmm_supported(K, M, D))
+
+
+_GMM_AGGRS = {"mean": "mean", "add": "add", "sum": "add"}
+
+
+def gmm_aggregate(h, e_slot, mu, sigma, graph, aggr="mean", y0=None):
+    """GMMConv's aggregation (MoNet; separate_gaussians=False) over a LOOPS_KEEP graph, the edges as given: self-loops
+    stay, duplicates count twice. h [N, K * M] = x @ g, k-major columns (h.view(N, K, M)); e_slot [nnz, D] float32, the
+    pseudo-coordinates of every forward CSR slot (edge_rows_to_slots gives the order); mu, sigma [K, D] float32 on the
+    device:
+        gauss[p, k] = exp(sum_d -0.5 (e[p, d] - mu[k, d])^2 / (1e-15 + sigma[k, d]^2))
+        out_i       = y0_i + AGG_p sum_k gauss[p, k] h[col[p], k, :]
+    AGG "mean" divides by the number of in-edges as given, "add" / "sum" does not; a node without in-edges gets y0 (or
+    zeros). `y0` [N, M] (optional) is the layer's dense root + bias term, so that the output is written once. Column
+    blocks of a wider matrix are taken as they are where their rows sit on the vector grid. Gradients for h, e_slot, mu,
+    sigma and y0, each pass only where asked for; nothing per edge is saved and the kernels read mu and sigma from device
+    memory. No float atomics: two runs are bit-identical. Timing names: gmm_fwd, gmm_bwd_src, gmm_bwd_edge."""
+    from .graph import LOOPS_KEEP
+    if _is_dist(graph):
+        raise RuntimeError("GMMConv has no node-partitioned form: run it on one GPU")
+    if aggr not in _GMM_AGGRS:
+        raise ValueError(f"gmm_aggregate: aggr={aggr!r} (mean, add or sum)")
+    aggr = _GMM_AGGRS[aggr]
+    if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
+        raise RuntimeError("gmm_aggregate: only a graph in mode LOOPS_KEEP keeps one CSR slot per input edge (got "
+                           f"loops_mode={getattr(graph, 'loops_mode', None)!r})")
+    N, nnz = graph.fwd.N, graph.fwd.nnz
+    if not all(torch.is_tensor(t) and t.dim() == 2 and t.dtype == torch.float32 for t in (mu, sigma)) \
+            or mu.shape != sigma.shape or mu.size(0) == 0:
+        raise RuntimeError("gmm_aggregate: mu and sigma must be float32 [K, D] of one shape")
+    K, D = mu.shape
+    if h.dim() != 2 or h.size(0) != N or h.size(1) == 0 or h.size(1) % K or h.dtype != torch.float32:
+        raise RuntimeError(f"gmm_aggregate: h {h.dtype} {tuple(h.shape)} for a graph of {N} nodes and {K} kernels "
+                           f"(float32 [N, {K} * M])")
+    M = h.size(1) // K
+    if e_slot.dim() != 2 or tuple(e_slot.shape) != (nnz, D) or e_slot.dtype != torch.float32:
+        raise RuntimeError(f"gmm_aggregate: e_slot {e_slot.dtype} {tuple(e_slot.shape)} for a graph of {nnz} slots and "
+                           f"{D} coordinates (float32 [nnz, D] = [{nnz}, {D}])")
+    if y0 is not None and (tuple(y0.shape) != (N, M) or y0.dtype != torch.float32):
+        raise RuntimeError(f"gmm_aggregate: y0 {y0.dtype} {tuple(y0.shape)} (float32 [N, M] = [{N}, {M}])")
+    _lib.require_device(h, e_slot, mu, sigma, y0)
+    if not gmm_supported(K, M, D):
+        raise RuntimeError(f"gmm_aggregate: {K} kernels of {M} channels over {D} coordinates: the kernels take "
+                           "1 <= K <= 64, 1 <= D <= 8 and any M <= 64, even M <= 128 or M % 4 == 0 up to 256; pad the "
+                           "width (GMMConv does)")
+    return _GMMAggregate.apply(h, e_slot, mu, sigma, y0, graph, aggr)
+
+
+def degree_pseudo(graph):
+    """The MoNet paper's pseudo-coordinates of a LOOPS_KEEP graph without edge attributes, [nnz, 2] float32 in forward
+    CSR slot order: u[p] = (1 / sqrt(1 + indeg(source)), 1 / sqrt(1 + indeg(target))), the in-degrees as given
+    (rgbx_gmm_degree_pseudo_f32). Built once per graph and kept on it; it takes no gradient."""
+    from .graph import LOOPS_KEEP
+    if _is_dist(graph):
+        raise RuntimeError("degree pseudo-coordinates have no node-partitioned form: run it on one GPU")
+    if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
+        raise RuntimeError("degree_pseudo: only a graph in mode LOOPS_KEEP keeps one CSR slot per input edge (got "
+                           f"loops_mode={getattr(graph, 'loops_mode', None)!r})")
+    cached = graph.__dict__.get("_degree_pseudo")
+    if cached is None:
+        csr = graph.fwd
+        _lib.require_device(csr.rowptr)
+        dev = csr.rowptr.device
+        u = torch.empty((csr.nnz, 2), dtype=torch.float32, device=dev)  # every slot is written
+        if csr.nnz:
+            split_ref, _, _scratch = _attn_split(csr, 1, dev)  # the plan only: no chunk record
+            with _Timed("gmm_degree_pseudo"):
+                _lib.check(_lib.load().rgbx_gmm_degree_pseudo_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(u),
+                                                                  csr.N, split_ref, _lib.stream_ptr()),
+                           "rgbx_gmm_degree_pseudo_f32")
+        cached = graph._degree_pseudo = u
+    return cached
+
+
 class _SoftmaxAggregate(torch.autograd.Function):
     """One softmax aggregation as a single autograd node: a softmax per channel over the in-edges at temperature t, fused
     with the sum of the weighted message rows; backward = one pass over the transposed CSR (g_m, and the g_t records
