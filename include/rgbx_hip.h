@@ -32,6 +32,8 @@
  *   rgbx_resgated_*       ResGatedGraphConv (per-channel sigmoid gate) [PyG]; not in the reference's zoo.
  *   rgbx_gine_*           GINEConv (GIN with a feature row per edge: relu(x_j + e_ji) summed) [PyG]; the zoo's
  *                         models/gin.py is its sibling without edge features.
+ *   rgbx_pna_*            PNAConv (statistics of a per-edge message, scaled by functions of the in-degree) [PyG]; not in
+ *                         the reference's zoo.
  *   rgbx_rgcn_*           RGCNConv (a relation per edge: mean per (target, relation), basis decomposition) [PyG]; not
  *                         in the reference's zoo.
  *   rgbx_softmax_aggr_*   SoftmaxAggregation / GENConv(aggr="softmax") (per-channel softmax at a trained temperature)
@@ -296,6 +298,84 @@ typedef struct rgbx_multi_grad {
 } rgbx_multi_grad_t;
 int rgbx_multi_bwd_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const rgbx_multi_grad_t* terms,
                        float* gx, int64_t ldgx, int64_t N, int64_t d, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* ---- PNAConv: degree-scaled multi-aggregation of a per-edge message -----------------------------------------------------
+ * PNAConv.message with pre_layers = 1, split by linearity into a target part a, a source part b and an edge part c, and
+ * DegreeScalerAggregation behind it, in PyG's own column order (tower, then scaler, then aggregator) [PyG]; Corso et al.,
+ * "Principal Neighbourhood Aggregation for Graph Nets". Not in the reference's zoo. For an edge j -> i in forward CSR
+ * slot p (RGBX_LOOPS_KEEP: the edges as given, n = the slots of row i), b [N, d], c [nnz, d] ONE ROW PER SLOT in forward
+ * slot order (NULL: u_p = b[j,:]), a [N, d] (NULL: no shift), d = T * F:
+ *   u_p    = b[j,:] + c[p,:]                                              (one fp32 add)
+ *   stat_k = sum | mean | var | std | max | min of u_p over the slots of i  (rgbx_spmm_csr_multi_f32's definitions, word
+ *            for word: biased var from shifted sums, std = sqrt(var) where var > 1e-5 else 0, the lowest slot wins a tie,
+ *            a row without slots gives 0 and arg = -1; with c == NULL that entry point's bits)
+ *   shift  : mean, max, min += a[i,:];  sum += n * a[i,:];  var, std unchanged;  a row without slots stays 0
+ *   scale_s: RGBX_PNA_IDENTITY 1 | _AMPLIFICATION log(D+1)/avg_log | _ATTENUATION avg_log/log(D+1) | _LINEAR D/avg_lin |
+ *            _INVERSE_LINEAR avg_lin/D,   D = max(n, 1)
+ *   out[i, t*S*A*F + (s*A + k)*F + f] = scale_s(i) * stat_k[i, t*F + f]
+ * `avg_deg` = two floats [avg_lin, avg_log] in DEVICE memory, read by the kernel (a captured launch needs no read-back;
+ * averages of 0 give inf / NaN in the scaled blocks of rows WITH slots, as in PyG; rows without slots are exact zeros).
+ * `which`: the OR of the RGBX_MULTI_* bits of the A aggregators; `aggr_order`: their A bits in output order k (HOST
+ * memory, read before the call returns; NULL = ascending bits); `scalers`: the S scale kinds in output order
+ * (HOST memory, 1 <= S <= 8). F = the tower width: F % 4 == 0 and F divides d, so a lane's four columns stay in one tower.
+ * rgbx_pna_out_t: out [N, T*S*A*F]; the others are what a backward needs and the scaled blocks do not hold, each [N, d]
+ * of u BEFORE the shift, NULL = not wanted: mean (with any of sum, mean, var, std), var / std (with var or std),
+ * argmax / argmin (with that extremum; otherwise RGBX_E_ARG).
+ * d % 4 == 0, 4 <= d <= 256 (rgbx_pna_supported; wider: cut at tower boundaries); a, b, c and every output 16-byte
+ * aligned with leading dimensions % 4 == 0 and >= their width; out aliases no input. `split`: rows above
+ * split->threshold are cut into the plan's chunks, one wave each, their records merged in chunk order by the same exact
+ * re-basing (the split changes no extremum or arg); split->partial holds `partial_words` 4-byte words, at least
+ * rgbx_pna_partial_words(n_chunks, d, which [| RGBX_MULTI_MEAN when the raw mean is kept]) (else RGBX_E_WS), 16-byte
+ * aligned. No float atomics: bitwise reproducible. */
+enum {
+  RGBX_PNA_IDENTITY = 0, RGBX_PNA_AMPLIFICATION = 1, RGBX_PNA_ATTENUATION = 2, RGBX_PNA_LINEAR = 3,
+  RGBX_PNA_INVERSE_LINEAR = 4
+};
+typedef struct rgbx_pna_out {
+  float* out;      int64_t ld_out;
+  float* mean;     int64_t ld_mean;
+  float* var;      int64_t ld_var;
+  float* std;      int64_t ld_std;
+  int32_t* argmax; int64_t ld_argmax;
+  int32_t* argmin; int64_t ld_argmin;
+} rgbx_pna_out_t;
+int rgbx_pna_supported(int64_t d, int64_t F);
+int rgbx_pna_partial_words(int64_t n_chunks, int64_t d, int which, int64_t* words);
+int rgbx_pna_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t lda, const float* b, int64_t ldb,
+                     const float* c, int64_t ldc, const float* avg_deg, int which, const int32_t* aggr_order,
+                     const int32_t* scalers, int n_scalers, const rgbx_pna_out_t* out, int64_t N, int64_t d, int64_t F,
+                     const rgbx_row_split_t* split, int64_t partial_words, rgbx_stream_t stream);
+
+/* Backward of rgbx_pna_fwd_f32 in b and c. A, B, gmax, gmin are per-TARGET rows [N, d] the caller prepares (nothing in
+ * them is indexed by an edge), with G_k = sum_s scale_s * g_out[(s, k)]:
+ *   B = G_std / (n std) (0 where std == 0) + 2 G_var / n,     A = G_sum + G_mean / n - B * mean_u,    gmax / gmin = G_max / G_min
+ *   bracket(i, p) = A[i,:] + B[i,:] * u_p + gmax[i,:] [argmax[i,:] == p] + gmin[i,:] [argmin[i,:] == p]
+ * with u_p recomputed from the forward's own add. Any term may be NULL and is then neither read nor added (none at all,
+ * or an extremum cotangent without its arg: RGBX_E_ARG). The gradient in a needs no kernel (the second-moment terms sum
+ * to zero over a row): g_a[i] = n G_sum + (G_mean + G_max + G_min) [n > 0].
+ *   rgbx_pna_bwd_src_f32, over the TRANSPOSED CSR (rows = sources j, col_t = targets, t2f [nnz] = the forward slot of
+ *     every transposed slot; needed with an extremum term, or with B and c):
+ *       g_b[j,:] = sum over the slots q of transposed row j of bracket(col_t[q], t2f[q])
+ *     b[j] is read once per row, c[t2f[q]] gathered (c may be NULL; both are read only with B). Row-wise sums in slot order
+ *     with a fixed butterfly over the lane groups, hub rows through split->partial [n_chunks, d] added in chunk order.
+ *   rgbx_pna_bwd_edge_f32, over the forward CSR: g_c[p,:] = bracket(i, p), one row per slot in forward slot order, every
+ *     slot row written; b and c are required with B. `split` only balances the hub rows (chunk_begin / chunk_end /
+ *     chunk_row; split->partial is not touched).
+ * Widths and alignment as the forward (any d % 4 == 0 up to 256: the towers play no part). No float atomics. */
+typedef struct rgbx_pna_grad {
+  const float* A;        int64_t ld_A;
+  const float* B;        int64_t ld_B;
+  const float* gmax;     int64_t ld_gmax;
+  const int32_t* argmax; int64_t ld_argmax;
+  const float* gmin;     int64_t ld_gmin;
+  const int32_t* argmin; int64_t ld_argmin;
+} rgbx_pna_grad_t;
+int rgbx_pna_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const float* b, int64_t ldb,
+                         const float* c, int64_t ldc, const rgbx_pna_grad_t* terms, float* g_b, int64_t ldgb, int64_t N,
+                         int64_t d, const rgbx_row_split_t* split, rgbx_stream_t stream);
+int rgbx_pna_bwd_edge_f32(const int32_t* rowptr, const int32_t* col, const float* b, int64_t ldb, const float* c,
+                          int64_t ldc, const rgbx_pna_grad_t* terms, float* g_c, int64_t ldgc, int64_t N, int64_t d,
+                          const rgbx_row_split_t* split, rgbx_stream_t stream);
 
 /* rgbx_spmm_csr_f32 with an epilogue over the finished output rows, for layers that transform BEFORE they aggregate
  * (in > out — every default configuration of the reference, initial_params.py:25-29: F -> 64 -> C with C = 7, 6, 3, 40 ...),

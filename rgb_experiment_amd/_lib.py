@@ -37,6 +37,18 @@ class MultiGrad(ctypes.Structure):
                 for f, t in ((name, ctypes.c_void_p), ("ld_" + name, ctypes.c_int64))]
 
 
+class PnaOut(ctypes.Structure):
+    """rgbx_pna_out_t"""
+    _fields_ = [(f, t) for name in ("out", "mean", "var", "std", "argmax", "argmin")
+                for f, t in ((name, ctypes.c_void_p), ("ld_" + name, ctypes.c_int64))]
+
+
+class PnaGrad(ctypes.Structure):
+    """rgbx_pna_grad_t"""
+    _fields_ = [(f, t) for name in ("A", "B", "gmax", "argmax", "gmin", "argmin")
+                for f, t in ((name, ctypes.c_void_p), ("ld_" + name, ctypes.c_int64))]
+
+
 class CeEpilogue(ctypes.Structure):
     """rgbx_ce_epilogue_t"""
     _fields_ = [("y", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("grad_scale", ctypes.c_void_p),
@@ -147,6 +159,11 @@ SIGNATURES = {
     "rgbx_resgated_bwd_dst_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
     "rgbx_resgated_bwd_src_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P,
                                   _P],
+    "rgbx_pna_supported": [_I64, _I64],
+    "rgbx_pna_partial_words": [_I64, _I64, _I, ctypes.POINTER(ctypes.c_int64)],
+    "rgbx_pna_fwd_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I, _P, _P, _I, _P, _I64, _I64, _I64, _P, _I64, _P],
+    "rgbx_pna_bwd_src_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P],
+    "rgbx_pna_bwd_edge_f32": [_P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P],
     "rgbx_gine_supported": [_I],
     "rgbx_gine_fwd_f32": [_P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I, _P, _P],
     "rgbx_gine_bwd_edge_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],

@@ -776,6 +776,136 @@ class GINEConv(nn.Module):
         return self.nn(out if Cp == C else out[:, :C])
 
 
+_PNA_ACTS = {"relu": nn.ReLU, "elu": nn.ELU, "tanh": nn.Tanh, "sigmoid": nn.Sigmoid, "leaky_relu": nn.LeakyReLU,
+             "gelu": nn.GELU, "silu": nn.SiLU}
+
+
+class PNAConv(nn.Module):
+    """Principal Neighbourhood Aggregation [PyG PNAConv; Corso et al., "Principal Neighbourhood Aggregation for Graph
+    Nets"]: per tower t (T towers, F_in = in_channels, or in_channels / T with divide_input; F_out = out_channels / T)
+        m_ji = pre_nns[t](cat[x_i, x_j, edge_encoder(e_ji)])             (one Linear: pre_layers = 1)
+        agg_i = cat over the scalers s, then the aggregators k, of scale_s(deg_i) * AGG_k over the in-edges of m_ji
+        out_i = lin(cat over t of post_nns[t](cat[x_i, agg_i]))
+    over the edges AS GIVEN (self-loops stay, duplicates count twice, a node without in-edges aggregates zeros).
+    Aggregators: sum / add, mean, var, std, max, min; scalers: identity, amplification, attenuation, linear,
+    inverse_linear, with deg = max(in-degree, 1) and the averages of PyG's `deg` histogram (`deg=None`, an addition:
+    the averages of the first graph the layer sees). Parameter names and shapes are PyG's (pre_nns.{t}.0.*,
+    post_nns.{t}.*, edge_encoder.*, lin.*); the averages live in a non-persistent buffer.
+
+    pre_nns[t] is linear, so the message splits into a target part a_i = W_i x_i + bias, a source part b_j = W_j x_j and
+    an edge part c_ji = W_e edge_encoder(e_ji): one GEMM makes a | b for all towers, one GEMM at the RAW edge width makes c
+    (the encoder folded into W_e, bias included), and ops.pna_aggregate reads every b and c row once and writes the
+    T * S * A blocks in the order post_nns read them. F_in % 4 != 0 runs zero-padded (the padded channels aggregate
+    zeros and meet zero columns of post_nns' first weight).
+
+    Refused (NotImplementedError): pre_layers != 1 (a non-linear network per edge), train_norm=True, unknown aggregator
+    or scaler names. Out of scope: the node-partitioned (distributed) route, towers wider than 256 channels."""
+
+    def __init__(self, in_channels, out_channels, aggregators, scalers, deg=None, edge_dim=None, towers=1, pre_layers=1,
+                 post_layers=1, divide_input=False, act="relu", train_norm=False):
+        super().__init__()
+        if pre_layers != 1:
+            raise NotImplementedError("PNAConv: pre_layers != 1 puts a non-linear network on every edge; only the "
+                                      "single Linear (pre_layers=1) is implemented")
+        if train_norm:
+            raise NotImplementedError("PNAConv: train_norm=True (trained degree averages) is not implemented")
+        try:
+            self.aggregators = ops.multi_names(list(aggregators))
+            self.scalers = ops.pna_scaler_names(list(scalers))
+        except ValueError as err:
+            raise NotImplementedError(f"PNAConv: {err}") from None
+        if act not in _PNA_ACTS:
+            raise NotImplementedError(f"PNAConv: act={act!r} (one of {sorted(_PNA_ACTS)})")
+        if towers < 1 or post_layers < 1 or out_channels % towers or (divide_input and in_channels % towers):
+            raise ValueError("PNAConv: towers must divide out_channels (and in_channels with divide_input); post_layers "
+                             "must be at least 1")
+        self.in_channels, self.out_channels, self.edge_dim = in_channels, out_channels, edge_dim
+        self.towers, self.divide_input = towers, divide_input
+        self.F_in = in_channels // towers if divide_input else in_channels
+        self.F_out = out_channels // towers
+        if edge_dim is not None:
+            self.edge_encoder = Linear(edge_dim, self.F_in)
+        self.pre_nns, self.post_nns = nn.ModuleList(), nn.ModuleList()
+        wide = (len(self.aggregators) * len(self.scalers) + 1) * self.F_in
+        for _ in range(towers):
+            self.pre_nns.append(nn.Sequential(Linear((3 if edge_dim is not None else 2) * self.F_in, self.F_in)))
+            post = [Linear(wide, self.F_out)]
+            for _ in range(post_layers - 1):
+                post += [_PNA_ACTS[act](), Linear(self.F_out, self.F_out)]
+            self.post_nns.append(nn.Sequential(*post))
+        self.lin = Linear(out_channels, out_channels)
+        avg = torch.zeros(2)
+        if deg is not None:  # PyG's histogram: deg[k] = the number of nodes with in-degree k
+            hist = torch.as_tensor(deg).detach().to("cpu", torch.float64).reshape(-1)
+            bins = torch.arange(hist.numel(), dtype=torch.float64)
+            avg = torch.stack([(bins * hist).sum(), ((bins + 1).log() * hist).sum()]) / hist.sum()
+        self.register_buffer("avg_deg", avg.to(torch.float32), persistent=False)
+        self._avg_known = deg is not None
+
+    def _node_operands(self):
+        """(weight [2 T Fp, in_channels], bias [2 T Fp]) of the GEMM that makes a | b for all towers: the x_i and x_j column
+        blocks of every pre_nns[t] weight, rows padded to Fp, block-diagonal over the towers with divide_input."""
+        Fi, pad = self.F_in, (self.F_in + 3) // 4 * 4 - self.F_in
+        rows = lambda w: torch.nn.functional.pad(w, (0, 0, 0, pad)) if pad else w
+        wi = [rows(p[0].weight[:, :Fi]) for p in self.pre_nns]
+        wj = [rows(p[0].weight[:, Fi:2 * Fi]) for p in self.pre_nns]
+        stack = (lambda ws: torch.block_diag(*ws)) if self.divide_input else (lambda ws: torch.cat(ws, 0))
+        bias = torch.cat([torch.nn.functional.pad(p[0].bias, (0, pad)) for p in self.pre_nns])
+        return torch.cat([stack(wi), stack(wj)], 0), torch.cat([bias, torch.zeros_like(bias)])
+
+    def _edge_operands(self):
+        """(weight [T Fp, edge_dim], bias [T Fp]): the edge encoder folded into the edge block of every pre_nns[t]."""
+        Fi, pad = self.F_in, (self.F_in + 3) // 4 * 4 - self.F_in
+        enc = self.edge_encoder
+        ws, bs = [], []
+        for p in self.pre_nns:
+            we = p[0].weight[:, 2 * Fi:]
+            ws.append(torch.nn.functional.pad(we @ enc.weight, (0, 0, 0, pad)))
+            bs.append(torch.nn.functional.pad(we @ enc.bias, (0, pad)))
+        return torch.cat(ws, 0), torch.cat(bs)
+
+    def forward(self, x, edge_index, edge_attr=None):
+        E = edge_index.size(1)
+        if self.edge_dim is not None:
+            if not torch.is_tensor(edge_attr) or edge_attr.dim() != 2 or tuple(edge_attr.shape) != (E, self.edge_dim) \
+                    or not edge_attr.is_floating_point():
+                got = tuple(edge_attr.shape) if torch.is_tensor(edge_attr) else type(edge_attr).__name__
+                raise ValueError(f"PNAConv: edge_attr must be float [E, edge_dim] = [{E}, {self.edge_dim}], got {got}")
+        elif edge_attr is not None:
+            raise ValueError("PNAConv: edge_attr given to a layer built with edge_dim=None")
+        if x.dim() != 2 or x.size(1) != self.in_channels:
+            raise ValueError(f"PNAConv: x {tuple(x.shape)} for in_channels={self.in_channels}")
+        _lib.require_device(x, edge_attr)
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        if not self._avg_known:  # the averages of the first graph seen, copied on the device
+            with torch.no_grad():
+                self.avg_deg.copy_(ops.degree_averages(graph))
+            self._avg_known = True
+        T, Fi = self.towers, self.F_in
+        Fp = (Fi + 3) // 4 * 4
+        d = T * Fp
+        ab = ops.linear(x, *self._node_operands())
+        c = None
+        if self.edge_dim is not None and E > 0:
+            ea = ops.edge_rows_to_slots(edge_attr.to(torch.float32), graph)
+            c = ops.linear(ea, *self._edge_operands())
+        out = ops.pna_aggregate(ab[:, :d], ab[:, d:], c, graph, self.aggregators, self.scalers, self.avg_deg, Fp)
+        blocks = len(self.aggregators) * len(self.scalers)
+        outs = []
+        for t, post in enumerate(self.post_nns):  # post_nns[t] on cat[x_t, out_t], read in place
+            first = post[0]
+            wx, wo = first.weight[:, :Fi], first.weight[:, Fi:]
+            if Fp != Fi:
+                wo = torch.nn.functional.pad(wo.reshape(-1, blocks, Fi), (0, Fp - Fi)).reshape(-1, blocks * Fp)
+            x_t = x[:, t * Fi:(t + 1) * Fi] if self.divide_input else x
+            h = ops.linear(out[:, t * blocks * Fp:(t + 1) * blocks * Fp], wo.contiguous()) \
+                + ops.linear(x_t, wx.contiguous(), first.bias)
+            for layer in list(post)[1:]:
+                h = layer(h)
+            outs.append(h)
+        return self.lin(outs[0] if T == 1 else torch.cat(outs, dim=1))
+
+
 class RGCNConv(nn.Module):
     """Relational graph convolution [PyG RGCNConv; Schlichtkrull et al., "Modeling Relational Data with Graph
     Convolutional Networks"]: every edge carries a relation, edge_type[e] in [0, num_relations), and

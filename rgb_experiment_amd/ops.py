@@ -3033,6 +3033,265 @@ def gine_aggregate(x, e_slot, graph, eps=None):
     return _GINEAggregate.apply(x, e_slot, eps, graph)
 
 
+# ---- PNAConv: the statistics of a per-edge message, scaled by functions of the in-degree -------------------------------
+
+PNA_SCALERS = {"identity": 0, "amplification": 1, "attenuation": 2, "linear": 3, "inverse_linear": 4}  # RGBX_PNA_*
+PNA_BLOCK = 256  # wider inputs run as column blocks of at most this many channels, cut at tower boundaries
+
+
+def pna_scaler_names(scalers):
+    """A name or a non-empty list / tuple of distinct scaler names as a tuple; anything else: ValueError."""
+    seq = (scalers,) if isinstance(scalers, str) else scalers
+    if (not isinstance(seq, (list, tuple)) or not seq or any(s not in PNA_SCALERS for s in seq)
+            or len(set(seq)) != len(seq)):
+        raise ValueError(f"scalers must name distinct scalers out of {sorted(PNA_SCALERS)}, got {scalers!r}")
+    return tuple(seq)
+
+
+def degree_averages(graph):
+    """float32 [2] on the graph's device: [mean of deg, mean of log(deg + 1)] over the in-degrees of all nodes — PyG's
+    avg_deg['lin'] and avg_deg['log'] of PNAConv's degree histogram (sum_k k hist[k] / sum_k hist[k], and the same with
+    log(k + 1)). Computed where the CSR lives, once per graph, with no read-back. A graph without nodes gives zeros."""
+    cached = graph.__dict__.get("_avg_deg")
+    if cached is None:
+        rowptr = graph.fwd.rowptr
+        deg = (rowptr[1:] - rowptr[:-1]).to(torch.float64)
+        if deg.numel() == 0:
+            cached = torch.zeros(2, dtype=torch.float32, device=rowptr.device)
+        else:
+            cached = torch.stack([deg.mean(), torch.log(deg + 1).mean()]).to(torch.float32)
+        graph._avg_deg = cached
+    return cached
+
+
+def pna_scales(graph, scalers, avg_deg):
+    """float32 [N, S]: scale_s of every node (D = max(in-degree, 1)), torch's restatement of the kernel's epilogue for
+    the dense per-node work of the backward."""
+    rowptr = graph.fwd.rowptr
+    D = (rowptr[1:] - rowptr[:-1]).to(torch.float32).clamp(min=1)
+    logD = torch.log(D + 1)
+    lin, log = avg_deg[0], avg_deg[1]
+    cols = {"identity": lambda: torch.ones_like(D), "amplification": lambda: logD / log,
+            "attenuation": lambda: log / logD, "linear": lambda: D / lin, "inverse_linear": lambda: lin / D}
+    return torch.stack([cols[s]() for s in scalers], dim=1)
+
+
+def _pna_blocks(d, F):
+    """[(t0, t1)]: the towers of every launch, as many as fit into PNA_BLOCK channels."""
+    per = max(PNA_BLOCK // F, 1)
+    return [(t0, min(t0 + per, d // F)) for t0 in range(0, d // F, per)]
+
+
+def pna_fwd_raw(csr, a, b, c, avg_deg, aggregators, scalers, F, keep=()):
+    """(out [N, T*S*A*F], kept): rgbx_pna_fwd_f32 over `csr` on operands that are already on the vector grid (a, c may be
+    None); `keep`: out of 'mean', 'var', 'std', 'argmax', 'argmin', the raw statistics of u stored beside (kept[name],
+    [N, d]). No autograd, no checks beyond the entry point's."""
+    lib = _lib.load()
+    names, scalers = multi_names(aggregators), pna_scaler_names(scalers)
+    N, dev = csr.N, b.device
+    d, S, A = b.size(1), len(scalers), len(names)
+    if csr.nnz == 0:
+        c = None  # no slot row is ever read
+    avg = avg_deg.detach().reshape(-1).contiguous()
+    out = torch.empty((N, (d // F) * S * A * F), dtype=torch.float32, device=dev)  # every row is written
+    kept = {k: torch.empty((N, d), dtype=torch.int32 if k.startswith("arg") else torch.float32, device=dev) for k in keep}
+    bits = sum(MULTI_BITS[n] for n in names)
+    order = (ctypes.c_int32 * A)(*[MULTI_BITS[n] for n in names])
+    kinds = (ctypes.c_int32 * S)(*[PNA_SCALERS[s] for s in scalers])
+    for t0, t1 in _pna_blocks(d, F):
+        c0, c1 = t0 * F, t1 * F
+        w = c1 - c0
+        o = _lib.PnaOut()
+        o.out, o.ld_out = _block_ptr(out, t0 * S * A * F, t1 * S * A * F)
+        for k, t in kept.items():
+            p, ld = _block_ptr(t, c0, c1)
+            setattr(o, k, p)
+            setattr(o, "ld_" + k, ld)
+        pa, lda = (0, 0) if a is None else _block_ptr(a, c0, c1)
+        pb, ldb = _block_ptr(b, c0, c1)
+        pc, ldc = (0, 0) if c is None else _block_ptr(c, c0, c1)
+        split, words = None, 0
+        if csr.split is not None:
+            n_words = ctypes.c_int64(0)
+            _lib.check(lib.rgbx_pna_partial_words(csr.split["n_chunks"], w, bits | (MULTI_BITS["mean"] if "mean" in kept else 0),
+                                                  ctypes.byref(n_words)), "rgbx_pna_partial_words")
+            words = n_words.value
+            split, _scratch = csr.split_arg(words // csr.split["n_chunks"], dev)
+        variant = (f"rows+d{w}+{'+'.join(names)}x{S}" + ("+c" if c is not None else "") + ("+kept" if kept else "")
+                   if _EVENT_SINK is not None else None)
+        with _Timed("pna_fwd", variant):
+            _lib.check(lib.rgbx_pna_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pa, lda, pb, ldb, pc, ldc,
+                                            _lib.ptr(avg), bits, order, kinds, S, ctypes.byref(o), N, w, F,
+                                            None if split is None else ctypes.byref(split), words,
+                                            _lib.stream_ptr()), "rgbx_pna_fwd_f32")
+    return out, kept
+
+
+def pna_bwd_raw(graph, terms, b, c, F, want_b=True, want_c=False):
+    """(g_b [N, d] or None, g_c [nnz, d] or None): rgbx_pna_bwd_src_f32 over the transposed CSR and rgbx_pna_bwd_edge_f32
+    over the forward one, each only where wanted. `terms`: the per-target rows A, B, gmax, argmax, gmin, argmin that are
+    present ([N, d], on the vector grid); b and c are read with B alone (c may be None for the source pass). No autograd."""
+    lib = _lib.load()
+    first = next(iter(terms.values()))
+    N, d, dev = graph.fwd.N, first.size(1), first.device
+    nnz = graph.fwd.nnz
+    with_b = "B" in terms
+    g_b = torch.empty((N, d), dtype=torch.float32, device=dev) if want_b else None  # every row is written
+    g_c = torch.empty((nnz, d), dtype=torch.float32, device=dev) if want_c else None  # every slot row is written
+    want_c = want_c and nnz > 0  # (no slot: the [0, d] gradient is complete as it is)
+    if nnz == 0:
+        c = None
+    for t0, t1 in _pna_blocks(d, F) if (want_b or want_c) else ():
+        c0, c1 = t0 * F, t1 * F
+        w = c1 - c0
+        t = _lib.PnaGrad()
+        for k, v in terms.items():
+            p, ld = _block_ptr(v, c0, c1)
+            setattr(t, k, p)
+            setattr(t, "ld_" + k, ld)
+        pb, ldb = _block_ptr(b, c0, c1) if with_b else (0, 0)
+        pc, ldc = _block_ptr(c, c0, c1) if (with_b and c is not None) else (0, 0)
+        variant = f"rows+d{w}+{'+'.join(terms)}" + ("+c" if pc else "") if _EVENT_SINK is not None else None
+        if want_c:
+            pg, ldg = _block_ptr(g_c, c0, c1)
+            split, _scratch = graph.fwd.split_arg(1, dev)  # the plan only: this pass leaves no chunk record
+            with _Timed("pna_bwd_edge", variant):
+                _lib.check(lib.rgbx_pna_bwd_edge_f32(_lib.ptr(graph.fwd.rowptr), _lib.ptr(graph.fwd.col), pb, ldb, pc, ldc,
+                                                     ctypes.byref(t), pg, ldg, N, w,
+                                                     None if split is None else ctypes.byref(split), _lib.stream_ptr()),
+                           "rgbx_pna_bwd_edge_f32")
+        if want_b:
+            pg, ldg = _block_ptr(g_b, c0, c1)
+            bwd = graph.bwd
+            split, _scratch2 = bwd.split_arg(w, dev)
+            with _Timed("pna_bwd_src", variant):
+                _lib.check(lib.rgbx_pna_bwd_src_f32(_lib.ptr(bwd.rowptr), _lib.ptr(bwd.col), _lib.ptr(graph.t2f), pb, ldb, pc,
+                                                    ldc, ctypes.byref(t), pg, ldg, bwd.N, w,
+                                                    None if split is None else ctypes.byref(split), _lib.stream_ptr()),
+                           "rgbx_pna_bwd_src_f32")
+    return g_b, g_c
+
+
+class _PNAAggregate(torch.autograd.Function):
+    """One PNA aggregation as a single autograd node: forward = rgbx_pna_fwd_f32 (statistics of u_p = b_j + c_p, the
+    shift by a, S * A scaled blocks stored once each); backward = the cotangent folded over the scalers and into the
+    per-target rows (A, B, G_max, G_min) with dense per-node work on torch, then the source pass (g_b) and the edge pass
+    (g_c), each run only where a gradient is asked for; g_a needs no kernel. Saved: b, c, the raw mean and std of u and
+    the winning slots (only when a gradient will be asked for)."""
+
+    @staticmethod
+    def forward(ctx, a, b, c_slot, avg_deg, graph, names, scalers, F, want):
+        a, b, c = (None if t is None else _rows_on_grid(t) for t in (a, b, c_slot))
+        second = want and ("std" in names or "var" in names)
+        keep = []
+        if second:
+            keep.append("mean")
+        if want:
+            keep += [k for k, n in (("std", "std"), ("argmax", "max"), ("argmin", "min")) if n in names]
+        out, kept = pna_fwd_raw(graph.fwd, a, b, c, avg_deg, names, scalers, F, keep)
+        ctx.graph, ctx.names, ctx.scalers, ctx.F = graph, names, scalers, F
+        ctx.has = (a is not None, c_slot is not None)
+        if want:
+            # built here, outside the backward (their construction reads sizes back to the host)
+            graph.bwd, graph.t2f
+            ctx.save_for_backward(b if second else None, c if second else None, avg_deg.detach().reshape(-1),
+                                  kept.get("mean"), kept.get("std"), kept.get("argmax"), kept.get("argmin"))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        b, c, avg, mean_u, std, amax, amin = ctx.saved_tensors
+        g, names, scalers, F = ctx.graph, ctx.names, ctx.scalers, ctx.F
+        need = ctx.needs_input_grad
+        N, dev = g.fwd.N, gout.device
+        S, A = len(scalers), len(names)
+        T = gout.size(1) // (S * A * F)
+        d = T * F
+        rowptr = g.fwd.rowptr
+        deg = (rowptr[1:] - rowptr[:-1]).to(torch.float32)[:, None]
+        inv_n = 1.0 / deg.clamp(min=1)
+        # G_k = sum_s scale_s g_out[(s, k)], [N, T, A, F]
+        G = (gout.reshape(N, T, S, A, F) * pna_scales(g, scalers, avg).view(N, 1, S, 1, 1)).sum(2)
+        Gk = lambda n: G[:, :, names.index(n), :].reshape(N, d) if n in names else None
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        B = A_row = None
+        if "std" in names:  # d std / d u_p = (u_p - mean) / (n std); 0 where the clamp or the mask is active
+            B = torch.where(std > 0, Gk("std") * inv_n / std, zero)
+        if "var" in names:  # d var / d u_p = 2 (u_p - mean) / n
+            t = Gk("var") * (2.0 * inv_n)
+            B = t if B is None else B + t
+        b_k = b
+        if B is not None:
+            # B (u_p - mean_u) as B u_p - B mean_u cancels on messages with an offset: both halves are taken relative to
+            # the column mean s of mean_u (the same number), so the kernels' b is b - s
+            s = mean_u.mean(0, keepdim=True)
+            A_row = -B * (mean_u - s)
+            b_k = b - s
+        if "sum" in names:
+            A_row = Gk("sum") if A_row is None else A_row + Gk("sum")
+        if "mean" in names:
+            t = Gk("mean") * inv_n
+            A_row = t if A_row is None else A_row + t
+        terms = {"A": A_row, "B": B, "gmax": Gk("max"), "argmax": amax, "gmin": Gk("min"), "argmin": amin}
+        terms = {k: _rows_on_grid(v) for k, v in terms.items() if v is not None}
+        has_a, has_c = ctx.has
+        g_a = None
+        if has_a and need[0]:  # the second-moment terms sum to zero over a row
+            g_a = torch.zeros((N, d), dtype=torch.float32, device=dev)
+            if "sum" in names:
+                g_a = g_a + deg * Gk("sum")
+            for n in ("mean", "max", "min"):
+                if n in names:
+                    g_a = g_a + Gk(n)
+            g_a = torch.where(deg > 0, g_a, zero)
+        g_b, g_c = pna_bwd_raw(g, terms, b_k, c, F, want_b=need[1], want_c=has_c and need[2])
+        return g_a, g_b, g_c, None, None, None, None, None, None
+
+
+def pna_supported(d, F):
+    return bool(_lib.load().rgbx_pna_supported(d, F))
+
+
+def pna_aggregate(a, b, c_slot, graph, aggregators, scalers, avg_deg, F):
+    """PNAConv's message, aggregation and degree scaling in one pass: with u_p = b_j + c_p for the edge j -> i in forward
+    CSR slot p, out[i, t*S*A*F + (s*A + k)*F + f] = scale_s(i) * stat_k(i)[t*F + f] — PyG's DegreeScalerAggregation
+    layout (tower, then scaler, then aggregator), float32 [N, T*S*A*F].
+      a [N, d] or None: the target part of the message; mean, max, min are shifted by a_i and the sum by n_i a_i
+      b [N, d]: the source part;  c_slot [nnz, d] or None: the edge part, one row per forward CSR slot (edge_rows_to_slots)
+      aggregators: distinct names out of sum / add, mean, var, std, max, min, in output order
+      scalers: distinct names out of identity, amplification, attenuation, linear, inverse_linear, in output order
+      avg_deg: float32 [2] on the device, [avg_lin, avg_log] (degree_averages(graph) for the graph's own)
+      F: the tower width; F % 4 == 0 and F divides d = T * F
+    The graph is in mode LOOPS_KEEP (edges as given; a node without in-edges gets zeros in every block). Column blocks of
+    wider matrices are read in place; d above 256 runs as column blocks cut at tower boundaries (F <= 256). Gradients
+    flow to a, b and c_slot, each pass run only where one is asked for; avg_deg takes none."""
+    from .graph import LOOPS_KEEP
+    if _is_dist(graph):
+        raise RuntimeError("PNAConv has no node-partitioned form: run it on one GPU")
+    _lib.require_device(a, b, c_slot, avg_deg)
+    if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
+        raise RuntimeError(f"pna_aggregate: the graph must be in mode LOOPS_KEEP (got loops_mode="
+                           f"{getattr(graph, 'loops_mode', None)!r})")
+    names, scalers = multi_names(aggregators), pna_scaler_names(scalers)
+    N, nnz = graph.fwd.N, graph.fwd.nnz
+    if b.dim() != 2 or b.size(0) != N or b.dtype != torch.float32:
+        raise RuntimeError(f"pna_aggregate: b {b.dtype} {tuple(b.shape)} for a graph of {N} nodes (float32 [N, d])")
+    d = b.size(1)
+    if a is not None and (tuple(a.shape) != (N, d) or a.dtype != torch.float32):
+        raise RuntimeError(f"pna_aggregate: a {a.dtype} {tuple(a.shape)} for a graph of {N} nodes and b [N, {d}]")
+    if c_slot is not None and (tuple(c_slot.shape) != (nnz, d) or c_slot.dtype != torch.float32):
+        raise RuntimeError(f"pna_aggregate: c_slot {c_slot.dtype} {tuple(c_slot.shape)} for a graph of {nnz} slots and "
+                           f"b [N, {d}] (float32 [nnz, d])")
+    if avg_deg.numel() != 2 or avg_deg.dtype != torch.float32:
+        raise RuntimeError(f"pna_aggregate: avg_deg {avg_deg.dtype} {tuple(avg_deg.shape)} (two float32: [lin, log])")
+    F = int(F)
+    if F < 4 or F % 4 or d % F or F > PNA_BLOCK:
+        raise RuntimeError(f"pna_aggregate: tower width F = {F} for d = {d}: the kernels take F % 4 == 0 up to "
+                           f"{PNA_BLOCK} with F dividing d; pad the tower width (PNAConv does)")
+    want = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (a, b, c_slot))
+    return _PNAAggregate.apply(a, b, c_slot, avg_deg, graph, names, scalers, F, want)
+
+
 _TYPED_VIEWS_MAX = 4  # cached typed views per graph (each holds a handful of [E] vectors)
 
 
