@@ -19,6 +19,9 @@
  *   rgbx_inv_degree_f32   the 1/max(count,1) of aggr='mean' (models/graphsage.py:39,58) [PyG].
  *   rgbx_spmm_csr_f32     MessagePassing.propagate with aggr='add' / 'mean' and message
  *                         norm * x_j (models/dagnn.py:34-36,46,57-59; models/graphsage.py:58).
+ *   rgbx_spmm_csr_bf16 / rgbx_rows_f32_to_bf16
+ *                         the same propagate with the gathered matrix stored as bfloat16 (fp32 sums), and the
+ *                         rounding in front of it (tensor.to(torch.bfloat16)).
  *   rgbx_spmm_csr_extremum_f32 / rgbx_extremum_bwd_f32
  *                         the same propagate with aggr='max' / 'min' (the keyword models/graphsage.py:38-40 leaves to
  *                         the caller) and its backward.
@@ -59,7 +62,8 @@
  *     stream); nothing inside synchronises the device.
  *   - Return value: 0 = OK; < 0 = argument/shape/alignment error (RGBX_E_*); > 0 = hipError_t.
  *     `rgbx_last_error_string()` describes the calling thread's last failure.
- *   - Feature matrices are fp32 row-major with an explicit leading dimension in ELEMENTS.
+ *   - Feature matrices are fp32 row-major with an explicit leading dimension in ELEMENTS (the one exception: the
+ *     bfloat16 table of rgbx_spmm_csr_bf16, passed as uint16_t).
  *   - Indices inside the library are int32 (requires N < 2^31 and E' < 2^31); `edge_index`
  *     arrives as the reference's int64 [2, E].
  */
@@ -196,6 +200,37 @@ int rgbx_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* w,
                       const float* x, int64_t ldx, const float* y, int64_t ldy, const float* bias,
                       float* out, int64_t ldo, int64_t N, int64_t d, float a, float b,
                       const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* ---- the same gather with the gathered table stored as bfloat16 ------------------------------------------------------
+ * bfloat16 values are passed as uint16_t: the upper 16 bits of the fp32 pattern (widening is `bits << 16`, exact). */
+
+/* 1 if rgbx_spmm_csr_bf16 takes width d: d % 8 == 0 and 8 <= d <= 256 (a lane holds 8 columns = one 16-byte load and a
+ * lane group a whole row); other widths: zero-pad the rows. */
+int rgbx_spmm_csr_bf16_supported(int64_t d);
+
+/* rgbx_spmm_csr_f32 with x stored as bfloat16 (replaces the same propagate, models/dagnn.py:57-59 / graphsage.py:58, at
+ * half the bytes of the gathered table): the same expression, x widened exactly, every sum and the whole epilogue in
+ * fp32; w, rs, y, bias are fp32 and optional as there. Outputs: `out` (fp32) and / or `out_bf16` (the same fp32 result
+ * rounded to nearest-even; NaN -> the quiet NaN 0xffff, overflow -> inf) — at least one (RGBX_E_ARG). `out` may alias
+ * `y`; out_bf16 must not alias x. Leading dimensions may exceed d (column slices).
+ * Constraints, checked on the host before any launch: rgbx_spmm_csr_bf16_supported(d) (RGBX_E_SHAPE); x and out_bf16
+ * 16-byte aligned with ldx % 8 == 0, ldob % 8 == 0; y / out / bias 16-byte aligned with ldy % 4 == 0, ldo % 4 == 0
+ * (RGBX_E_ALIGN); null rowptr / col / x, a leading dimension < d, an incomplete plan (RGBX_E_ARG).
+ * `split`: as rgbx_spmm_csr_f32 — rows above the threshold are cut into the plan's chunks, the partials are fp32 in
+ * split->partial ([n_chunks, d], 16-byte aligned) and added in chunk order. No float atomics, no scratch memory: two
+ * launches give the same bits. The backward pass is this entry on the transposed CSR. */
+int rgbx_spmm_csr_bf16(const int32_t* rowptr, const int32_t* col, const float* w, const float* rs, const uint16_t* x,
+                       int64_t ldx, const float* y, int64_t ldy, const float* bias, float* out, int64_t ldo,
+                       uint16_t* out_bf16, int64_t ldob, int64_t N, int64_t d, float a, float b,
+                       const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* dst[r, 0:d] = src[r, 0:d] rounded to bfloat16, nearest-even, for r in [0, n): the conversion in front of
+ * rgbx_spmm_csr_bf16 (replaces tensor.to(torch.bfloat16), whose CPU result it matches bit for bit: NaN -> 0xffff, the
+ * largest finite fp32 -> inf, subnormals rounded like any value). Strided source and destination (lds, ldd >= d), so a
+ * column slice needs no contiguous copy; any d (rows on the 16-byte grid with d % 8 == 0, lds % 4 == 0, ldd % 8 == 0 take
+ * the vector path). n == 0 or d == 0: nothing to do, returns 0. */
+int rgbx_rows_f32_to_bf16(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int64_t n, int64_t d,
+                          rgbx_stream_t stream);
 
 /* g[p] = sum_c a[i,c] * b[col[p],c] for every slot p of row i: dL/dw of the aggregation out = sum_p w[p] x[col[p],:]
  * (message norm * x_j, models/dagnn.py:57-59, norm from models/dagnn.py:12-31) with a = dL/dout and b = x. One wave per

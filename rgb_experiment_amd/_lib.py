@@ -89,6 +89,9 @@ SIGNATURES = {
     "rgbx_edge_dot_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P],
     "rgbx_gcn_norm_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P],
     "rgbx_spmm_csr_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P],
+    "rgbx_spmm_csr_bf16_supported": [_I64],
+    "rgbx_spmm_csr_bf16": [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _F, _F, _P, _P],
+    "rgbx_rows_f32_to_bf16": [_P, _I64, _P, _I64, _I64, _I64, _P],
     "rgbx_spmm_csr_extremum_supported": [_I64],
     "rgbx_spmm_csr_extremum_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
     "rgbx_extremum_bwd_f32": [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _P],
@@ -290,6 +293,16 @@ def mat(t, name="tensor"):
     """Row-major fp32 matrix -> (pointer, leading dimension in elements)."""
     if t.dtype != torch.float32 or t.dim() != 2:
         raise RuntimeError(f"{name}: expected a 2-D float32 tensor, got {t.dtype} {tuple(t.shape)}")
+    if t.size(1) > 1 and t.stride(1) != 1:
+        raise RuntimeError(f"{name}: rows must be contiguous (stride {t.stride()})")
+    ld = t.stride(0) if t.size(0) > 1 else max(t.size(1), 1)
+    return t.data_ptr(), ld
+
+
+def mat_bf16(t, name="tensor"):
+    """Row-major bfloat16 matrix -> (pointer, leading dimension in elements); `mat` stays fp32-only."""
+    if t.dtype != torch.bfloat16 or t.dim() != 2:
+        raise RuntimeError(f"{name}: expected a 2-D bfloat16 tensor, got {t.dtype} {tuple(t.shape)}")
     if t.size(1) > 1 and t.stride(1) != 1:
         raise RuntimeError(f"{name}: rows must be contiguous (stride {t.stride()})")
     ld = t.stride(0) if t.size(0) > 1 else max(t.size(1), 1)

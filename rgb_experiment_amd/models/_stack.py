@@ -195,6 +195,8 @@ def _layer_maps(conv):
     name = type(conv).__name__
     if getattr(conv, "aggr", "mean") != "mean":
         return None
+    if getattr(conv, "gather_dtype", None) is not None:
+        return None  # the collapsed forward gathers fp32 rows: it would bypass the layer's bfloat16 gather
     if name == "GCNConv":
         return conv.lin.weight, None, conv.bias, "gcn", LOOPS_ADD_REMAINING
     if name == "MySAGEConv" and conv.add_self_loops:

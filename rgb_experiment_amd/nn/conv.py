@@ -70,6 +70,29 @@ def _set_aggr(conv, aggr, lists=False):
     return len(conv.aggr) if isinstance(conv.aggr, tuple) else 1
 
 
+# accepted gather_dtype keyword -> storage dtype of the gathered matrix
+GATHER_DTYPES = {torch.bfloat16: torch.bfloat16, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}
+
+
+def _set_gather_dtype(conv, gather_dtype):
+    """The `gather_dtype` keyword of GCNConv / SAGEConv / MySAGEConv. None leaves the layer exactly as it is. torch.bfloat16
+    ('bf16', 'bfloat16'): the neighbour rows are gathered from a bfloat16 copy (rounded once, to nearest-even) with fp32
+    sums — ops.propagate_rows_bf16 / propagate_bf16, at the narrower of the layer's two widths, between the dense products.
+    Every form that would gather fp32 rows instead (loss-in-kernel, column sums, the BatchNorm hand-over, folded,
+    cached-aggregate, collapsed and fused aggregate + transform) is switched off for this instance, as _set_aggr does."""
+    if gather_dtype is None:
+        return
+    known = isinstance(gather_dtype, (str, torch.dtype)) and gather_dtype in GATHER_DTYPES
+    if not known:
+        raise ValueError(f"{type(conv).__name__}: gather_dtype must be None, torch.bfloat16, 'bf16' or 'bfloat16', got "
+                         f"{gather_dtype!r}")
+    if getattr(conv, "aggr", "mean") != "mean":
+        raise ValueError(f"{type(conv).__name__}: gather_dtype is implemented for aggr='mean' only, got aggr="
+                         f"{conv.aggr!r}")
+    conv.gather_dtype = GATHER_DTYPES[gather_dtype]
+    conv.accepts_ce = conv.accepts_ce_pair = conv.emits_colsums = conv.owns_next_bn_backward = False
+
+
 def _aggregate(x, graph, aggr):
     """The non-mean neighbourhood reductions of the SAGE layers over `graph` (single GPU); a tuple of names: their
     concatenation [N, k * d] from one gather pass."""
@@ -150,12 +173,14 @@ class GCNConv(nn.Module):
     folds_post_affine = True  # forward(..., post_affine=(scale, shift)): see models/_stack.py
     emits_colsums = True      # forward(..., want_colsums=True): the output may carry its column sums (ops.COLSUMS)
     owns_next_bn_backward = True  # forward(..., next_bn=bn): see ops.propagate_linear
+    gather_dtype = None       # torch.bfloat16: the neighbour rows are gathered from a bfloat16 copy (_set_gather_dtype)
 
-    def __init__(self, in_channels, out_channels):
+    def __init__(self, in_channels, out_channels, gather_dtype=None):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.lin = nn.Linear(in_channels, out_channels, bias=False)
         self.bias = nn.Parameter(torch.zeros(out_channels))
+        _set_gather_dtype(self, gather_dtype)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -177,6 +202,8 @@ class GCNConv(nn.Module):
         `next_bn`: the training-mode BatchNorm1d this output goes through into the next conv's forward_after_bn, and
         nowhere else; where the fused kernel runs, this layer's autograd node then owns that BatchNorm's backward
         (ops.propagate_linear)."""
+        if self.gather_dtype is not None:
+            return _finish_composed(self._forward_bf16(x, edge_index, edge_weight), post_affine, ce)
         if ce is not None:
             return self._ce(x, edge_index, ce, None, None, edge_weight)
         weight, bias = self.lin.weight, self.bias
@@ -187,11 +214,14 @@ class GCNConv(nn.Module):
 
     def eval_operands(self, bn=None):
         """(W'^T, b', None) of this layer for an eval forward, the eval-mode BatchNorm `bn` behind it folded in."""
+        if self.gather_dtype is not None:
+            return None
         return ops.fold_bn_linear(self.lin.weight, self.bias, bn=bn)
 
     # opt-in cache of the static input features' aggregate (models/_stack.ConvStack.cache_input_aggregate)
     def aggregate_input(self, x, edge_index, edge_weight=None):
-        if self.in_channels > self.out_channels or not ops.aggregate_linear_ok(self.in_channels, self.out_channels):
+        if (self.gather_dtype is not None or self.in_channels > self.out_channels
+                or not ops.aggregate_linear_ok(self.in_channels, self.out_channels)):
             return None
         return _aggregate_input(x, edge_index, LOOPS_ADD_REMAINING, "gcn", edge_weight)
 
@@ -204,7 +234,22 @@ class GCNConv(nn.Module):
         """Eval forward (no_grad) from prepared operands (eval_operands; models/_stack.ConvStack keeps them per
         parameter state): one fused launch. `ce` = (y, mask): returns (None, stats). None when this layer / graph does
         not take the fused kernel (the caller then runs the ordinary forward)."""
+        if self.gather_dtype is not None:
+            return None
         return _forward_folded(self, x, edge_index, operands, ce, LOOPS_ADD_REMAINING, "gcn", False, edge_weight)
+
+    def _forward_bf16(self, x, edge_index, edge_weight=None):
+        """gather_dtype=torch.bfloat16: A_hat gathers bfloat16 rows at the narrower width — A_hat bf16(x W^T) + b for
+        in > out (the columns padded to a multiple of 8), (A_hat bf16(x)) W^T + b otherwise."""
+        if edge_weight is not None and edge_weight.requires_grad:
+            raise ValueError("GCNConv: gather_dtype and an edge_weight that requires grad exclude each other (the gradient "
+                             "in the edge weights is taken over fp32 rows)")
+        graph = get_graph(edge_index, x.size(0), LOOPS_ADD_REMAINING, edge_weight)
+        if self.in_channels > self.out_channels:
+            weight, bias, n = ops.pad_rows8(self.lin.weight, self.bias)
+            out = ops.propagate_rows_bf16(ops.linear(x, weight), graph, "gcn", bias=bias)
+            return out if n == self.out_channels else out[:, :self.out_channels]
+        return ops.linear(ops.propagate_bf16(x, graph, "gcn"), self.lin.weight, self.bias)
 
     @staticmethod
     def _learned(edge_weight):
@@ -234,6 +279,8 @@ class GCNConv(nn.Module):
         """self(bn(x), edge_index) for the BatchNorm1d in front of this layer. In a training forward on one GPU the
         normalised matrix is not written: the fused kernel gathers the raw rows and applies BatchNorm's affine map to
         the aggregate (ops.bn_propagate_linear). `colsums`: the column sums of x if its producer took them."""
+        if self.gather_dtype is not None:
+            return self.forward(bn(x, colsums=colsums), edge_index, edge_weight, ce=ce)
         if ce is not None:
             return self._ce(x, edge_index, ce, bn, colsums, edge_weight)
         if self._learned(edge_weight):
@@ -281,10 +328,13 @@ class SAGEConv(nn.Module):
     emits_colsums = True      # see GCNConv
     owns_next_bn_backward = True  # see GCNConv
 
-    def __init__(self, in_channels, out_channels, aggr="mean"):
+    gather_dtype = None       # see GCNConv
+
+    def __init__(self, in_channels, out_channels, aggr="mean", gather_dtype=None):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         k = _set_aggr(self, aggr, lists=True)
+        _set_gather_dtype(self, gather_dtype)
         self.lin_l = nn.Linear(k * in_channels, out_channels, bias=True)
         self.lin_r = nn.Linear(in_channels, out_channels, bias=False)
 
@@ -292,12 +342,12 @@ class SAGEConv(nn.Module):
     accepts_ce_pair = True
 
     def eval_operands(self, bn=None):
-        if self.aggr != "mean":
+        if self.aggr != "mean" or self.gather_dtype is not None:
             return None
         return ops.fold_bn_linear(self.lin_l.weight, self.lin_l.bias, root_weight=self.lin_r.weight, bn=bn)
 
     def aggregate_input(self, x, edge_index):
-        if (self.aggr != "mean" or self.in_channels > self.out_channels
+        if (self.aggr != "mean" or self.gather_dtype is not None or self.in_channels > self.out_channels
                 or not ops.aggregate_linear_ok(self.in_channels, self.out_channels, True)):
             return None
         return _aggregate_input(x, edge_index, LOOPS_KEEP, "mean")
@@ -308,6 +358,18 @@ class SAGEConv(nn.Module):
         agg = _aggregate(x, graph, self.aggr)
         return ops.linear(agg, self.lin_l.weight, self.lin_l.bias) + ops.linear(x, self.lin_r.weight)
 
+    def _forward_bf16(self, x, edge_index):
+        """gather_dtype=torch.bfloat16: the mean gathers bfloat16 rows at the narrower width — for in > out one product
+        x [W_l; W_r]^T whose left half is rounded and gathered, the root half (with lin_l's bias) being the fp32 addend;
+        otherwise lin_l(mean bf16(x)) + lin_r(x)."""
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        w_l, b_l, w_r = self.lin_l.weight, self.lin_l.bias, self.lin_r.weight
+        if self.in_channels > self.out_channels:
+            h, n = self._transform_first(x, w_l, b_l, w_r, pad=ops.pad_rows8)
+            out = ops.propagate_rows_bf16(h, graph, "mean", n=n)
+            return out if n == self.out_channels else out[:, :self.out_channels]
+        return ops.linear(ops.propagate_bf16(x, graph, "mean"), w_l, b_l) + ops.linear(x, w_r)
+
     def forward_from_aggregate(self, z, x, want_colsums=False, folded=None):
         if folded is not None:
             return _folded_from_aggregate(z, x, folded, True)
@@ -315,7 +377,7 @@ class SAGEConv(nn.Module):
 
     def forward_folded(self, x, edge_index, operands, ce=None):
         """See GCNConv.forward_folded."""
-        if self.aggr != "mean":
+        if self.aggr != "mean" or self.gather_dtype is not None:
             return None
         return _forward_folded(self, x, edge_index, operands, ce, LOOPS_KEEP, "mean", True)
 
@@ -335,16 +397,18 @@ class SAGEConv(nn.Module):
         return ops.ce_from_logits(self.forward(x, edge_index), y, mask)
 
     @staticmethod
-    def _transform_first(x, w_l, b_l, w_r):
+    def _transform_first(x, w_l, b_l, w_r, pad=ops.pad_rows4):
         """h = x [W_l; W_r]^T + [0; b_l] as ONE product ([N, 2 n], n = out rounded up to a multiple of 4): the left half is
         what the mean runs over, the right half the root term plus lin_l's bias (which PyG adds after the aggregation:
         a node without in-edges gets b_l + W_r x_i). The wide input (F = 1433 on Cora) is read once for both Linears."""
-        w_l, b_l, n = ops.pad_rows4(w_l, b_l)
-        w_r = ops.pad_rows4(w_r)[0]
+        w_l, b_l, n = pad(w_l, b_l)
+        w_r = pad(w_r)[0]
         return ops.linear(x, torch.cat([w_l, w_r]), torch.cat([torch.zeros_like(b_l), b_l])), n
 
     def forward_after_bn(self, x, edge_index, bn, colsums=None, want_colsums=False, ce=None):
         """See GCNConv.forward_after_bn; the root term lin_r(bn(x)_i) gets the affine map as its rows are loaded."""
+        if self.gather_dtype is not None:
+            return self.forward(bn(x, colsums=colsums), edge_index, ce=ce)
         if self.aggr != "mean":
             return _finish_composed(self._forward_composed(bn(x, colsums=colsums), edge_index), None, ce)
         if ce is not None:
@@ -357,6 +421,8 @@ class SAGEConv(nn.Module):
         return self.forward(bn(x, colsums=colsums), edge_index, want_colsums=want_colsums)
 
     def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None, next_bn=None):
+        if self.gather_dtype is not None:
+            return _finish_composed(self._forward_bf16(x, edge_index), post_affine, ce)
         if self.aggr != "mean":
             return _finish_composed(self._forward_composed(x, edge_index), post_affine, ce)
         if ce is not None:
@@ -399,11 +465,14 @@ class MySAGEConv(nn.Module):
     emits_colsums = True      # see GCNConv
     owns_next_bn_backward = True  # see GCNConv
 
-    def __init__(self, in_channels, out_channels, add_self_loops=True, aggr="mean"):
+    gather_dtype = None       # see GCNConv
+
+    def __init__(self, in_channels, out_channels, add_self_loops=True, aggr="mean", gather_dtype=None):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.add_self_loops = add_self_loops
         _set_aggr(self, aggr)
+        _set_gather_dtype(self, gather_dtype)
         self.lin_l = nn.Linear(in_channels, out_channels)
         self.lin_r = nn.Linear(in_channels, out_channels)
 
@@ -418,15 +487,28 @@ class MySAGEConv(nn.Module):
         out = _aggregate(h[:, :n], graph, self.aggr) + h[:, n:]
         return out if n == self.out_channels else out[:, :self.out_channels]
 
+    def _forward_bf16(self, x, edge_index):
+        """gather_dtype=torch.bfloat16: the mean gathers bfloat16 rows at the narrower width — [lin_l(x), lin_r(x)] in one
+        product, the left half rounded and gathered, the right half the fp32 addend, for in > out; lin_l(mean bf16(x)) +
+        lin_r(x) otherwise (with the self-loop a row's mean weights sum to 1, so b_l passes through the mean; without
+        add_self_loops the layer always transforms first: a row without entries must get no b_l)."""
+        graph = get_graph(edge_index, x.size(0), LOOPS_REMOVE_ADD if self.add_self_loops else LOOPS_KEEP)
+        w_l, b_l, w_r, b_r = self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, self.lin_r.bias
+        if self.in_channels > self.out_channels or not self.add_self_loops:
+            h, n = self._transform_both(x, w_l, b_l, w_r, b_r, pad=ops.pad_rows8)
+            out = ops.propagate_rows_bf16(h, graph, "mean", n=n)
+            return out if n == self.out_channels else out[:, :self.out_channels]
+        return ops.linear(ops.propagate_bf16(x, graph, "mean"), w_l, b_l) + ops.linear(x, w_r, b_r)
+
     def eval_operands(self, bn=None):
-        if not self.add_self_loops or self.aggr != "mean":
+        if not self.add_self_loops or self.aggr != "mean" or self.gather_dtype is not None:
             return None
         return ops.fold_bn_linear(self.lin_l.weight, self.lin_l.bias, self.lin_r.bias, root_weight=self.lin_r.weight,
                                   bn=bn)
 
     def aggregate_input(self, x, edge_index):
-        if (not self.add_self_loops or self.aggr != "mean" or self.in_channels > self.out_channels
-                or not ops.aggregate_linear_ok(self.in_channels, self.out_channels, True)):
+        if (not self.add_self_loops or self.aggr != "mean" or self.gather_dtype is not None
+                or self.in_channels > self.out_channels or not ops.aggregate_linear_ok(self.in_channels, self.out_channels, True)):
             return None
         return _aggregate_input(x, edge_index, LOOPS_REMOVE_ADD, "mean")
 
@@ -439,7 +521,7 @@ class MySAGEConv(nn.Module):
     def forward_folded(self, x, edge_index, operands, ce=None):
         """See GCNConv.forward_folded (mean over N(i) + {i}: the weights of a row sum to 1, so both biases and the
         BatchNorm shift ride in the kernel's bias)."""
-        if self.aggr != "mean":
+        if self.aggr != "mean" or self.gather_dtype is not None:
             return None
         return _forward_folded(self, x, edge_index, operands, ce, LOOPS_REMOVE_ADD, "mean", True)
 
@@ -462,16 +544,18 @@ class MySAGEConv(nn.Module):
         return ops.ce_from_logits(self.forward(x, edge_index), y, mask)
 
     @staticmethod
-    def _transform_both(x, w_l, b_l, w_r, b_r):
+    def _transform_both(x, w_l, b_l, w_r, b_r, pad=ops.pad_rows4):
         """h = [lin_l(x), lin_r(x)] as ONE product (models/graphsage.py:49-50 runs two Linears over the same x): [N, 2 n],
         n = out rounded up to a multiple of 4. b_l stays inside the mean, as in the reference (a row without entries —
         add_self_loops=False and no in-edge — gets no b_l)."""
-        w_l, b_l, n = ops.pad_rows4(w_l, b_l)
-        w_r, b_r, _ = ops.pad_rows4(w_r, b_r)
+        w_l, b_l, n = pad(w_l, b_l)
+        w_r, b_r, _ = pad(w_r, b_r)
         return ops.linear(x, torch.cat([w_l, w_r]), torch.cat([b_l, b_r])), n
 
     def forward_after_bn(self, x, edge_index, bn, colsums=None, want_colsums=False, ce=None):
         """See GCNConv.forward_after_bn."""
+        if self.gather_dtype is not None:
+            return self.forward(bn(x, colsums=colsums), edge_index, ce=ce)
         if self.aggr != "mean":
             return _finish_composed(self._forward_composed(bn(x, colsums=colsums), edge_index), None, ce)
         if ce is not None:
@@ -486,6 +570,8 @@ class MySAGEConv(nn.Module):
         return self.forward(bn(x, colsums=colsums), edge_index, want_colsums=want_colsums)
 
     def forward(self, x, edge_index, post_affine=None, want_colsums=False, ce=None, next_bn=None):
+        if self.gather_dtype is not None:
+            return _finish_composed(self._forward_bf16(x, edge_index), post_affine, ce)
         if self.aggr != "mean":
             return _finish_composed(self._forward_composed(x, edge_index), post_affine, ce)
         if ce is not None:

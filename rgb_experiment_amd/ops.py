@@ -781,6 +781,144 @@ def propagate_rows_ce(h, graph, kind, n, n_classes, y, mask, bias=None):
     return (None if pair else loss), stats
 
 
+# ---- the row gather with the gathered matrix stored as bfloat16 (rgbx_spmm_csr_bf16) ----------------------------------
+# The gather is memory-bound and the gathered table is most of its bytes; stored as bfloat16 that term halves. Values are
+# rounded ONCE (to nearest-even, rgbx_rows_f32_to_bf16) in front of the gather; every sum, the addend, the bias and the
+# output are fp32. Opt-in (the layers' gather_dtype keyword): no fp32 route goes through here.
+
+BF16_MAX_WIDTH = 256  # rgbx_spmm_csr_bf16_supported: wider matrices are gathered in column blocks of this many
+
+
+def pad_rows8(weight, *vectors):
+    """pad_rows4 for the bfloat16 gather: zero rows up to the next multiple of 8 (a lane of rgbx_spmm_csr_bf16 holds 8
+    columns = 16 bytes). Returns (weight', *vectors', padded out)."""
+    n = weight.size(0)
+    p = (-n) % 8
+    if p == 0:
+        return (weight,) + vectors + (n,)
+    pad = torch.nn.functional.pad
+    return (pad(weight, (0, 0, 0, p)),) + tuple(None if v is None else pad(v, (0, p)) for v in vectors) + (n + p,)
+
+
+def _no_dist_bf16(graph):
+    if _is_dist(graph):
+        raise NotImplementedError("the bfloat16 gather is not implemented on the partitioned (distributed) route")
+
+
+def to_bf16_rows(t):
+    """fp32 [n, d] (rows contiguous, possibly a column slice of a wider matrix) -> a fresh contiguous torch.bfloat16
+    [n, d], rounded to nearest-even by rgbx_rows_f32_to_bf16 (the bits of t.to(torch.bfloat16)); no autograd."""
+    _lib.require_device(t)
+    t = t.detach()
+    t = t if t.dim() != 2 or t.stride(-1) == 1 or t.size(1) <= 1 else t.contiguous()
+    ps, lds = _lib.mat(t, "t")
+    n, d = t.shape
+    out = torch.empty((n, d), dtype=torch.bfloat16, device=t.device)
+    with _Timed("rows_to_bf16", f"d{d}" if _EVENT_SINK is not None else None):
+        _lib.check(_lib.load().rgbx_rows_f32_to_bf16(ps, lds, out.data_ptr(), max(d, 1), n, d, _lib.stream_ptr()),
+                   "rgbx_rows_f32_to_bf16")
+    return out
+
+
+def spmm_bf16_raw(csr, w, rs, xb, y=None, a=1.0, b=0.0, bias=None, out=None, out_dtype=torch.float32, kind="spmm_bf16"):
+    """out[i] = a*rs[i]*sum_p w[p]*xb[col[p]] + b*y[i] + bias over `csr` with xb stored as bfloat16 and every sum in
+    fp32 (no autograd; rgbx_spmm_csr_bf16). `out_dtype`: torch.float32, or torch.bfloat16 for the result rounded to
+    nearest-even in the kernel's store; `out` (of that dtype) may be given. The width must be a multiple of 8 (pad_rows8);
+    beyond BF16_MAX_WIDTH the columns are gathered in blocks of that many (one launch each, the same sums)."""
+    if not isinstance(xb, torch.Tensor) or xb.dtype != torch.bfloat16:
+        raise RuntimeError(f"spmm_bf16_raw: xb must be a torch.bfloat16 matrix, got {getattr(xb, 'dtype', type(xb))}")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"spmm_bf16_raw: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
+    _lib.require_device(xb, y, bias, out)
+    xb = xb if xb.stride(-1) == 1 else xb.contiguous()
+    px, ldx = _lib.mat_bf16(xb, "xb")
+    N, d = csr.N, xb.size(1)
+    if d % 8:
+        raise RuntimeError(f"spmm_bf16_raw: width {d} is no multiple of 8 (zero-pad the rows: ops.pad_rows8)")
+    if out is None:
+        out = torch.empty((N, d), dtype=out_dtype, device=xb.device)
+    elif out.dtype != out_dtype or tuple(out.shape) != (N, d):
+        raise RuntimeError(f"spmm_bf16_raw: out is {out.dtype} {tuple(out.shape)}, expected {out_dtype} {(N, d)}")
+    po, ldo = _lib.mat(out, "out") if out_dtype == torch.float32 else _lib.mat_bf16(out, "out")
+    py, ldy = (0, 0) if y is None else _lib.mat(y, "y")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != d):
+        raise RuntimeError(f"spmm_bf16_raw: bias must be float32 [{d}]")
+    pb = _lib.ptr(bias)
+    lib = _lib.load()
+    for c0 in range(0, max(d, 1), BF16_MAX_WIDTH):
+        dc = min(BF16_MAX_WIDTH, d - c0)
+        split, _scratch = csr.split_arg(dc, xb.device)
+        f32 = (po + 4 * c0, ldo, 0, 0) if out_dtype == torch.float32 else (0, 0, po + 2 * c0, ldo)
+        with _Timed(kind, f"rows+d{dc}" if _EVENT_SINK is not None else None):
+            _lib.check(
+                lib.rgbx_spmm_csr_bf16(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w), _lib.ptr(rs), px + 2 * c0, ldx,
+                                       py + 4 * c0 if py else 0, ldy, pb + 4 * c0 if pb else 0, *f32, N, dc, float(a),
+                                       float(b), None if split is None else ctypes.byref(split), _lib.stream_ptr()),
+                "rgbx_spmm_csr_bf16")
+    return out
+
+
+class _PropagateRowsBF16(torch.autograd.Function):
+    """_PropagateRows in mode 'plain' with the gathered half stored as bfloat16: out = P bf16(h[:, :n]) (+ h[:, n:2n])
+    (+ bias), fp32 sums and output. Backward: g_h[:, :n] = P^T bf16(g_out) on the transposed CSR, g_h[:, n:] = g_out,
+    g_bias = column sums of g_out; the rounding counts as the identity in the gradient. Only the passes whose gradients
+    are asked for run."""
+
+    @staticmethod
+    def forward(ctx, h, graph, kind, n, bias):
+        split = h.size(1) == 2 * n
+        if not split and h.size(1) != n:
+            raise RuntimeError(f"propagate_rows_bf16: h is {tuple(h.shape)} for n = {n}")
+        h = h if h.stride(-1) == 1 else h.contiguous()
+        w, rs = _kind_weights(graph, kind)
+        xb = to_bf16_rows(h[:, :n] if split else h)
+        y = h[:, n:] if split else None
+        b = None if bias is None else bias.detach().contiguous()
+        ctx.graph, ctx.kind, ctx.n, ctx.split = graph, kind, n, split
+        ctx.has_bias, ctx.h_shape = bias is not None, tuple(h.shape)
+        return spmm_bf16_raw(graph.fwd, w, rs, xb, y=y, a=1.0, b=1.0, bias=b, kind=f"{kind}_fwd_bf16")
+
+    @staticmethod
+    def backward(ctx, g):
+        graph, kind, n = ctx.graph, ctx.kind, ctx.n
+        gy = g.contiguous()
+        gh = gb = None
+        if ctx.needs_input_grad[0]:
+            wt, _ = _kind_weights(graph, kind, transposed=True)
+            gh = torch.empty(ctx.h_shape, dtype=torch.float32, device=gy.device)
+            if ctx.split:
+                gh[:, n:].copy_(gy)
+            spmm_bf16_raw(graph.bwd, wt, None, to_bf16_rows(gy), out=gh[:, :n] if ctx.split else gh,
+                          kind=f"{kind}_bwd_bf16")
+        if ctx.has_bias and ctx.needs_input_grad[4]:
+            gb = gy.sum(0)
+        return gh, None, None, None, gb
+
+
+def propagate_rows_bf16(h, graph, kind, n=None, bias=None):
+    """P h[:, :n] (+ h[:, n:2n]) (+ bias) with the gathered left half rounded to bfloat16 — see _PropagateRowsBF16. `kind`
+    in 'gcn' / 'mean' / 'sum'; `n` defaults to h's width (no addend half) and must be a multiple of 8: the caller
+    zero-pads (pad_rows8)."""
+    if kind not in ("gcn", "mean", "sum"):
+        raise ValueError(f"propagate_rows_bf16: kind must be 'gcn', 'mean' or 'sum', got {kind!r}")
+    _no_dist_bf16(graph)
+    _lib.require_device(h, bias)
+    n = h.size(1) if n is None else n
+    if n % 8:
+        raise RuntimeError(f"propagate_rows_bf16: n = {n} is no multiple of 8 (zero-pad the rows: ops.pad_rows8)")
+    return _PropagateRowsBF16.apply(h, graph, kind, n, bias)
+
+
+def propagate_bf16(x, graph, kind):
+    """P x with x rounded to bfloat16 for the gather (fp32 sums and output); any width: columns are zero-padded to a
+    multiple of 8 here and sliced off again (autograd pads the gradient)."""
+    _no_dist_bf16(graph)
+    d = x.size(1)
+    if d % 8 == 0:
+        return propagate_rows_bf16(x, graph, kind)
+    return propagate_rows_bf16(torch.nn.functional.pad(x, (0, (-d) % 8)), graph, kind)[:, :d]
+
+
 def fused_linear_ok(graph, in_channels, out_channels, root=False, x=None):
     """The fused aggregate-then-transform kernel applies: supported widths, aggregating at the input width is
     not the more expensive order, and the graph is a single-GPU one — or a partitioned one asked to propagate its
