@@ -1109,6 +1109,64 @@ int rgbx_rgcn_mix_bwd_coef_f32(const int32_t* rowptr, const int32_t* col, const 
                                const float* gout, int64_t ldg, float* d, int64_t N, int R, int B, int C,
                                const rgbx_row_split_t* split, rgbx_stream_t stream);
 
+/* ---- FiLMConv / GNN-FiLM: the target modulates every message per channel, before the nonlinearity ------------------- */
+
+/* FiLMConv.forward [PyG] loops over the relations, masks the edge list and propagates once per relation with
+ * `message = act(gamma_i * x_j + beta_i)` on [E_r, C] tensors (Brockschmidt, "GNN-FiLM: Graph Neural Networks with
+ * Feature-wise Linear Modulation"). The reference's zoo has no such layer. Here the dense products come first, with R
+ * relations and C channels:
+ *   h  = x @ [W_0 | ... | W_{R-1}]           viewed [N*R, C]:   row j*R + r = the message row of source j under r
+ *   fb = [film_0(x) | ... | film_{R-1}(x)]   viewed [N*R, 2C]:  row i*R + r = beta_r[i] | gamma_r[i]   (beta FIRST)
+ * (each its own pointer and leading dimension: column blocks of wider matrices are taken as they are; `gofs` >= C is
+ * the offset of gamma inside a film row, C for the layout above, and the leading dimension of fb is >= gofs + C, so
+ * that the column block [a, b) of a wider fb is the view that starts at beta's column a with gofs = the full C) and
+ * ONE pass over the edges forms, for the edge j -> i of relation r in slot p,
+ *   z_p = fmaf(gamma_r[i], h[j*R + r], beta_r[i]),   m_p = act(z_p),   act: 0 = identity, 1 = relu.
+ * The edges are taken as they are (RGBX_LOOPS_KEEP). No entry point uses float atomics, scratch or LDS; nothing per
+ * edge is saved: both backward passes recompute z with the same fmaf, so the relu mask is the forward's (relu'(0) = 0).
+ * Every sum runs in a fixed order (slots of a lane group in slot order, lane groups, hub-row chunks in chunk order) and
+ * every output row is written: two runs are bit-identical. N * R >= 2^31 is refused with RGBX_E_RANGE. */
+
+/* 1 if the kernels take C channels (the widths of rgbx_transformer_supported(1, C)), else 0. */
+int rgbx_film_supported(int C);
+
+/* Forward over the target-grouped CSR, out [N, C]:
+ *   out[i,:] = y0[i,:] + sum_p w[p] * act(z_p)
+ * `etype` / `w` [nnz]: the relation and the weight of every slot (w: the mean weights of rgbx_rgcn_slot_norm_f32, or
+ * ones for aggr="add"); the film row (i, etype[p]) is read from device memory per slot. etype == NULL is the
+ * single-relation call (R must be 1, w is ignored): the weight is 1.0f / (float)len from rowptr with mean != 0, else 1,
+ * and the target's film row stays in registers. y0 [N, C] is optional (NULL: zeros) and carries the dense skip term,
+ * added after the slot loop so that out is written once; out must alias none of h, fb, y0. A row without slots stores
+ * y0 (or exact zeros). split->partial holds n_chunks * C floats; y0 rides on a row's first chunk and the partials are
+ * added in chunk order. */
+int rgbx_film_fwd_f32(const int32_t* rowptr, const int32_t* col, const int32_t* etype, const float* w, const float* h,
+                      int64_t ldh, const float* fb, int64_t ldfb, int64_t gofs, const float* y0, int64_t ldy, float* out,
+                      int64_t ldo, int64_t N, int R, int C, int mean, int act, const rgbx_row_split_t* split,
+                      rgbx_stream_t stream);
+
+/* Backward, source side, over the relation-expanded TRANSPOSED CSR of N*R rows (row j*R + r = the out-edges of j with
+ * relation r, col_t = targets i; with R = 1 the plain transposed CSR):
+ *   g_h[j*R + r,:] = sum_q w_q * gamma_r[i_q] (.) act'(z_q) (.) gout[i_q,:],   g_h [N*R, C].
+ * The slot weight w_q is w_t[q] (in this CSR's slot order), or with w_t == NULL 1.0f / (float)indeg(i_q) read from the
+ * forward rowptr `deg_rowptr` [N + 1], or 1 with both NULL. A row without slots stores zeros. split->partial holds
+ * n_chunks * C floats. */
+int rgbx_film_bwd_src_f32(const int32_t* rowptr_x, const int32_t* col_t, const float* w_t, const int32_t* deg_rowptr,
+                          const float* h, int64_t ldh, const float* fb, int64_t ldfb, int64_t gofs, const float* gout,
+                          int64_t ldg, float* g_h, int64_t ldgh, int64_t N, int R, int C, int act,
+                          const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward, film side, over the relation-expanded FORWARD CSR of N*R rows (row i*R + r = the in-edges of i with
+ * relation r, col_e = sources j; with R = 1 the plain forward CSR), g_fb [N*R, gofs + C] in fb's layout (the same gofs;
+ * columns between the two blocks are not touched):
+ *   g_fb[i*R + r, :C] = w (.) gout[i,:] (.) sum_p act'(z_p)          (g_beta)
+ *   g_fb[i*R + r, gofs:gofs+C] = w (.) gout[i,:] (.) sum_p act'(z_p) (.) h[col_e[p]*R + r,:]   (g_gamma)
+ * with ONE weight per row, w = 1.0f / (float)len with mean != 0 (the bits of the per-slot mean weights), else 1. A row
+ * without slots stores zeros. split->partial holds n_chunks * 2C floats: a chunk's record is (g_beta | g_gamma). */
+int rgbx_film_bwd_film_f32(const int32_t* rowptr_e, const int32_t* col_e, const float* h, int64_t ldh, const float* fb,
+                           int64_t ldfb, int64_t gofs, const float* gout, int64_t ldg, float* g_fb, int64_t ldgfb,
+                           int64_t N, int R, int C, int mean, int act, const rgbx_row_split_t* split,
+                           rgbx_stream_t stream);
+
 /* ---- GMMConv / MoNet: a trained Gaussian mixture over the pseudo-coordinates of every edge --------------------------- */
 
 /* Every edge j -> i carries D pseudo-coordinates, e [nnz, D] with one row PER SLOT of the target-grouped CSR (its own

@@ -176,6 +176,10 @@ SIGNATURES = {
     "rgbx_rgcn_mix_fwd_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],
     "rgbx_rgcn_mix_bwd_src_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],
     "rgbx_rgcn_mix_bwd_coef_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _P, _P],
+    "rgbx_film_supported": [_I],
+    "rgbx_film_fwd_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _I, _I, _P, _P],
+    "rgbx_film_bwd_src_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],
+    "rgbx_film_bwd_film_f32": [_P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _I, _I, _P, _P],
     "rgbx_gmm_supported": [_I, _I, _I],
     "rgbx_gmm_fwd_f32": [_P, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],
     "rgbx_gmm_bwd_src_f32": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],

@@ -282,7 +282,8 @@ def experiment(model_init_param: dict, *,
     one without (``gine`` then fails at its forward, which needs the argument). ``use_edge_type=True`` (an addition, off by
     default): ``data.edge_type`` (int64 [E], one relation per edge) goes to the device with the data and into the forward
     arguments as ``edge_type``, for ``model_name="rgcn"`` (models.RGCN, built with ``num_relations`` and optionally
-    ``num_bases`` in ``model_init_param``) and for a caller's ``model=`` whose forward takes ``edge_type`` (any other
+    ``num_bases`` in ``model_init_param``), for ``model_name="film"`` (models.FiLM, built with ``num_relations``; without
+    the flag it runs with one relation) and for a caller's ``model=`` whose forward takes ``edge_type`` (any other
     model_name: ValueError). Not with ``to_undirected_graph`` (that call carries no types: ValueError) and not on the
     partitioned route (NotImplementedError). With the flag off a ``Data`` that happens to carry an ``edge_type`` behaves
     exactly as one without."""
@@ -322,9 +323,9 @@ def experiment(model_init_param: dict, *,
         if model is not None:
             if not isinstance(model, nn.Module) or "edge_type" not in inspect.signature(model.forward).parameters:
                 raise ValueError("use_edge_type=True: the forward of the module passed as model= takes no edge_type")
-        elif name != "rgcn":
+        elif name not in ("rgcn", "film"):
             raise ValueError(f"use_edge_type=True: model_name={model_name!r} takes no edge types; the routes that do "
-                             "are rgcn and a model= whose forward takes edge_type")
+                             "are rgcn, film and a model= whose forward takes edge_type")
         if to_undirected_graph:
             raise ValueError("use_edge_type=True cannot be combined with to_undirected_graph=True: the reference's "
                              "to_undirected call (:235-238) carries no types")

@@ -13,6 +13,7 @@ computing their ``propagate`` in HIP kernels (rgb_experiment_amd.ops).
 Dense X·W^T products go through hipBLASLt (forward, input gradient) and rgbx_gemm_tn_f32 (weight
 gradient, split-K fp32 MFMA); everything indexed by edge_index goes through librgbx_hip.so.
 """
+import copy
 import math
 
 import torch
@@ -1091,6 +1092,110 @@ class RGCNConv(nn.Module):
         if self.root is None and self.bias is not None:
             out = out + self.bias
         return out
+
+
+def _reset_module(module):
+    """PyG's `reset`: a module's own reset_parameters, else that of its children, recursively."""
+    if hasattr(module, "reset_parameters"):
+        module.reset_parameters()
+    else:
+        for child in module.children():
+            _reset_module(child)
+
+
+class FiLMConv(nn.Module):
+    """Feature-wise linear modulation [PyG FiLMConv; Brockschmidt, "GNN-FiLM: Graph Neural Networks with Feature-wise
+    Linear Modulation"]: the TARGET node modulates every incoming message per channel, before the nonlinearity,
+        beta_r, gamma_r = films[r](x).split(out, dim=-1)               (beta FIRST, then gamma: PyG's order)
+        beta_s, gamma_s = film_skip(x).split(out, dim=-1)
+        out_i = act(gamma_s[i] * lin_skip(x)[i] + beta_s[i])
+              + sum_r AGG_{j : (j -> i) has relation r} act(gamma_r[i] * lins[r](x)[j] + beta_r[i])
+    with AGG the mean per (target, relation) over the edges AS GIVEN (duplicates count twice, self-loops are ordinary
+    edges; a (target, relation) pair without an edge contributes 0, a node without in-edges gets the skip term alone), or
+    the sum with aggr="add" / "sum". Module names and shapes are PyG's: lins[r] = Linear(in, out, bias=False), films[r] =
+    Linear(in, 2 * out) with bias or a deep copy of `nn`, lin_skip = Linear(in, out, bias=False), film_skip = Linear(in,
+    2 * out, bias=False) or a deep copy of `nn`. `act`: "relu" (an nn.ReLU instance is accepted), None or "identity".
+    With num_relations=1 `edge_type` is not needed (and ignored, as in PyG).
+
+    The dense products run first (h and fb are each ONE product over the concatenated weights when `nn` is None) and the
+    edges are touched once, in the rgbx_film_* kernels (ops.film_aggregate); the skip term is dense per-node work on
+    torch, handed to the kernel as y0. THE FORM MATERIALISES N * R * 3 * out FLOATS (h: N * R * out, fb: N * R * 2 * out).
+    An output width outside the kernels' set is zero-padded and sliced off again. Parity with PyG's implementation is
+    unpinned (PyG is not installed where this project runs): the formulas above are the contract.
+
+    Refused: a tuple in_channels (ValueError), an aggr other than mean / add / sum (ValueError), any other act
+    (NotImplementedError). Out of scope: bipartite inputs, bf16 storage, the node-partitioned (distributed) route."""
+
+    def __init__(self, in_channels, out_channels, num_relations=1, nn=None, act="relu", aggr="mean"):
+        super().__init__()
+        tnn = torch.nn  # the argument `nn` (PyG's name) shadows the module in here
+        if not isinstance(in_channels, int) or isinstance(in_channels, bool):
+            raise ValueError(f"FiLMConv: in_channels must be one int (got {in_channels!r}): bipartite inputs are not "
+                             "implemented")
+        if aggr not in ("mean", "add", "sum"):
+            raise ValueError(f"FiLMConv: aggr={aggr!r} (mean, add or sum)")
+        if isinstance(act, tnn.ReLU):
+            act = "relu"
+        if not (act is None or isinstance(act, str)) or act not in ("relu", "identity", None):
+            raise NotImplementedError(f"FiLMConv: act={act!r} is not built (relu, None or identity: the nonlinearity "
+                                      "lives in the kernels)")
+        if num_relations < 1:
+            raise ValueError("FiLMConv: num_relations must be at least 1")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.num_relations, self.act, self.aggr = num_relations, act, aggr
+        self.custom_film = nn is not None
+        self.lins, self.films = tnn.ModuleList(), tnn.ModuleList()
+        for _ in range(num_relations):
+            self.lins.append(Linear(in_channels, out_channels, bias=False))
+            self.films.append(copy.deepcopy(nn) if nn is not None else Linear(in_channels, 2 * out_channels))
+        self.lin_skip = Linear(in_channels, out_channels, bias=False)
+        self.film_skip = copy.deepcopy(nn) if nn is not None else Linear(in_channels, 2 * out_channels, bias=False)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for module in list(self.lins) + list(self.films) + [self.lin_skip, self.film_skip]:
+            _reset_module(module)  # the Linear's own default, as in PyG's layer
+
+    def kernel_channels(self):
+        """The width the aggregation runs at: out_channels where the kernels take it (their set up to 256, and column
+        blocks of 256 above it whose last block is in the set), else the next multiple of 4."""
+        C = self.out_channels
+        last = C if C <= ops.FILM_BLOCK else (C % ops.FILM_BLOCK or ops.FILM_BLOCK)
+        return C if GATConv.kernel_channels(last) == last else (C + 3) // 4 * 4
+
+    def forward(self, x, edge_index, edge_type=None):
+        R, C = self.num_relations, self.out_channels
+        if R > 1 and (not torch.is_tensor(edge_type) or edge_type.dtype != torch.int64 or edge_type.dim() != 1
+                      or edge_type.numel() != edge_index.size(1)):
+            got = f"{edge_type.dtype} {tuple(edge_type.shape)}" if torch.is_tensor(edge_type) else type(edge_type).__name__
+            raise ValueError(f"FiLMConv: edge_type must be int64 [E] = [{edge_index.size(1)}], got {got}")
+        if x.dim() != 2 or x.size(1) != self.in_channels:
+            raise ValueError(f"FiLMConv: x {tuple(x.shape)} for in_channels={self.in_channels}")
+        if R == 1:
+            edge_type = None  # one relation: every edge has it, whatever the caller's vector says (PyG ignores it too)
+        _lib.require_device(x, edge_type)
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        Cp = self.kernel_channels()
+        pad = torch.nn.functional.pad
+        relu = torch.relu if self.act == "relu" else (lambda t: t)
+        rows = (lambda w: w) if Cp == C else (lambda w: pad(w, (0, 0, 0, Cp - C)))       # zero weight rows
+        cols = (lambda t: t) if Cp == C else (lambda t: pad(t, (0, Cp - C)))             # zero columns / bias entries
+        # a padded channel has h = beta = gamma = 0: z = 0, which is 0 under both activations, and its cotangent is 0
+        h = ops.linear(x, torch.cat([rows(lin.weight) for lin in self.lins]))
+        if self.custom_film:
+            parts = []
+            for film in self.films:
+                beta, gamma = film(x).split(C, dim=-1)
+                parts += [cols(beta), cols(gamma)]
+            fb = torch.cat(parts, dim=1)
+        else:   # one product: per relation the beta rows, then the gamma rows
+            w = torch.cat([rows(blk) for film in self.films for blk in film.weight.split(C, dim=0)])
+            b = torch.cat([cols(blk) for film in self.films for blk in film.bias.split(C, dim=0)])
+            fb = ops.linear(x, w, b)
+        beta_s, gamma_s = self.film_skip(x).split(C, dim=-1)
+        y0 = cols(relu(gamma_s * self.lin_skip(x) + beta_s))
+        out = ops.film_aggregate(h, fb, graph, edge_type, R, aggr=self.aggr, act=self.act, y0=y0)
+        return out if Cp == C else out[:, :C]
 
 
 class GMMConv(nn.Module):

@@ -3439,7 +3439,8 @@ class TypedView:
     relation), w_f[p] = 1 / #{p' in the row of p with p's relation} (rgbx_rgcn_slot_norm_f32) and w_t = w_f[t2f];
     `ones` for aggr="add"; `rel`, the forward slots grouped by relation as a CSR of R rows (rel_ptr [R + 1], rel_slots
     [E], a stable grouping: slot order inside a relation), which the reduction of g_comp walks. `select` holds the index
-    sets of the select form and is built on first use."""
+    sets of the select form and `expand_fwd` the relation-expanded forward CSR (FiLMConv's film pass); each is built on
+    first use."""
 
     def __init__(self, graph, R, etype_f, etype_t, w_f, w_t, rel, etype_edge):
         self.graph, self.R = graph, R
@@ -3447,6 +3448,7 @@ class TypedView:
         self.ones = torch.ones_like(w_f)
         self._etype_edge = etype_edge  # int64 [E], per input edge
         self._select = None
+        self._expand_fwd = None
 
     def weights(self, aggr, transposed=False):
         if aggr != "mean":
@@ -3473,6 +3475,22 @@ class TypedView:
                 w_bwd = self.w_f
             self._select = (fwd, bwd, w_bwd)
         return self._select
+
+    @property
+    def expand_fwd(self):
+        """The relation-expanded FORWARD CSR of N * R rows: row i * R + r holds the in-edges of i with relation r, its
+        columns are their sources (rgbx_csr_build on the keys i * R + r, with its own hub plan). A row's length is the
+        count behind the mean weight of its slots, so the film pass of FiLMConv takes ONE weight per row, 1 / len. With one
+        relation it is the graph's forward CSR itself. N * R >= 2^31 is refused. Built on first use, once per view."""
+        if self._expand_fwd is None:
+            from .graph import LOOPS_KEEP, build_csr
+            g, R = self.graph, self.R
+            if g.N * R >= 2 ** 31:
+                raise RuntimeError(f"typed_view: the relation-expanded index sets hold N * R = {g.N} * {R} rows, beyond "
+                                   "int32")
+            self._expand_fwd = g.fwd if R == 1 else build_csr(g._dst * R + self._etype_edge, g._src, g.N * R,
+                                                              LOOPS_KEEP)
+        return self._expand_fwd
 
 
 def typed_view(graph, edge_type, num_relations):
@@ -3685,6 +3703,172 @@ def rgcn_aggregate(h, graph, edge_type, num_relations, comp=None, aggr="mean", y
     if comp is None:
         return _RGCNSelect.apply(h, y0, view, aggr)
     return _RGCNMix.apply(h, comp, y0, view, aggr)
+
+
+# ---- FiLMConv: the target modulates every message per channel, before the nonlinearity ---------------------------------
+
+_FILM_AGGRS = {"mean": "mean", "add": "add", "sum": "add"}
+_FILM_ACTS = {"relu": 1, "identity": 0, None: 0}  # the kernels' `act`
+FILM_BLOCK = 256  # wider inputs run as column blocks of this many channels
+
+
+def film_supported(C):
+    return bool(_lib.load().rgbx_film_supported(C))
+
+
+def film_fwd_raw(hv, fv, gofs, graph, view, mean, act, y0=None):
+    """rgbx_film_fwd_f32 (no autograd): hv [N * R, C] and fv [N * R, gofs + C] (beta at column 0, gamma at column gofs)
+    -> out [N, C]. `view`: the TypedView, or None for the single-relation call; `mean` / `act`: the kernels' ints."""
+    _lib.require_device(hv, fv, y0)
+    lib = _lib.load()
+    csr, N, C, dev = graph.fwd, graph.fwd.N, hv.size(1), hv.device
+    R = 1 if view is None else view.R
+    # the relation and the weight of every slot; one relation: none of either, the kernel divides by the row length
+    etype, w = (None, None) if view is None else (view.etype_f, view.w_f if mean else view.ones)
+    out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: y0 / zeros)
+    ph, ldh = _lib.mat(hv, "h")
+    pf, ldf = _lib.mat(fv, "fb")
+    py, ldy = (0, 0) if y0 is None else _lib.mat(y0, "y0")
+    po, ldo = _lib.mat(out, "out")
+    split_ref, _, _scratch = _attn_split(csr, C, dev)
+    with _Timed("film_fwd"):
+        _lib.check(lib.rgbx_film_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(etype), _lib.ptr(w), ph, ldh,
+                                         pf, ldf, gofs, py, ldy, po, ldo, N, R, C, int(mean), int(act), split_ref,
+                                         _lib.stream_ptr()), "rgbx_film_fwd_f32")
+    return out
+
+
+def film_bwd_raw(hv, fv, gofs, gout, graph, view, mean, act, want_h=True, want_fb=True):
+    """rgbx_film_bwd_src_f32 and rgbx_film_bwd_film_f32 (no autograd), each launched only when asked for: (g_h [N * R, C]
+    or None, g_fb in fv's shape and layout or None)."""
+    _lib.require_device(hv, fv, gout)
+    lib = _lib.load()
+    N, C, dev = graph.fwd.N, hv.size(1), hv.device
+    R = 1 if view is None else view.R
+    ph, ldh = _lib.mat(hv, "h")
+    pf, ldf = _lib.mat(fv, "fb")
+    pg, ldg = _lib.mat(gout, "gout")
+    g_h = g_fb = None
+    if want_h:
+        if view is None:  # the plain transposed CSR; the mean weight of a slot from its target's row length
+            csr, w_t, deg_rowptr = graph.bwd, None, (graph.fwd.rowptr if mean else None)
+        else:             # the relation-expanded transposed CSR the RGCN select form builds: shared, not built twice
+            _, csr, w_bwd = view.select
+            w_t, deg_rowptr = (w_bwd if mean else None), None
+        g_h = torch.empty((N * R, C), dtype=torch.float32, device=dev)  # every row is written (no out-edge: zeros)
+        pgh, ldgh = _lib.mat(g_h, "g_h")
+        split_ref, _, _scratch = _attn_split(csr, C, dev)
+        with _Timed("film_bwd_src"):
+            _lib.check(lib.rgbx_film_bwd_src_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w_t),
+                                                 _lib.ptr(deg_rowptr), ph, ldh, pf, ldf, gofs, pg, ldg, pgh, ldgh, N, R, C,
+                                                 int(act), split_ref, _lib.stream_ptr()), "rgbx_film_bwd_src_f32")
+    if want_fb:
+        csr = graph.fwd if view is None else view.expand_fwd
+        # the kernel writes the two blocks of every row; columns between them (a column block of a wider fb) stay zero
+        alloc = torch.empty if gofs == C else torch.zeros
+        g_fb = alloc((N * R, gofs + C), dtype=torch.float32, device=dev)
+        pgf, ldgf = _lib.mat(g_fb, "g_fb")
+        split_ref, _, _scratch2 = _attn_split(csr, 2 * C, dev)
+        with _Timed("film_bwd_film"):
+            _lib.check(lib.rgbx_film_bwd_film_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), ph, ldh, pf, ldf, gofs, pg, ldg,
+                                                  pgf, ldgf, N, R, C, int(mean), int(act), split_ref, _lib.stream_ptr()),
+                       "rgbx_film_bwd_film_f32")
+    return g_h, g_fb
+
+
+class _FiLMAggregate(torch.autograd.Function):
+    """FiLMConv's aggregation as one autograd node: out = y0 + sum_p w[p] act(gamma[i, r] h[j, r] + beta[i, r]) in
+    rgbx_film_fwd_f32; backward = the source pass over the (relation-expanded) transposed CSR (g_h, only when h asks),
+    the film pass over the (relation-expanded) forward CSR (g_fb, only when fb asks), g_y0 = gout. Saves h and fb and
+    nothing per edge: both passes recompute the mask from the forward's own fmaf."""
+
+    @staticmethod
+    def forward(ctx, hv, fv, y0, graph, view, mean, act, gofs):
+        _lib.require_device(hv, fv, y0)
+        vec = _head_vec(hv.size(1))
+        # column blocks of wider matrices stay views, where the row still fits a wave at the vector width they allow
+        hv, fv = _rows_on_grid(hv, vec), _rows_on_grid(fv, vec)
+        y = None if y0 is None else _rows_on_grid(y0, vec)
+        out = film_fwd_raw(hv, fv, gofs, graph, view, mean, act, y)
+        ctx.args = (graph, view, mean, act, gofs)
+        ctx.save_for_backward(hv, fv)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        hv, fv = ctx.saved_tensors
+        graph, view, mean, act, gofs = ctx.args
+        need = ctx.needs_input_grad
+        g_h = g_fb = None
+        if need[0] or need[1]:
+            g = _rows_on_grid(gout.contiguous(), _head_vec(hv.size(1)))
+            g_h, g_fb = film_bwd_raw(hv, fv, gofs, g, graph, view, mean, act, want_h=need[0], want_fb=need[1])
+        return g_h, g_fb, (gout if need[2] else None), None, None, None, None, None
+
+
+def film_aggregate(h, fb, graph, edge_type=None, num_relations=1, aggr="mean", act="relu", y0=None):
+    """FiLMConv's aggregation over a LOOPS_KEEP graph (the edges as given: duplicates count twice, self-loops are ordinary
+    edges), with R = num_relations and C channels:
+      h  [N, R * C]  = x @ [W_0 | ... | W_{R-1}]           (column block r: the message rows under relation r)
+      fb [N, R * 2C] = [film_0(x) | ... | film_{R-1}(x)]   (column block r: beta_r | gamma_r, beta FIRST)
+      out_i = y0_i + sum_r AGG_{j : (j -> i) of relation r} act(gamma_r[i] * h_r[j] + beta_r[i])
+    `edge_type` int64 [E] with values in [0, R), one relation per INPUT edge; None is the single-relation call (R must
+    be 1: no typed view is built, the mean weights come from the row lengths). `aggr` "mean" is the mean per (target,
+    relation), "add" / "sum" the sum; a (target, relation) pair without an edge contributes 0. `act`: "relu", or
+    "identity" / None. `y0` [N, C] (optional) is the dense skip term, added in the kernel so that the output is written
+    once. IT MATERIALISES N * R * 3C FLOATS (h and fb), and as many again for their gradients; N * R >= 2^31 is refused
+    before any launch. One autograd node: g_h through the source pass, g_fb through the film pass, g_y0 = gout, each only
+    when asked for; h and fb are saved and nothing per edge. The op is per channel: a width above 256 runs as column
+    blocks of 256, which is exact. No float atomics: two runs are bit-identical. Timing names: film_fwd, film_bwd_src,
+    film_bwd_film."""
+    from .graph import LOOPS_KEEP
+    if _is_dist(graph):
+        raise RuntimeError("FiLMConv has no node-partitioned form: run it on one GPU")
+    if aggr not in _FILM_AGGRS:
+        raise ValueError(f"film_aggregate: aggr={aggr!r} (mean, add or sum)")
+    if not (act is None or isinstance(act, str)) or act not in _FILM_ACTS:
+        raise ValueError(f"film_aggregate: act={act!r} (relu, identity or None)")
+    if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
+        raise RuntimeError("film_aggregate: only a graph in mode LOOPS_KEEP takes the edges as given "
+                           f"(got loops_mode={getattr(graph, 'loops_mode', None)!r})")
+    mean, act = int(_FILM_AGGRS[aggr] == "mean"), _FILM_ACTS[act]
+    R = int(num_relations)
+    if R <= 0:
+        raise ValueError(f"film_aggregate: num_relations must be positive, got {num_relations}")
+    if edge_type is None and R != 1:
+        raise ValueError(f"film_aggregate: edge_type must be int64 [E] for num_relations={R}, got None")
+    N = graph.fwd.N
+    if h.dim() != 2 or h.size(0) != N or h.size(1) % R or h.size(1) == 0 or h.dtype != torch.float32:
+        raise RuntimeError(f"film_aggregate: h {h.dtype} {tuple(h.shape)} for a graph of {N} nodes and {R} relations "
+                           f"(float32 [N, {R} * C])")
+    C = h.size(1) // R
+    if tuple(fb.shape) != (N, 2 * R * C) or fb.dtype != torch.float32:
+        raise RuntimeError(f"film_aggregate: fb {fb.dtype} {tuple(fb.shape)} (float32 [N, R * 2C] = [{N}, {2 * R * C}])")
+    if y0 is not None and (tuple(y0.shape) != (N, C) or y0.dtype != torch.float32):
+        raise RuntimeError(f"film_aggregate: y0 {y0.dtype} {tuple(y0.shape)} (float32 [N, C] = [{N}, {C}])")
+    if N * R >= 2 ** 31:
+        raise RuntimeError(f"film_aggregate: the operands hold N * R = {N} * {R} rows, beyond int32")
+    _lib.require_device(h, fb, y0)
+    blocked = C > FILM_BLOCK and film_supported(C % FILM_BLOCK or FILM_BLOCK)
+    if not blocked and not film_supported(C):
+        raise RuntimeError(f"film_aggregate: h {tuple(h.shape)} with {R} relations: the kernels take any C <= 64, even "
+                           "C <= 128 or C % 4 == 0 up to 256 (and blocks of 256 above); pad the width (FiLMConv does)")
+    view = None if edge_type is None else typed_view(graph, edge_type, R)
+    # one relation: column blocks of wider matrices are taken as they are; several: the [N * R, .] views need whole rows
+    hv = h if R == 1 else h.contiguous().view(N * R, C)
+    fv = fb if R == 1 else fb.contiguous().view(N * R, 2 * C)
+    if not blocked:
+        return _FiLMAggregate.apply(hv, fv, y0, graph, view, mean, act, C)
+    outs = []
+    for a in range(0, C, FILM_BLOCK):
+        b = min(a + FILM_BLOCK, C)
+        if C % 4 == 0:   # beta's block to gamma's block as ONE view: gamma sits the full width behind beta
+            fblk, gofs = fv[:, a:C + b], C
+        else:            # the vector width of a 256-wide block needs gamma on its grid: the two blocks side by side
+            fblk, gofs = torch.cat([fv[:, a:b], fv[:, C + a:C + b]], dim=1), b - a
+        outs.append(_FiLMAggregate.apply(hv[:, a:b], fblk, None if y0 is None else y0[:, a:b], graph, view, mean, act,
+                                         gofs))
+    return torch.cat(outs, dim=1)
 
 
 class _GMMAggregate(torch.autograd.Function):
