@@ -35,6 +35,7 @@
  *   rgbx_resgated_*       ResGatedGraphConv (per-channel sigmoid gate) [PyG]; not in the reference's zoo.
  *   rgbx_gine_*           GINEConv (GIN with a feature row per edge: relu(x_j + e_ji) summed) [PyG]; the zoo's
  *                         models/gin.py is its sibling without edge features.
+ *   rgbx_cgconv_*         CGConv (gated softplus message over [x_i, x_j, e_ij]) [PyG]; not in the reference's zoo.
  *   rgbx_pna_*            PNAConv (statistics of a per-edge message, scaled by functions of the in-degree) [PyG]; not in
  *                         the reference's zoo.
  *   rgbx_rgcn_*           RGCNConv (a relation per edge: mean per (target, relation), basis decomposition) [PyG]; not
@@ -1055,6 +1056,56 @@ int rgbx_gine_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const i
                           int64_t ldx, const float* e, int64_t lde, const float* gout, int64_t ldg, const float* eps,
                           float* g_x, int64_t ldgx, int64_t N, int C, const rgbx_row_split_t* split,
                           rgbx_stream_t stream);
+
+/* ---- CGConv: sigmoid(lin_f(z)) * softplus(lin_s(z)) over the in-edges, z = [x_i, x_j, e_ij] ----------------------- */
+
+/* CGConv.message [PyG] forms `z = torch.cat([x_i, x_j, edge_attr], dim=-1)` per edge and returns
+ * `self.lin_f(z).sigmoid() * F.softplus(self.lin_s(z))` (Xie & Grossman, "Crystal Graph Convolutional Neural Networks
+ * for an Accurate and Interpretable Prediction of Material Properties"). The reference's zoo has no such layer. A
+ * Linear over a concatenation is a sum of three Linears, so the dense products come first. For an edge j -> i (p = its
+ * slot in the target-grouped CSR), with a, b [N, 2C] and c [nnz, 2C] — ONE ROW PER SLOT, in forward CSR slot order; every
+ * row is (f half | s half); each operand its own pointer and leading dimension >= 2C (column blocks of a wider matrix
+ * are taken as they are); c == NULL: no edge term —
+ *   zf = a[i,:C] + b[j,:C] + c[p,:C]         zs = a[i,C:] + b[j,C:] + c[p,C:]
+ *   msg_p    = sigmoid(zf) (.) softplus(zs)                          (a vector per edge: one gate per channel)
+ *   out[i,:] = root[i,:] + scale_i * sum_p msg_p                     scale_i = 1, or with mean != 0  1.0f / (float)deg_i
+ * with deg_i read from rowptr inside the kernels, never by the host (0 for a row without slots). Both branches go
+ * through e = exp(-|z|): sigmoid = (z >= 0 ? 1 : e) / (1 + e), softplus = max(z, 0) + log1p(e), so no intermediate
+ * overflows for any z and a saturated gate is exactly 0 or 1; exp, log and the reciprocal are the hardware instructions
+ * (about 1 ulp each) and log1p(e) is log(1 + e): an absolute error of at most 2^-24 per slot in softplus. Nothing is saved for the backward: its two passes
+ * recompute both branches from a, b, c and are independent of each other. The edges are taken as they are
+ * (RGBX_LOOPS_KEEP): a row WITHOUT slots stores the root term alone (exact zeros without one) and a zero g_a row; a
+ * source without out-edges gets a zero g_b row. Every output row is written, every slot row of g_c too. No entry point
+ * uses float atomics, scratch or LDS; every sum runs in a fixed order: two runs are bit-identical. */
+
+/* 1 if the kernels take C channels (the widths of rgbx_resgated_supported), else 0. */
+int rgbx_cgconv_supported(int C);
+
+/* Forward over the target-grouped CSR, out [N, C]: the target's a row stays in registers, b rows are gathered, the c
+ * rows of a target read as a stream. `root` [N, C] is optional (NULL: none). `split`: hub rows as in rgbx_gatv2_fwd_f32;
+ * split->partial holds n_chunks * C floats, added in chunk order (the root term rides on the row's first chunk). */
+int rgbx_cgconv_fwd_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t lda, const float* b,
+                        int64_t ldb, const float* c, int64_t ldc, const float* root, int64_t ldr, float* out,
+                        int64_t ldo, int64_t N, int C, int mean, const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward, target side, over the forward CSR. With s = sigmoid(zf), t = softplus(zs), u = sigmoid(zs):
+ *   gf_p = scale_i * gout[i,:] (.) s (1 - s) t       gs_p = scale_i * gout[i,:] (.) s u
+ *   g_a[i,:] = (sum_p gf_p | sum_p gs_p)  [N, 2C]     g_c[p,:] = (gf_p | gs_p)  [nnz, 2C], one row per slot
+ * Each output is optional (NULL: not wanted; both NULL: RGBX_E_ARG); g_c does not need c. split->partial holds
+ * n_chunks * 2C floats (a chunk's record is the two sums); every slot's g_c row is written exactly once. */
+int rgbx_cgconv_bwd_dst_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t lda, const float* b,
+                            int64_t ldb, const float* c, int64_t ldc, const float* gout, int64_t ldg, float* g_a,
+                            int64_t ldga, float* g_c, int64_t ldgc, int64_t N, int C, int mean,
+                            const rgbx_row_split_t* split, rgbx_stream_t stream);
+
+/* Backward, source side, over the TRANSPOSED CSR (rows = sources j, col_t = targets i), in any order with the target
+ * side:   g_b[j,:] = (sum_q gf_q | sum_q gs_q)  [N, 2C].
+ * `t2f` [nnz] = the forward slot of every transposed slot (needed with c), `rowptr_f` [N + 1] = the forward rowptr
+ * (needed with mean != 0: the targets' degrees). split->partial holds n_chunks * 2C floats. */
+int rgbx_cgconv_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* t2f, const int32_t* rowptr_f,
+                            const float* a, int64_t lda, const float* b, int64_t ldb, const float* c, int64_t ldc,
+                            const float* gout, int64_t ldg, float* g_b, int64_t ldgb, int64_t N, int C, int mean,
+                            const rgbx_row_split_t* split, rgbx_stream_t stream);
 
 /* ---- RGCNConv: a relation per edge; mean per (target, relation), basis decomposition ------------------------------- */
 

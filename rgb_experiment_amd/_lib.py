@@ -171,6 +171,11 @@ SIGNATURES = {
     "rgbx_gine_fwd_f32": [_P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I, _P, _P],
     "rgbx_gine_bwd_edge_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P],
     "rgbx_gine_bwd_src_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I, _P, _P],
+    "rgbx_cgconv_supported": [_I],
+    "rgbx_cgconv_fwd_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _P, _P],
+    "rgbx_cgconv_bwd_dst_f32": [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _P,
+                                _P],
+    "rgbx_cgconv_bwd_src_f32": [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _P, _P],
     "rgbx_rgcn_slot_norm_f32": [_P, _P, _P, _I64, _I, _P, _P],
     "rgbx_rgcn_mix_supported": [_I, _I],
     "rgbx_rgcn_mix_fwd_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _I, _I, _P, _P],

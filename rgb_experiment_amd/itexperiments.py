@@ -276,7 +276,9 @@ def experiment(model_init_param: dict, *,
     forward arguments as ``edge_attr``, for ``model_name="gine"`` (models.GINE, built with ``edge_dim`` in
     ``model_init_param``), for ``model_name="monet"`` (models.MoNet, built with ``kernel_size`` and ``dim`` = D; without the
     flag it runs on the degree pseudo-coordinates of the graph), for ``model_name="pna"`` (models.PNA, built with ``edge_dim``
-    = D; without the flag, and with ``edge_dim`` left out, it runs on the node features alone) and for a caller's ``model=`` whose forward takes
+    = D; without the flag, and with ``edge_dim`` left out, it runs on the node features alone), for ``model_name="cgcnn"``
+    (models.CGCNN, built with ``edge_dim`` = D; without the flag, and with ``edge_dim`` = 0, it runs on the node features
+    alone) and for a caller's ``model=`` whose forward takes
     ``edge_attr`` (any other model_name: ValueError). Not with ``to_undirected_graph`` (that call carries no attributes: ValueError) and not on the partitioned
     route (NotImplementedError). With the flag off a ``Data`` that happens to carry an ``edge_attr`` behaves exactly as
     one without (``gine`` then fails at its forward, which needs the argument). ``use_edge_type=True`` (an addition, off by
@@ -312,9 +314,9 @@ def experiment(model_init_param: dict, *,
         if model is not None:
             if not isinstance(model, nn.Module) or "edge_attr" not in inspect.signature(model.forward).parameters:
                 raise ValueError("use_edge_attr=True: the forward of the module passed as model= takes no edge_attr")
-        elif name not in ("gine", "monet", "pna"):
+        elif name not in ("gine", "monet", "pna", "cgcnn"):
             raise ValueError(f"use_edge_attr=True: model_name={model_name!r} takes no edge attributes; the routes that do "
-                             "are gine, monet, pna and a model= whose forward takes edge_attr")
+                             "are gine, monet, pna, cgcnn and a model= whose forward takes edge_attr")
         if to_undirected_graph:
             raise ValueError("use_edge_attr=True cannot be combined with to_undirected_graph=True: the reference's "
                              "to_undirected call (:235-238) carries no attributes")

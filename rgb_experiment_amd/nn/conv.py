@@ -1650,6 +1650,79 @@ class ResGatedGraphConv(nn.Module):
         return out
 
 
+class CGConv(nn.Module):
+    """The crystal graph convolution [PyG CGConv; Xie & Grossman, "Crystal Graph Convolutional Neural Networks for an
+    Accurate and Interpretable Prediction of Material Properties"]: with z_ij = [x_i, x_j, e_ij] (e_ij absent when
+    dim = 0), out_i = x_i + bn(aggr_j sigmoid(lin_f(z_ij)) * softplus(lin_s(z_ij))), elementwise over the C channels,
+    over the in-edges of i, the edges AS GIVEN (self-loops stay, duplicates count twice, a node without in-edges
+    aggregates zeros, so it gets bn(0) + x_i). `edge_attr` [E, dim] holds one row per input edge. Parameter names are
+    PyG's: lin_f, lin_s = Linear(2C + dim, C, bias=bias), bn (BatchNorm1d(C)) only with batch_norm.
+
+    A Linear over a concatenation is a sum of three: the target and source terms of both maps are the column blocks of
+    ONE product over x, the edge terms ONE product over the attribute rows, permuted into CSR slot order once at their
+    raw width (ops.edge_rows_to_slots); gate, softplus, sum or mean and, without batch_norm, the root term x_i run in
+    the rgbx_cgconv_* kernels (ops.cgconv_aggregate). A width outside the kernels' set is padded with zero weight rows
+    and sliced off again.
+
+    Out of scope: aggr="max" (the kernels form sums), bipartite `channels`, the node-partitioned (distributed) route,
+    edge attributes through to_undirected / coalesce."""
+
+    def __init__(self, channels, dim=0, aggr="add", batch_norm=False, bias=True):
+        super().__init__()
+        if isinstance(channels, (tuple, list)):
+            raise NotImplementedError("CGConv: bipartite channels (a pair of widths) are not built")
+        if aggr not in ("add", "mean"):
+            raise NotImplementedError(f"CGConv: aggr={aggr!r} is not built (the kernels form sums: 'add' or 'mean')")
+        self.channels, self.dim, self.aggr, self.batch_norm = int(channels), int(dim), aggr, batch_norm
+        self.lin_f = Linear(2 * self.channels + self.dim, self.channels, bias=bias)
+        self.lin_s = Linear(2 * self.channels + self.dim, self.channels, bias=bias)
+        self.bn = BatchNorm1d(self.channels) if batch_norm else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.lin_f.reset_parameters()
+        self.lin_s.reset_parameters()
+        if self.bn is not None:
+            self.bn.reset_parameters()
+
+    def forward(self, x, edge_index, edge_attr=None):
+        C, D = self.channels, self.dim
+        if x.dim() != 2 or x.size(1) != C:
+            raise ValueError(f"CGConv: x must be [N, {C}], got {tuple(x.shape)}")
+        if D == 0 and edge_attr is not None:
+            raise ValueError("CGConv: built with dim=0, it takes no edge_attr")
+        if D > 0 and (not torch.is_tensor(edge_attr) or edge_attr.dim() != 2 or edge_attr.size(1) != D
+                      or edge_attr.size(0) != edge_index.size(1) or not edge_attr.is_floating_point()):
+            got = tuple(edge_attr.shape) if torch.is_tensor(edge_attr) else type(edge_attr).__name__
+            raise ValueError(f"CGConv: edge_attr must be float [E, dim] = [{edge_index.size(1)}, {D}], got {got}")
+        _lib.require_device(x, edge_attr)
+        Cp = GATConv.kernel_channels(C)
+        graph = get_graph(edge_index, x.size(0), LOOPS_KEEP)
+        pad = torch.nn.functional.pad
+        rows = (lambda w: w) if Cp == C else (lambda w: pad(w, (0, 0, 0, Cp - C)))
+        wf, ws = self.lin_f.weight, self.lin_s.weight
+        # One product over [W_f^i; W_s^i; W_f^j; W_s^j]: a = its first 2 Cp columns (f half | s half, with the biases),
+        # b the other 2 Cp. A padded channel has zf = zs = 0, so its message is sigmoid(0) softplus(0) = 0.5 ln 2, NOT
+        # zero: it is harmless only because it is sliced off here and its gout is therefore zero.
+        w_ab = torch.cat([rows(wf[:, :C]), rows(ws[:, :C]), rows(wf[:, C:2 * C]), rows(ws[:, C:2 * C])])
+        b_ab = None
+        if self.lin_f.bias is not None:
+            vec = (lambda v: v) if Cp == C else (lambda v: pad(v, (0, Cp - C)))
+            b_ab = torch.cat([vec(self.lin_f.bias), vec(self.lin_s.bias), x.new_zeros(2 * Cp)])
+        h = ops.linear(x, w_ab, b_ab)
+        c = None
+        if D > 0 and edge_index.size(1) > 0:  # (no slot, no product)
+            ea = ops.edge_rows_to_slots(edge_attr.to(torch.float32), graph)
+            c = ops.linear(ea, torch.cat([rows(wf[:, 2 * C:]), rows(ws[:, 2 * C:])]))
+        fused_root = self.bn is None and Cp == C
+        out = ops.cgconv_aggregate(h[:, :2 * Cp], h[:, 2 * Cp:], c, graph, Cp, self.aggr, root=x if fused_root else None)
+        if fused_root:
+            return out
+        if Cp != C:
+            out = out[:, :C]
+        return (out if self.bn is None else self.bn(out)) + x
+
+
 class GENConv(nn.Module):
     """DeeperGCN's generalised graph convolution with the softmax aggregator [PyG GENConv(aggr="softmax"); Li et al.,
     "DeeperGCN: All You Need to Train Deeper GCNs"]: with xs = lin_src(x) and xd = lin_dst(x) (both layers exist only

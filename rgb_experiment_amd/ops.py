@@ -3171,6 +3171,118 @@ def gine_aggregate(x, e_slot, graph, eps=None):
     return _GINEAggregate.apply(x, e_slot, eps, graph)
 
 
+# ---- CGConv: sigmoid(lin_f(z)) * softplus(lin_s(z)) with z = [x_i, x_j, e_ij], as three linear terms -----------------
+
+class _CGConvAggregate(torch.autograd.Function):
+    """One CGConv aggregation as a single autograd node: fused message sigmoid(zf) * softplus(zs) with
+    z = a_i + b_j + c_p, sum or mean over the in-edges and root term; backward = target-side pass (g_a and, from the same
+    registers, g_c, one row per slot) and source-side pass (g_b), independent of each other and run only where a gradient
+    is asked for; g_root = gout. Saves a, b, c and nothing else (of root only whether it was there): both passes recompute
+    both branches. The mean's 1 / deg is read from rowptr inside the kernels, so a captured launch stays valid."""
+
+    @staticmethod
+    def forward(ctx, a, b, c_slot, root, graph, C, mean):
+        _lib.require_device(a, b, c_slot, root)
+        lib = _lib.load()
+        # column blocks of one product stay views, where the row still fits a wave at the vector width they allow
+        vec = _head_vec(C)
+        a, b = (_rows_on_grid(t, vec) for t in (a, b))
+        csr, N, dev = graph.fwd, graph.fwd.N, a.device
+        c = None
+        if c_slot is not None and csr.nnz:  # (no slot: no c row is ever read, the call runs without the edge term)
+            c = _rows_on_grid(c_slot, vec)
+        rt = None if root is None else _rows_on_grid(root, vec)
+        out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: the root)
+        pa, lda = _lib.mat(a, "a")
+        pb, ldb = _lib.mat(b, "b")
+        pc, ldc = (0, 0) if c is None else _lib.mat(c, "c_slot")
+        pr, ldr = (0, 0) if rt is None else _lib.mat(rt, "root")
+        po, ldo = _lib.mat(out, "out")
+        split_ref, _, _scratch = _attn_split(csr, C, dev)
+        with _Timed("cgconv_fwd"):
+            _lib.check(lib.rgbx_cgconv_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pa, lda, pb, ldb, pc, ldc, pr, ldr,
+                                               po, ldo, N, C, int(mean), split_ref, _lib.stream_ptr()),
+                       "rgbx_cgconv_fwd_f32")
+        ctx.graph, ctx.C, ctx.mean = graph, C, mean
+        ctx.c_shape = None if c_slot is None else tuple(c_slot.shape)
+        ctx.save_for_backward(a, b, c)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b, c = ctx.saved_tensors
+        g = ctx.graph
+        lib = _lib.load()
+        N, C, dev, mean = g.fwd.N, ctx.C, a.device, int(ctx.mean)
+        need = ctx.needs_input_grad
+        gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
+        pa, lda = _lib.mat(a, "a")
+        pb, ldb = _lib.mat(b, "b")
+        pc, ldc = (0, 0) if c is None else _lib.mat(c, "c_slot")
+        pg, ldg = _lib.mat(gout, "gout")
+        g_a = g_b = g_c = None
+        want_c = need[2] and ctx.c_shape is not None
+        if want_c:
+            g_c = torch.empty(ctx.c_shape, dtype=torch.float32, device=dev)  # every slot row is written
+        if need[0] or (want_c and g.fwd.nnz):  # one pass forms both from the same registers
+            if need[0]:
+                g_a = torch.empty((N, 2 * C), dtype=torch.float32, device=dev)  # every row is written
+            pga, ldga = (0, 0) if g_a is None else _lib.mat(g_a, "g_a")
+            pgc, ldgc = (0, 0) if not (want_c and g.fwd.nnz) else _lib.mat(g_c, "g_c")
+            split_ref, _, _scratch = _attn_split(g.fwd, 2 * C, dev)
+            with _Timed("cgconv_bwd_dst"):
+                _lib.check(
+                    lib.rgbx_cgconv_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pa, lda, pb, ldb, pc, ldc, pg,
+                                                ldg, pga, ldga, pgc, ldgc, N, C, mean, split_ref, _lib.stream_ptr()),
+                    "rgbx_cgconv_bwd_dst_f32")
+        if need[1]:
+            g_b = torch.empty((N, 2 * C), dtype=torch.float32, device=dev)  # every row is written
+            pgb, ldgb = _lib.mat(g_b, "g_b")
+            split_ref, _, _scratch2 = _attn_split(g.bwd, 2 * C, dev)
+            with _Timed("cgconv_bwd_src"):
+                _lib.check(
+                    lib.rgbx_cgconv_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(g.t2f),
+                                                _lib.ptr(g.fwd.rowptr), pa, lda, pb, ldb, pc, ldc, pg, ldg, pgb, ldgb, N,
+                                                C, mean, split_ref, _lib.stream_ptr()), "rgbx_cgconv_bwd_src_f32")
+        return g_a, g_b, g_c, gout if need[3] else None, None, None, None
+
+
+def cgconv_supported(C):
+    return bool(_lib.load().rgbx_cgconv_supported(C))
+
+
+def cgconv_aggregate(a, b, c_slot, graph, C, aggr="add", root=None):
+    """One CGConv aggregation on a, b [N, 2C] and c_slot [nnz, 2C] or None, every row (f half | s half); c_slot has one
+    row per forward CSR slot (edge_rows_to_slots gives the order). Rows contiguous; column blocks of one wider matrix are
+    taken as they are. With zf = a_f[i] + b_f[j] + c_f[p] and zs likewise:
+    out_i = root_i + aggr_p sigmoid(zf) * softplus(zs), elementwise over the C channels, over the in-edges of i, the graph
+    in mode LOOPS_KEEP (edges as given: self-loops stay, duplicates count twice, a node without in-edges gets the root
+    term alone). aggr: "add" or "mean" (the division by the in-edge count). root [N, C] or None. No dropout, no random
+    state."""
+    from .graph import LOOPS_KEEP
+    if _is_dist(graph):
+        raise RuntimeError("CGConv has no node-partitioned form: run it on one GPU")
+    _lib.require_device(a, b, c_slot, root)
+    if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
+        raise RuntimeError("cgconv_aggregate: the graph must be in mode LOOPS_KEEP (edges as given; got "
+                           f"loops_mode={getattr(graph, 'loops_mode', None)!r})")
+    if aggr not in ("add", "mean"):
+        raise NotImplementedError(f"cgconv_aggregate: aggr={aggr!r} (the kernels form sums: 'add' or 'mean')")
+    N, nnz = graph.fwd.N, graph.fwd.nnz
+    C = int(C)
+    if (a.dim() != 2 or b.dim() != 2 or tuple(a.shape) != (N, 2 * C) or tuple(b.shape) != (N, 2 * C)
+            or (c_slot is not None and tuple(c_slot.shape) != (nnz, 2 * C))
+            or (root is not None and tuple(root.shape) != (N, C))):
+        raise RuntimeError(f"cgconv_aggregate: a {tuple(a.shape)} / b {tuple(b.shape)} / c_slot "
+                           f"{None if c_slot is None else tuple(c_slot.shape)} / root "
+                           f"{None if root is None else tuple(root.shape)} for a graph of {N} nodes and {nnz} slots at "
+                           f"C = {C} (a, b [N, 2C], c_slot [nnz, 2C], root [N, C])")
+    if not cgconv_supported(C):
+        raise RuntimeError(f"cgconv_aggregate: C = {C}: the kernels take any C <= 64, even C <= 128 or C % 4 == 0 up to "
+                           "256; pad the width (CGConv does)")
+    return _CGConvAggregate.apply(a, b, c_slot, root, graph, C, aggr == "mean")
+
+
 # ---- PNAConv: the statistics of a per-edge message, scaled by functions of the in-degree -------------------------------
 
 PNA_SCALERS = {"identity": 0, "amplification": 1, "attenuation": 2, "linear": 3, "inverse_linear": 4}  # RGBX_PNA_*
