@@ -840,9 +840,13 @@ def spmm_bf16_raw(csr, w, rs, xb, y=None, a=1.0, b=0.0, bias=None, out=None, out
     elif out.dtype != out_dtype or tuple(out.shape) != (N, d):
         raise RuntimeError(f"spmm_bf16_raw: out is {out.dtype} {tuple(out.shape)}, expected {out_dtype} {(N, d)}")
     po, ldo = _lib.mat(out, "out") if out_dtype == torch.float32 else _lib.mat_bf16(out, "out")
+    # the kernel reads y and bias four floats at a time: an addend half behind an offset view, a bias sliced out of a flat
+    # parameter buffer are copied onto that grid (the sums are read from the copy, `out` may still alias the original)
+    y = None if y is None else _rows_on_grid(y)
     py, ldy = (0, 0) if y is None else _lib.mat(y, "y")
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != d):
         raise RuntimeError(f"spmm_bf16_raw: bias must be float32 [{d}]")
+    bias = _vec_on_grid(bias, d)
     pb = _lib.ptr(bias)
     lib = _lib.load()
     for c0 in range(0, max(d, 1), BF16_MAX_WIDTH):
@@ -3472,6 +3476,10 @@ class _PNAAggregate(torch.autograd.Function):
             B = t if B is None else B + t
         b_k = b
         if B is not None:
+            # a row of one slot has u_p = mean_u exactly: var and std are constant there and B contributes nothing. Left in,
+            # B u_p - B mean_u cancels at the size of B, which is largest exactly there (2 / n, times lin / 1 under
+            # inverse_linear): 5e-4 off a gradient that is 0
+            B = torch.where(deg > 1, B, zero)
             # B (u_p - mean_u) as B u_p - B mean_u cancels on messages with an offset: both halves are taken relative to
             # the column mean s of mean_u (the same number), so the kernels' b is b - s
             s = mean_u.mean(0, keepdim=True)

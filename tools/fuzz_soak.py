@@ -6,7 +6,9 @@ Usage: python tools/fuzz_soak.py first last            (conv layers: run_case)
        python tools/fuzz_soak.py --fused first last    (rgbx_fused_layer_f32 by option: run_fused_layer_case)
        python tools/fuzz_soak.py --ref64 seed [seed ...]   (the listed seeds against the oracle computing in float64)
        python tools/fuzz_soak.py --families first last [--kind NAME]   (tests/test_gpu_fuzz_families.py: run_family_case;
-                                  with --kind every seed runs that kind, else a seed's kind is seed % 8; a HIP error ends the run)"""
+                                  with --kind every seed runs that kind, else a seed's kind is seed % 8; a HIP error ends the run)
+       python tools/fuzz_soak.py --edge-families first last [--kind NAME]   (tests/test_gpu_fuzz_edge_families.py:
+                                  run_edge_family_case; --kind and a HIP error as for --families, a seed's kind is seed % 9)"""
 import os
 import sys
 import time
@@ -17,6 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 
 import test_gpu_fuzz as F
+import test_gpu_fuzz_edge_families as EF
 import test_gpu_fuzz_families as FF
 from conftest import usable_cpus
 
@@ -50,21 +53,25 @@ def main():
     if "--kind" in sys.argv:
         at = sys.argv.index("--kind")
         family = sys.argv[at + 1]
-        if which != "--families" or family not in FF.KINDS:
-            sys.exit(f"--kind goes with --families and names one of {FF.KINDS}")
+        names = {"--families": FF.KINDS, "--edge-families": EF.KINDS}.get(which)
+        if names is None or family not in names:
+            sys.exit(f"--kind goes with --families ({FF.KINDS}) or --edge-families ({EF.KINDS}) and names one of its kinds")
         del sys.argv[at:at + 2]
     run, kinds = {"--models": (F.run_model_case, F.MODEL_KINDS), "--fused": (F.run_fused_layer_case, ["fused_layer"]),
                   "--families": (lambda d, seed: FF.run_family_case(d, seed, family), [family] if family else FF.KINDS),
+                  "--edge-families": (lambda d, seed: EF.run_edge_family_case(d, seed, family),
+                                      [family] if family else EF.KINDS),
                   "": (F.run_case, F.KINDS)}[which]
+    by_family = which in ("--families", "--edge-families")
     first, last = int(sys.argv[1]), int(sys.argv[2])
     bad, t0, mark = [], time.time(), time.time()
     for seed in range(first, last):
         try:
             run(dev, seed)
         except Exception as exc:  # noqa: BLE001 - collected, reported below
-            bad.append((seed, kinds[seed % len(kinds)], repr(exc)[:300 if which != "--families" else 1200]))
+            bad.append((seed, kinds[seed % len(kinds)], repr(exc)[:1200 if by_family else 300]))
             print("FAIL", bad[-1], flush=True)
-            if which == "--families" and is_hip_error(exc):  # the device is in an unknown state: nothing more runs on it
+            if by_family and is_hip_error(exc):  # the device is in an unknown state: nothing more runs on it
                 print(f"soak [{first}, {seed}]: ended by a HIP error after {seed - first + 1} cases, {len(bad)} failures", flush=True)
                 return 2
         if time.time() - mark > 30:
