@@ -298,10 +298,10 @@ def ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
-def mat(t, name="tensor"):
-    """Row-major fp32 matrix -> (pointer, leading dimension in elements)."""
-    if t.dtype != torch.float32 or t.dim() != 2:
-        raise RuntimeError(f"{name}: expected a 2-D float32 tensor, got {t.dtype} {tuple(t.shape)}")
+def mat(t, name="tensor", dtype=torch.float32):
+    """Row-major matrix (fp32 unless `dtype` says otherwise) -> (pointer, leading dimension in elements)."""
+    if t.dtype != dtype or t.dim() != 2:
+        raise RuntimeError(f"{name}: expected a 2-D {str(dtype)[6:]} tensor, got {t.dtype} {tuple(t.shape)}")
     if t.size(1) > 1 and t.stride(1) != 1:
         raise RuntimeError(f"{name}: rows must be contiguous (stride {t.stride()})")
     ld = t.stride(0) if t.size(0) > 1 else max(t.size(1), 1)
@@ -309,10 +309,60 @@ def mat(t, name="tensor"):
 
 
 def mat_bf16(t, name="tensor"):
-    """Row-major bfloat16 matrix -> (pointer, leading dimension in elements); `mat` stays fp32-only."""
-    if t.dtype != torch.bfloat16 or t.dim() != 2:
-        raise RuntimeError(f"{name}: expected a 2-D bfloat16 tensor, got {t.dtype} {tuple(t.shape)}")
-    if t.size(1) > 1 and t.stride(1) != 1:
-        raise RuntimeError(f"{name}: rows must be contiguous (stride {t.stride()})")
-    ld = t.stride(0) if t.size(0) > 1 else max(t.size(1), 1)
-    return t.data_ptr(), ld
+    """Row-major bfloat16 matrix -> (pointer, leading dimension in elements); `mat` stays fp32-only by default."""
+    return mat(t, name, torch.bfloat16)
+
+
+def mat_opt(t, name="tensor"):
+    """`mat` of an optional operand: None -> (null, 0). `mat(None)` itself keeps raising."""
+    return (0, 0) if t is None else mat(t, name)
+
+
+def marshal(args, _tensor=torch.Tensor, _struct=ctypes.Structure, _byref=ctypes.byref):
+    """Arguments as the C ABI takes them: a tensor -> its data pointer, None -> null, a tuple (the (pointer, ld) pairs of
+    `mat`) -> its members in place, a ctypes.Structure -> a reference to it, bool -> int; everything else (int, float,
+    an explicit byref of an out-parameter) as it is. The caller keeps every tensor and structure alive over the call.
+    (Runs once per launch: the common types first, the globals bound as defaults.)"""
+    out = []
+    push = out.append
+    for a in args:
+        t = type(a)
+        if t is int or t is float:
+            push(a)
+        elif t is _tensor:
+            push(a.data_ptr())
+        elif t is tuple:
+            out += a
+        elif a is None:
+            push(0)
+        elif isinstance(a, _tensor):
+            push(a.data_ptr())
+        elif isinstance(a, _struct):
+            push(_byref(a))
+        elif t is bool:
+            push(int(a))
+        else:
+            push(a)
+    return out
+
+
+def call(name, *args):
+    """Call the entry point `name` with `args` marshalled (see `marshal`) and check its return code."""
+    rc = getattr(_lib or load(), name)(*marshal(args))
+    if rc:
+        check(rc, name)
+
+
+def launch(name, *args, bracket=None):
+    """`call` of a launching entry point: the current stream goes last. `bracket` (a context manager: ops._Timed) is
+    entered after the arguments are marshalled and left before the return code is checked, so it holds the call alone."""
+    fn = getattr(_lib or load(), name)
+    argv = marshal(args)
+    argv.append(stream_ptr())
+    if bracket is None:
+        rc = fn(*argv)
+    else:
+        with bracket:
+            rc = fn(*argv)
+    if rc:
+        check(rc, name)

@@ -81,22 +81,18 @@ def make_row_split(rowptr, threshold=None):
 def build_csr(agg_row, other_row, N, loops_mode):
     """int64 device vectors (aggregate-into index, gather-from index) -> CSR via the HIP library."""
     _lib.require_device(agg_row, other_row)
-    lib = _lib.load()
     E = agg_row.numel()
     dev = agg_row.device
     agg_row = agg_row.contiguous()
     other_row = other_row.contiguous()
     nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.rgbx_csr_workspace_bytes(E, N, ctypes.byref(nbytes)), "rgbx_csr_workspace_bytes")
+    _lib.call("rgbx_csr_workspace_bytes", E, N, ctypes.byref(nbytes))
     cap = max(E + N, 1)
     rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
     col = torch.empty(cap, dtype=torch.int32, device=dev)
     perm = torch.empty(cap, dtype=torch.int32, device=dev)
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-    _lib.check(
-        lib.rgbx_csr_build(_lib.ptr(agg_row), _lib.ptr(other_row), E, N, loops_mode, _lib.ptr(rowptr),
-                           _lib.ptr(col), _lib.ptr(perm), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-        "rgbx_csr_build")
+    _lib.launch("rgbx_csr_build", agg_row, other_row, E, N, loops_mode, rowptr, col, perm, ws, ws.numel())
     nnz = int(rowptr[N].item())  # one sync per graph; also orders `ws` lifetime after the kernels
     return CSR(rowptr, col[:max(nnz, 1)], perm[:max(nnz, 1)], N, nnz, make_row_split(rowptr))
 
@@ -135,15 +131,12 @@ class Graph:
     def dis(self):
         if self._dis is None:
             self._dis = self._f32(self.N)
-            _lib.check(_lib.load().rgbx_deg_inv_sqrt_f32(_lib.ptr(self.fwd.rowptr), self.N, _lib.ptr(self._dis),
-                                                         _lib.stream_ptr()), "rgbx_deg_inv_sqrt_f32")
+            _lib.launch("rgbx_deg_inv_sqrt_f32", self.fwd.rowptr, self.N, self._dis)
         return self._dis
 
     def _norm(self, csr):
         w = self._f32(csr.nnz)
-        _lib.check(_lib.load().rgbx_gcn_norm_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), self.N,
-                                                 _lib.ptr(self.dis), _lib.ptr(w), _lib.stream_ptr()),
-                   "rgbx_gcn_norm_f32")
+        _lib.launch("rgbx_gcn_norm_f32", csr.rowptr, csr.col, self.N, self.dis, w)
         return w
 
     @property
@@ -162,9 +155,7 @@ class Graph:
     def inv_deg(self):
         if self._inv_deg is None:
             self._inv_deg = self._f32(self.N)
-            _lib.check(_lib.load().rgbx_inv_degree_f32(_lib.ptr(self.fwd.rowptr), self.N,
-                                                       _lib.ptr(self._inv_deg), _lib.stream_ptr()),
-                       "rgbx_inv_degree_f32")
+            _lib.launch("rgbx_inv_degree_f32", self.fwd.rowptr, self.N, self._inv_deg)
         return self._inv_deg
 
     def rowsum(self, kind):
@@ -189,20 +180,17 @@ class Graph:
         input edge; rgbx_coalesce_keys_i64 with mirror = 1), built once: what the SuperGAT negative sampler searches."""
         cached = self.__dict__.get("_und_keys")
         if cached is None:
-            lib = _lib.load()
             dev = self.fwd.rowptr.device
             M = 2 * self.E
             keys = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
             count = 0
             if M:
                 nbytes = ctypes.c_size_t(0)
-                _lib.check(lib.rgbx_coalesce_workspace_bytes(self.E, self.N, 1, ctypes.byref(nbytes)),
-                           "rgbx_coalesce_workspace_bytes")
+                _lib.call("rgbx_coalesce_workspace_bytes", self.E, self.N, 1, ctypes.byref(nbytes))
                 counts = torch.empty(2, dtype=torch.int64, device=dev)
                 ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-                _lib.check(lib.rgbx_coalesce_keys_i64(_lib.ptr(self._src.contiguous()), _lib.ptr(self._dst.contiguous()),
-                                                      self.E, self.N, 1, _lib.ptr(keys), _lib.ptr(counts), _lib.ptr(ws),
-                                                      ws.numel(), _lib.stream_ptr()), "rgbx_coalesce_keys_i64")
+                _lib.launch("rgbx_coalesce_keys_i64", self._src.contiguous(), self._dst.contiguous(), self.E, self.N, 1,
+                            keys, counts, ws, ws.numel())
                 count = int(counts[0].item())  # one read-back per graph
             cached = self._und_keys = (keys, count)
         return cached
@@ -276,17 +264,14 @@ class WeightedGraph(Graph):
             else:
                 loop_w = self._f32(self.N)
                 loop_src = torch.empty(max(self.N, 1), dtype=torch.int32, device=loop_w.device)
-                _lib.check(_lib.load().rgbx_loop_weights_f32(
-                    _lib.ptr(self._src.contiguous()), _lib.ptr(self._dst.contiguous()), _lib.ptr(self.ew), self.E, self.N,
-                    self.loops_mode, 1.0, _lib.ptr(loop_w), _lib.ptr(loop_src), _lib.stream_ptr()), "rgbx_loop_weights_f32")
+                _lib.launch("rgbx_loop_weights_f32", self._src.contiguous(), self._dst.contiguous(), self.ew, self.E, self.N,
+                            self.loops_mode, 1.0, loop_w, loop_src)
                 self._loops = (loop_w, loop_src)
         return self._loops
 
     def _slot_weights(self, csr):
         out = self._f32(csr.nnz)
-        _lib.check(_lib.load().rgbx_edge_slot_weights_f32(_lib.ptr(csr.perm), csr.nnz, _lib.ptr(self.ew), self.E,
-                                                          _lib.ptr(self.loops[0]), _lib.ptr(out), _lib.stream_ptr()),
-                   "rgbx_edge_slot_weights_f32")
+        _lib.launch("rgbx_edge_slot_weights_f32", csr.perm, csr.nnz, self.ew, self.E, self.loops[0], out)
         return out
 
     @property
@@ -305,16 +290,12 @@ class WeightedGraph(Graph):
     def dis(self):
         if self._dis is None:
             self._dis = self._f32(self.N)
-            _lib.check(_lib.load().rgbx_weighted_deg_inv_sqrt_f32(_lib.ptr(self.fwd.rowptr), _lib.ptr(self.ew_slot), self.N,
-                                                                  _lib.ptr(self._dis), _lib.stream_ptr()),
-                       "rgbx_weighted_deg_inv_sqrt_f32")
+            _lib.launch("rgbx_weighted_deg_inv_sqrt_f32", self.fwd.rowptr, self.ew_slot, self.N, self._dis)
         return self._dis
 
     def _norm_weighted(self, csr, ew_slot):
         w = self._f32(csr.nnz)
-        _lib.check(_lib.load().rgbx_gcn_norm_weighted_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(ew_slot), self.N,
-                                                          _lib.ptr(self.dis), _lib.ptr(w), _lib.stream_ptr()),
-                   "rgbx_gcn_norm_weighted_f32")
+        _lib.launch("rgbx_gcn_norm_weighted_f32", csr.rowptr, csr.col, ew_slot, self.N, self.dis, w)
         return w
 
     @property

@@ -12,7 +12,7 @@ from .. import _lib
 
 def _scratch(n, d, device):
     cnt = ctypes.c_int64(0)
-    _lib.check(_lib.load().rgbx_bn_scratch_doubles(n, d, ctypes.byref(cnt)), "rgbx_bn_scratch_doubles")
+    _lib.call("rgbx_bn_scratch_doubles", n, d, ctypes.byref(cnt))
     return torch.empty(cnt.value, dtype=torch.float64, device=device), cnt.value
 
 
@@ -21,22 +21,20 @@ def column_sums(x):
     if not x.is_cuda:  # host tensors (MLP on the CPU, gloo tests): plain torch, still fp64 accumulation
         xd = x.double()
         return torch.stack([xd.sum(0), (xd * xd).sum(0)])
-    px, ldx = _lib.mat(x, "x")
+    xm = _lib.mat(x, "x")
     n, d = x.shape
     sums = torch.empty((2, d), dtype=torch.float64, device=x.device)
     scratch, cnt = _scratch(n, d, x.device)
-    _lib.check(_lib.load().rgbx_bn_stats_f32(px, ldx, n, d, _lib.ptr(sums), _lib.ptr(scratch), cnt, _lib.stream_ptr()),
-               "rgbx_bn_stats_f32")
+    _lib.launch("rgbx_bn_stats_f32", xm, n, d, sums, scratch, cnt)
     return sums
 
 
 def affine_cols(x, scale, shift):
     if not x.is_cuda:
         return x * scale + shift
-    px, ldx = _lib.mat(x, "x")
+    xm = _lib.mat(x, "x")
     y = torch.empty((x.size(0), x.size(1)), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rgbx_affine_cols_f32(px, ldx, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), y.stride(0),
-                                                x.size(0), x.size(1), _lib.stream_ptr()), "rgbx_affine_cols_f32")
+    _lib.launch("rgbx_affine_cols_f32", xm, scale, shift, y, y.stride(0), x.size(0), x.size(1))
     return y
 
 
@@ -45,25 +43,20 @@ def bwd_sums(gy, x, mean, rstd):
     if not gy.is_cuda:
         xhat = (x - mean) * rstd
         return torch.stack([gy.double().sum(0), (gy * xhat).double().sum(0)])
-    pg, ldg = _lib.mat(gy, "gy")
-    px, ldx = _lib.mat(x, "x")
+    gm, xm = _lib.mat(gy, "gy"), _lib.mat(x, "x")
     n, d = x.shape
     sums = torch.empty((2, d), dtype=torch.float64, device=x.device)
     scratch, cnt = _scratch(n, d, x.device)
-    _lib.check(_lib.load().rgbx_bn_bwd_reduce_f32(pg, ldg, px, ldx, _lib.ptr(mean), _lib.ptr(rstd), n, d, _lib.ptr(sums),
-                                                  _lib.ptr(scratch), cnt, _lib.stream_ptr()), "rgbx_bn_bwd_reduce_f32")
+    _lib.launch("rgbx_bn_bwd_reduce_f32", gm, xm, mean, rstd, n, d, sums, scratch, cnt)
     return sums
 
 
 def bwd_apply(gy, x, mean, rstd, ca, cb, ck):
     if not gy.is_cuda:
         return (gy - ca - (x - mean) * rstd * cb) * ck
-    pg, ldg = _lib.mat(gy, "gy")
-    px, ldx = _lib.mat(x, "x")
+    gm, xm = _lib.mat(gy, "gy"), _lib.mat(x, "x")
     gx = torch.empty((x.size(0), x.size(1)), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().rgbx_bn_bwd_apply_f32(pg, ldg, px, ldx, _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(ca),
-                                                 _lib.ptr(cb), _lib.ptr(ck), _lib.ptr(gx), gx.stride(0), x.size(0),
-                                                 x.size(1), _lib.stream_ptr()), "rgbx_bn_bwd_apply_f32")
+    _lib.launch("rgbx_bn_bwd_apply_f32", gm, xm, mean, rstd, ca, cb, ck, gx, gx.stride(0), x.size(0), x.size(1))
     return gx
 
 
@@ -113,10 +106,8 @@ def train_statistics(x, weight, bias, eps, reduce, running, colsums=None, packed
     if x.is_cuda:
         mean, rstd, scale, shift = (torch.empty(d, dtype=torch.float32, device=x.device) for _ in range(4))
         rm, rv, mom = running if running is not None else (None, None, 0.0)
-        _lib.check(_lib.load().rgbx_bn_finalize_f32(
-            _lib.ptr(packed), _lib.ptr(weight.detach().contiguous()), _lib.ptr(bias.detach().contiguous()),
-            float(eps), float(mom), _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(scale),
-            _lib.ptr(shift), d, _lib.stream_ptr()), "rgbx_bn_finalize_f32")
+        _lib.launch("rgbx_bn_finalize_f32", packed, weight.detach().contiguous(), bias.detach().contiguous(), float(eps),
+                    float(mom), rm, rv, mean, rstd, scale, shift, d)
     else:
         mean64 = packed[:d] / n
         var64 = (packed[d:2 * d] / n - mean64 * mean64).clamp_(min=0.0)  # biased variance
@@ -157,10 +148,7 @@ def train_backward_coefficients(gy, x, weight, mean, rstd, n, reduce, grads_out=
         ca, cb, ck = (torch.empty(d, dtype=torch.float32, device=gy.device) for _ in range(3))
         gw, gb = grads_out if grads_out is not None else (torch.empty(d, dtype=torch.float32, device=gy.device)
                                                           for _ in range(2))
-        _lib.check(_lib.load().rgbx_bn_bwd_finalize_f32(
-            _lib.ptr(glob), _lib.ptr(local), _lib.ptr(n), _lib.ptr(weight.detach().contiguous()), _lib.ptr(rstd),
-            _lib.ptr(ca), _lib.ptr(cb), _lib.ptr(ck), _lib.ptr(gw), _lib.ptr(gb), d, _lib.stream_ptr()),
-            "rgbx_bn_bwd_finalize_f32")
+        _lib.launch("rgbx_bn_bwd_finalize_f32", glob, local, n, weight.detach().contiguous(), rstd, ca, cb, ck, gw, gb, d)
     else:
         glob = glob.reshape(2, -1)
         ca = (glob[0] / n).float().contiguous()

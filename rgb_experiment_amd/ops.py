@@ -48,23 +48,25 @@ class _Timed:
         return False
 
 
+def _launch(kind, name, *args, variant=None):
+    """Launch the entry point `name` on the current stream inside a `_Timed(kind, variant)` bracket (_lib.launch): the
+    arguments are marshalled BEFORE the bracket opens, so its start event sits directly in front of the launch, and the
+    return code is checked after it has closed. Without an event sink the bracket would do nothing and is not made."""
+    _lib.launch(name, *args, bracket=None if _EVENT_SINK is None else _Timed(kind, variant))
+
+
 def spmm_raw(csr, w, rs, x, y=None, a=1.0, b=0.0, out=None, kind="spmm", bias=None):
     """out[i] = a*rs[i]*sum_p w[p]*x[col[p]] + b*y[i] + bias over `csr` (no autograd)."""
     _lib.require_device(x, y, bias)
     x = x if x.stride(-1) == 1 else x.contiguous()
-    px, ldx = _lib.mat(x, "x")
+    xm = _lib.mat(x, "x")
     N, d = csr.N, x.size(1)
     if out is None:
         out = torch.empty((N, d), dtype=torch.float32, device=x.device)
-    po, ldo = _lib.mat(out, "out")
-    py, ldy = (0, 0) if y is None else _lib.mat(y, "y")
     split, _scratch = csr.split_arg(d, x.device)
-    with _Timed(kind, f"rows+d{d}" if _EVENT_SINK is not None else None):
-        _lib.check(
-            _lib.load().rgbx_spmm_csr_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w), _lib.ptr(rs),
-                                          px, ldx, py, ldy, _lib.ptr(bias), po, ldo, N, d, float(a), float(b),
-                                          None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-            "rgbx_spmm_csr_f32")
+    _launch(kind, "rgbx_spmm_csr_f32", csr.rowptr, csr.col, w, rs, xm, _lib.mat_opt(y, "y"), bias,
+            _lib.mat(out, "out"), N, d, float(a), float(b), split,
+            variant=f"rows+d{d}" if _EVENT_SINK is not None else None)
     return out
 
 
@@ -230,16 +232,11 @@ def edge_dot_raw(csr, a, b, kind="edge_dot"):
     d = a.size(1)
     g = torch.empty(max(csr.nnz, 1), dtype=torch.float32, device=a.device)
     total = None
-    lib = _lib.load()
     for c0 in range(0, d, 256):
         c1 = min(c0 + 256, d)
-        pa, lda = _lib.mat(a[:, c0:c1], "a")
-        pb, ldb = _lib.mat(b[:, c0:c1], "b")
         split, _scratch = (None, None) if csr.split is None else csr.split_arg(1, a.device)
-        with _Timed(kind, f"rows+d{c1 - c0}" if _EVENT_SINK is not None else None):
-            _lib.check(lib.rgbx_edge_dot_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pa, lda, pb, ldb, _lib.ptr(g), csr.N,
-                                             c1 - c0, None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-                       "rgbx_edge_dot_f32")
+        _launch(kind, "rgbx_edge_dot_f32", csr.rowptr, csr.col, _lib.mat(a[:, c0:c1], "a"), _lib.mat(b[:, c0:c1], "b"), g,
+                csr.N, c1 - c0, split, variant=f"rows+d{c1 - c0}" if _EVENT_SINK is not None else None)
         if c1 < d or total is not None:
             total = g.clone() if total is None else total.add_(g)
     return g if total is None else total
@@ -251,11 +248,8 @@ def gcn_norm_bwd(graph, g_slot):
     dev = f.rowptr.device
     dew = torch.empty(max(graph.E, 1), dtype=torch.float32, device=dev)
     ddeg = torch.empty(max(graph.N, 1), dtype=torch.float32, device=dev)
-    with _Timed("gcn_norm_bwd"):
-        _lib.check(_lib.load().rgbx_gcn_norm_bwd_f32(
-            _lib.ptr(f.rowptr), _lib.ptr(f.col), _lib.ptr(f.perm), _lib.ptr(b.rowptr), _lib.ptr(b.col), _lib.ptr(graph.t2f),
-            _lib.ptr(graph.loops[1]), _lib.ptr(g_slot), _lib.ptr(graph.ew_slot), _lib.ptr(graph.dis), graph.N, graph.E,
-            _lib.ptr(ddeg), _lib.ptr(dew), _lib.stream_ptr()), "rgbx_gcn_norm_bwd_f32")
+    _launch("gcn_norm_bwd", "rgbx_gcn_norm_bwd_f32", f.rowptr, f.col, f.perm, b.rowptr, b.col, graph.t2f, graph.loops[1],
+            g_slot, graph.ew_slot, graph.dis, graph.N, graph.E, ddeg, dew)
     return dew[:graph.E]
 
 
@@ -324,20 +318,15 @@ def spmm_extremum_raw(csr, x, mode, want_arg, kind=None):
         raise RuntimeError(f"spmm_extremum_raw: width {d} is no multiple of 4 (pad the rows)")
     out = torch.empty((N, d), dtype=torch.float32, device=x.device)
     arg = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_arg else None
-    lib = _lib.load()
     for c0 in range(0, d, 256):
         c1 = min(c0 + 256, d)
         w = c1 - c0
-        px, ldx = _lib.mat(x[:, c0:c1], "x")
-        po, ldo = _lib.mat(out[:, c0:c1], "out")
         # one column block's arg rows are [N, w] with leading dimension w: a block of a wider matrix gets its own buffer
         blk = arg if (arg is None or w == d) else torch.empty((N, w), dtype=torch.int32, device=x.device)
         split, _scratch = csr.split_arg(2 * w, x.device)  # chunk values + chunk slots
-        with _Timed(kind or f"{mode}_fwd", f"rows+d{w}" + ("+arg" if want_arg else "") if _EVENT_SINK is not None else None):
-            _lib.check(lib.rgbx_spmm_csr_extremum_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), px, ldx, po, ldo,
-                                                      _lib.ptr(blk), N, w, EXTREMUM_MODES[mode],
-                                                      None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-                       "rgbx_spmm_csr_extremum_f32")
+        _launch(kind or f"{mode}_fwd", "rgbx_spmm_csr_extremum_f32", csr.rowptr, csr.col, _lib.mat(x[:, c0:c1], "x"),
+                _lib.mat(out[:, c0:c1], "out"), blk, N, w, EXTREMUM_MODES[mode], split,
+                variant=f"rows+d{w}" + ("+arg" if want_arg else "") if _EVENT_SINK is not None else None)
         if blk is not arg:
             arg[:, c0:c1] = blk
     return out, arg
@@ -351,19 +340,13 @@ def extremum_bwd_raw(graph, gout, arg, kind="extremum_bwd"):
     gout = _rows_on_grid(gout)
     d = gout.size(1)
     gx = torch.empty((csr.N, d), dtype=torch.float32, device=gout.device)
-    lib = _lib.load()
     for c0 in range(0, d, 256):
         c1 = min(c0 + 256, d)
         w = c1 - c0
-        pg, ldg = _lib.mat(gout[:, c0:c1], "gout")
-        px, ldgx = _lib.mat(gx[:, c0:c1], "gx")
         blk = arg if w == d else arg[:, c0:c1].contiguous()
         split, _scratch = csr.split_arg(w, gout.device)
-        with _Timed(kind, f"rows+d{w}" if _EVENT_SINK is not None else None):
-            _lib.check(lib.rgbx_extremum_bwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(t2f), pg, ldg,
-                                                 _lib.ptr(blk), px, ldgx, csr.N, w,
-                                                 None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-                       "rgbx_extremum_bwd_f32")
+        _launch(kind, "rgbx_extremum_bwd_f32", csr.rowptr, csr.col, t2f, _lib.mat(gout[:, c0:c1], "gout"), blk,
+                _lib.mat(gx[:, c0:c1], "gx"), csr.N, w, split, variant=f"rows+d{w}" if _EVENT_SINK is not None else None)
     return gx
 
 
@@ -450,7 +433,6 @@ def spmm_multi_raw(csr, x, which, want_arg, keep=(), kind="multi_fwd"):
     dest.update(kept)
     args = {a: torch.empty((N, dp), dtype=torch.int32, device=dev) for a in ("max", "min") if want_arg and a in names}
     bits = sum(MULTI_BITS[a] for a in dest)
-    lib = _lib.load()
     for c0 in range(0, dp, 256):
         c1 = min(c0 + 256, dp)
         w = c1 - c0
@@ -463,18 +445,13 @@ def spmm_multi_raw(csr, x, which, want_arg, keep=(), kind="multi_fwd"):
             p, ld = _block_ptr(t, c0, c1)
             setattr(o, "arg" + a, p)
             setattr(o, "ld_arg" + a, ld)
-        px, ldx = _block_ptr(x, c0, c1)
         split = None
         if csr.split is not None:
             words = ctypes.c_int64(0)
-            _lib.check(lib.rgbx_spmm_csr_multi_partial_words(csr.split["n_chunks"], w, bits, ctypes.byref(words)),
-                       "rgbx_spmm_csr_multi_partial_words")
+            _lib.call("rgbx_spmm_csr_multi_partial_words", csr.split["n_chunks"], w, bits, ctypes.byref(words))
             split, _scratch = csr.split_arg(words.value // csr.split["n_chunks"], dev)
-        variant = f"rows+d{w}+{'+'.join(dest)}" + ("+arg" if args else "") if _EVENT_SINK is not None else None
-        with _Timed(kind, variant):
-            _lib.check(lib.rgbx_spmm_csr_multi_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), px, ldx, ctypes.byref(o), N, w,
-                                                   None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-                       "rgbx_spmm_csr_multi_f32")
+        _launch(kind, "rgbx_spmm_csr_multi_f32", csr.rowptr, csr.col, _block_ptr(x, c0, c1), o, N, w, split,
+                variant=f"rows+d{w}+{'+'.join(dest)}" + ("+arg" if args else "") if _EVENT_SINK is not None else None)
     out = buf if dp == d else buf.view(N, k, dp)[:, :, :d].reshape(N, k * d)
     cut = (lambda t: t) if dp == d else (lambda t: t[:, :d])
     return (out, cut(args["max"]) if "max" in args else None, cut(args["min"]) if "min" in args else None,
@@ -501,7 +478,6 @@ def multi_bwd_raw(graph, a=None, b=None, x=None, gmax=None, argmax=None, gmin=No
     t2f = graph.t2f if ("gmax" in terms or "gmin" in terms) else None
     dp, dev = (d + 3) // 4 * 4, next(iter(terms.values())).device
     gx = torch.empty((csr.N, dp), dtype=torch.float32, device=dev)
-    lib = _lib.load()
     for c0 in range(0, dp, 256):
         c1 = min(c0 + 256, dp)
         w = c1 - c0
@@ -510,12 +486,9 @@ def multi_bwd_raw(graph, a=None, b=None, x=None, gmax=None, argmax=None, gmin=No
             p, ld = _block_ptr(v, c0, c1)
             setattr(t, k, p)
             setattr(t, "ld_" + k, ld)
-        pg, ldgx = _block_ptr(gx, c0, c1)
         split, _scratch = csr.split_arg(w, dev)
-        with _Timed(kind, f"rows+d{w}+{'+'.join(terms)}" if _EVENT_SINK is not None else None):
-            _lib.check(lib.rgbx_multi_bwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(t2f), ctypes.byref(t), pg,
-                                              ldgx, csr.N, w, None if split is None else ctypes.byref(split),
-                                              _lib.stream_ptr()), "rgbx_multi_bwd_f32")
+        _launch(kind, "rgbx_multi_bwd_f32", csr.rowptr, csr.col, t2f, t, _block_ptr(gx, c0, c1), csr.N, w, split,
+                variant=f"rows+d{w}+{'+'.join(terms)}" if _EVENT_SINK is not None else None)
     return gx if dp == d else gx[:, :d]
 
 
@@ -625,10 +598,9 @@ def spmm_epilogue_raw(csr, w, rs, x, y=None, a=1.0, b=0.0, bias=None, out=None, 
     grad_scale or None) -> (loss gradient w.r.t. the logits, or None when grad_scale is None: nothing is written; stats [3]
     or [2, 3] float64 = nll sum, selected rows, correct). `n_classes`: columns beyond are padding (see pad_rows4)."""
     _lib.require_device(x, y, bias)
-    lib = _lib.load()
-    px, ldx = _lib.mat(x, "x")
+    xm = _lib.mat(x, "x")
     N, d = csr.N, x.size(1)
-    py, ldy = (0, 0) if y is None else _lib.mat(y, "y")
+    ym = _lib.mat_opt(y, "y")
     keep = []
     E = _lib.SpmmEpilogue()
     stats = colsums = None
@@ -656,7 +628,7 @@ def spmm_epilogue_raw(csr, w, rs, x, y=None, a=1.0, b=0.0, bias=None, out=None, 
         want_out = grad_scale is not None
     elif want_colsums:
         nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.rgbx_spmm_linear_stats_workspace_bytes(N, d, ctypes.byref(nbytes)), "rgbx_spmm_linear_stats_workspace_bytes")
+        _lib.call("rgbx_spmm_linear_stats_workspace_bytes", N, d, ctypes.byref(nbytes))
         ws = torch.empty(max(nbytes.value, 8), dtype=torch.uint8, device=x.device)
         colsums = torch.empty((2, d), dtype=torch.float64, device=x.device)
         keep.append(ws)
@@ -665,17 +637,12 @@ def spmm_epilogue_raw(csr, w, rs, x, y=None, a=1.0, b=0.0, bias=None, out=None, 
         raise RuntimeError("spmm_epilogue_raw: no epilogue asked for (use spmm_raw)")
     if out is None and want_out:
         out = torch.empty((N, d), dtype=torch.float32, device=x.device)
-    po, ldo = (0, d) if out is None else _lib.mat(out, "out")
     split, _scratch = csr.split_arg(d, x.device, hub_rows=1)
     variant = None
     if _EVENT_SINK is not None:
         variant = "rows+" + ("stats" if ce is None else ("ce_grad" if want_out else "ce_stats")) + f"+d{d}"
-    with _Timed(kind, variant):
-        _lib.check(
-            lib.rgbx_spmm_csr_epilogue_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w), _lib.ptr(rs), px, ldx,
-                                           py, ldy, _lib.ptr(bias), po, ldo, N, d, float(a), float(b),
-                                           None if split is None else ctypes.byref(split), ctypes.byref(E),
-                                           _lib.stream_ptr()), "rgbx_spmm_csr_epilogue_f32")
+    _launch(kind, "rgbx_spmm_csr_epilogue_f32", csr.rowptr, csr.col, w, rs, xm, ym, bias,
+            (0, d) if out is None else _lib.mat(out, "out"), N, d, float(a), float(b), split, E, variant=variant)
     del keep
     if ce is not None:
         return out, (stats.view(2, 3) if stats.numel() == 6 else stats)
@@ -811,12 +778,11 @@ def to_bf16_rows(t):
     _lib.require_device(t)
     t = t.detach()
     t = t if t.dim() != 2 or t.stride(-1) == 1 or t.size(1) <= 1 else t.contiguous()
-    ps, lds = _lib.mat(t, "t")
+    tm = _lib.mat(t, "t")
     n, d = t.shape
     out = torch.empty((n, d), dtype=torch.bfloat16, device=t.device)
-    with _Timed("rows_to_bf16", f"d{d}" if _EVENT_SINK is not None else None):
-        _lib.check(_lib.load().rgbx_rows_f32_to_bf16(ps, lds, out.data_ptr(), max(d, 1), n, d, _lib.stream_ptr()),
-                   "rgbx_rows_f32_to_bf16")
+    _launch("rows_to_bf16", "rgbx_rows_f32_to_bf16", tm, out, max(d, 1), n, d,
+            variant=f"d{d}" if _EVENT_SINK is not None else None)
     return out
 
 
@@ -843,22 +809,18 @@ def spmm_bf16_raw(csr, w, rs, xb, y=None, a=1.0, b=0.0, bias=None, out=None, out
     # the kernel reads y and bias four floats at a time: an addend half behind an offset view, a bias sliced out of a flat
     # parameter buffer are copied onto that grid (the sums are read from the copy, `out` may still alias the original)
     y = None if y is None else _rows_on_grid(y)
-    py, ldy = (0, 0) if y is None else _lib.mat(y, "y")
+    py, ldy = _lib.mat_opt(y, "y")
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != d):
         raise RuntimeError(f"spmm_bf16_raw: bias must be float32 [{d}]")
     bias = _vec_on_grid(bias, d)
     pb = _lib.ptr(bias)
-    lib = _lib.load()
-    for c0 in range(0, max(d, 1), BF16_MAX_WIDTH):
+    for c0 in range(0, max(d, 1), BF16_MAX_WIDTH):  # the column blocks are pointer offsets into the same matrices
         dc = min(BF16_MAX_WIDTH, d - c0)
         split, _scratch = csr.split_arg(dc, xb.device)
         f32 = (po + 4 * c0, ldo, 0, 0) if out_dtype == torch.float32 else (0, 0, po + 2 * c0, ldo)
-        with _Timed(kind, f"rows+d{dc}" if _EVENT_SINK is not None else None):
-            _lib.check(
-                lib.rgbx_spmm_csr_bf16(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w), _lib.ptr(rs), px + 2 * c0, ldx,
-                                       py + 4 * c0 if py else 0, ldy, pb + 4 * c0 if pb else 0, *f32, N, dc, float(a),
-                                       float(b), None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-                "rgbx_spmm_csr_bf16")
+        _launch(kind, "rgbx_spmm_csr_bf16", csr.rowptr, csr.col, w, rs, px + 2 * c0, ldx, py + 4 * c0 if py else 0, ldy,
+                pb + 4 * c0 if pb else 0, f32, N, dc, float(a), float(b), split,
+                variant=f"rows+d{dc}" if _EVENT_SINK is not None else None)
     return out
 
 
@@ -1036,7 +998,6 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
     A vector that came from selected_cols is also carried in the column stream (col_tags, rgbx_fused_layer_t.col_tag).
     Returns (out, z, colsums or stats)."""
     _lib.require_device(x, wt, bias, x_root, wt_root, out_blocked, col_sel)
-    lib = _lib.load()
     L = _lib.FusedLayer()
     dense = csr is None
     if x.dim() == 3:
@@ -1121,7 +1082,7 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
                 rows = selected_rows(y, mask, n_out)  # None: inside a graph capture before the list exists (all tiles)
         if rows is not None and grad_scale is not None:
             count = ctypes.c_int64(0)
-            _lib.check(lib.rgbx_ce_rows_grad_scratch_doubles(N, ctypes.byref(count)), "rgbx_ce_rows_grad_scratch_doubles")
+            _lib.call("rgbx_ce_rows_grad_scratch_doubles", N, ctypes.byref(count))
             scratch_doubles = count.value
         ce_scratch = torch.empty(scratch_doubles, dtype=torch.float64, device=x.device)
         ce_arg = _lib.CeEpilogue(_lib.ptr(y), _lib.ptr(mask), _lib.ptr(grad_scale), _lib.ptr(ce_stats),
@@ -1165,8 +1126,7 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
     colsums = None
     if want_colsums:
         nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.rgbx_spmm_linear_stats_workspace_bytes(N, n_out, ctypes.byref(nbytes)),
-                   "rgbx_spmm_linear_stats_workspace_bytes")
+        _lib.call("rgbx_spmm_linear_stats_workspace_bytes", N, n_out, ctypes.byref(nbytes))
         ws = torch.empty(max(nbytes.value, 8), dtype=torch.uint8, device=x.device)
         colsums = torch.empty((2, n_out), dtype=torch.float64, device=x.device)
         keep.append(ws)
@@ -1179,8 +1139,7 @@ def fused_layer(x, wt, csr=None, w=None, rs=None, bias=None, x_root=None, wt_roo
             ("zpos", w_pos is not None), ("stats", want_colsums), ("ce_stats", ce is not None and ce[2] is None),
             ("ce_grad", ce is not None and ce[2] is not None), ("noout", out is None and out_blocked is None and ce is None),
             ("blk", out_blocked is not None)) if on]) or "plain"
-    with _Timed(kind, variant):
-        _lib.check(lib.rgbx_fused_layer_f32(ctypes.byref(L), _lib.stream_ptr()), "rgbx_fused_layer_f32")
+    _launch(kind, "rgbx_fused_layer_f32", L, variant=variant)
     del keep
     if groups == 2:
         ce_stats = ce_stats.view(2, 3)  # row k = [nll sum, selected rows, correct] under mask k
@@ -1195,8 +1154,7 @@ def blocked_to_rows(src, out=None, bias=None):
     if out is None:
         out = torch.empty((n, d), dtype=torch.float32, device=src.device)
     b = None if bias is None else bias.detach().contiguous()
-    _lib.check(_lib.load().rgbx_blocked_to_rows_f32(ptr, bc, bs, out.data_ptr(), out.stride(0), n, d, _lib.ptr(b),
-                                                    _lib.stream_ptr()), "rgbx_blocked_to_rows_f32")
+    _lib.launch("rgbx_blocked_to_rows_f32", ptr, bc, bs, out, out.stride(0), n, d, b)
     return out
 
 
@@ -1286,10 +1244,8 @@ def fold_bn_linear(weight, bias=None, bias2=None, root_weight=None, bn=None):
     eps = 0.0
     if bn is not None:
         g, be, rm, rv, eps = c(bn.weight), c(bn.bias), c(bn.running_mean), c(bn.running_var), bn.eps
-    _lib.check(_lib.load().rgbx_fold_bn_linear_f32(
-        _lib.ptr(W), W.stride(0), _lib.ptr(Wr), 0 if Wr is None else Wr.stride(0), _lib.ptr(b1), _lib.ptr(b2),
-        _lib.ptr(g), _lib.ptr(be), _lib.ptr(rm), _lib.ptr(rv), float(eps), _lib.ptr(wt), _lib.ptr(wrt), _lib.ptr(b_out),
-        n_out, K, _lib.stream_ptr()), "rgbx_fold_bn_linear_f32")
+    _lib.launch("rgbx_fold_bn_linear_f32", W, W.stride(0), Wr, 0 if Wr is None else Wr.stride(0), b1, b2, g, be, rm, rv,
+                float(eps), wt, wrt, b_out, n_out, K)
     return wt, b_out, wrt
 
 
@@ -1611,8 +1567,7 @@ def col_tags(csr, col_sel):
         if torch.cuda.is_current_stream_capturing():
             return None
         tag = torch.empty(csr.nnz, dtype=torch.int32, device=csr.col.device)
-        _lib.check(_lib.load().rgbx_col_tag_i32(csr.col.data_ptr(), col_sel.data_ptr(), csr.nnz, col_sel.numel(),
-                                                tag.data_ptr(), _lib.stream_ptr()), "rgbx_col_tag_i32")
+        _lib.launch("rgbx_col_tag_i32", csr.col, col_sel, csr.nnz, col_sel.numel(), tag)
         hit = (_MadeOn(tag), csr.col, col_sel)  # the tensors stay alive with their addresses
         _COL_TAGS[key] = hit
         while len(_COL_TAGS) > 2:
@@ -1801,17 +1756,12 @@ def propagate_linear(x, graph, kind, weight, bias=None, root_weight=None, want_c
 def appnp_raw(csr, w, h, K, alpha, kind="appnp"):
     _lib.require_device(h)
     h = h.contiguous()
-    ph, ldh = _lib.mat(h, "h")
+    hm = _lib.mat(h, "h")
     out = torch.empty_like(h)
     tmp = torch.empty_like(h) if K > 1 else None
-    po, ldo = _lib.mat(out, "out")
+    po, ldo = _lib.mat(out, "out")  # out and tmp share the leading dimension
     split, _scratch = csr.split_arg(h.size(1), h.device)
-    with _Timed(kind):
-        _lib.check(
-            _lib.load().rgbx_appnp_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w), ph, ldh, po,
-                                       _lib.ptr(tmp), ldo, csr.N, h.size(1), int(K), float(alpha),
-                                       None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-            "rgbx_appnp_f32")
+    _launch(kind, "rgbx_appnp_f32", csr.rowptr, csr.col, w, hm, po, tmp, ldo, csr.N, h.size(1), int(K), float(alpha), split)
     return out
 
 
@@ -1895,7 +1845,6 @@ class _DAGNNProp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, graph, K, s, b):
-        lib = _lib.load()
         N, d = x.shape
         x = x.contiguous()
         hops = torch.empty((K, N, d), dtype=torch.float32, device=x.device)
@@ -1906,17 +1855,14 @@ class _DAGNNProp(torch.autograd.Function):
         out = torch.empty_like(x)
         sv = s.detach().reshape(-1).contiguous()
         bv = None if b is None else b.detach().reshape(-1).contiguous()
-        with _Timed("dagnn_gate_fwd"):
-            _lib.check(lib.rgbx_dagnn_gate_fwd_f32(_lib.ptr(x), x.stride(0), _lib.ptr(hops), N * d, d, _lib.ptr(sv),
-                                                   _lib.ptr(bv), _lib.ptr(out), out.stride(0), N, d, K,
-                                                   _lib.stream_ptr()), "rgbx_dagnn_gate_fwd_f32")
+        _launch("dagnn_gate_fwd", "rgbx_dagnn_gate_fwd_f32", x, x.stride(0), hops, N * d, d, sv, bv, out, out.stride(0),
+                N, d, K)
         ctx.graph, ctx.K, ctx.has_b = graph, K, b is not None
         ctx.save_for_backward(x, hops, sv, bv)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.load()
         x, hops, sv, bv = ctx.saved_tensors
         g, K = ctx.graph, ctx.K
         N, d = x.shape
@@ -1926,14 +1872,10 @@ class _DAGNNProp(torch.autograd.Function):
         g_s = torch.empty(d, dtype=torch.float32, device=x.device)
         g_b = torch.empty(1, dtype=torch.float32, device=x.device) if ctx.has_b else None
         need = ctypes.c_size_t(0)
-        _lib.check(lib.rgbx_dagnn_gate_bwd_workspace_bytes(d, ctypes.byref(need)), "rgbx_dagnn_gate_bwd_workspace_bytes")
+        _lib.call("rgbx_dagnn_gate_bwd_workspace_bytes", d, ctypes.byref(need))
         ws = torch.empty(need.value, dtype=torch.uint8, device=x.device)
-        with _Timed("dagnn_gate_bwd"):
-            _lib.check(lib.rgbx_dagnn_gate_bwd_f32(_lib.ptr(x), x.stride(0), _lib.ptr(hops), N * d, d, _lib.ptr(sv),
-                                                   _lib.ptr(bv), _lib.ptr(gout), gout.stride(0), _lib.ptr(d0),
-                                                   d0.stride(0), _lib.ptr(dk), N * d, d, _lib.ptr(g_s), _lib.ptr(g_b),
-                                                   _lib.ptr(ws), need.value, N, d, K, _lib.stream_ptr()),
-                       "rgbx_dagnn_gate_bwd_f32")
+        _launch("dagnn_gate_bwd", "rgbx_dagnn_gate_bwd_f32", x, x.stride(0), hops, N * d, d, sv, bv, gout, gout.stride(0),
+                d0, d0.stride(0), dk, N * d, d, g_s, g_b, ws, need.value, N, d, K)
         gx = None
         if ctx.needs_input_grad[0]:
             # G_K = direct_K; G_k = A_hat^T G_{k+1} + direct_k, each written over direct_k
@@ -2015,12 +1957,8 @@ def gru_gate_fwd(pre, x, out=None):
     N, C = x.shape
     if out is None:
         out = torch.empty((N, C), dtype=torch.float32, device=x.device)
-    pp, ldp = _lib.mat(pre, "pre")
-    px, ldx = _lib.mat(x, "x")
-    po, ldo = _lib.mat(out, "out")
-    with _Timed("gru_gate_fwd", f"d{C}" if _EVENT_SINK is not None else None):
-        _lib.check(_lib.load().rgbx_gru_gate_fwd_f32(pp, ldp, px, ldx, po, ldo, N, C, _lib.stream_ptr()),
-                   "rgbx_gru_gate_fwd_f32")
+    _launch("gru_gate_fwd", "rgbx_gru_gate_fwd_f32", _lib.mat(pre, "pre"), _lib.mat(x, "x"), _lib.mat(out, "out"), N, C,
+            variant=f"d{C}" if _EVENT_SINK is not None else None)
     return out
 
 
@@ -2030,12 +1968,8 @@ def gru_gate_bwd(pre, x, gout):
     N, C = x.shape
     dpre = torch.empty((N, 4 * C), dtype=torch.float32, device=x.device)
     dx = torch.empty((N, C), dtype=torch.float32, device=x.device)
-    pp, ldp = _lib.mat(pre, "pre")
-    px, ldx = _lib.mat(x, "x")
-    pg, ldg = _lib.mat(gout, "gout")
-    with _Timed("gru_gate_bwd", f"d{C}" if _EVENT_SINK is not None else None):
-        _lib.check(_lib.load().rgbx_gru_gate_bwd_f32(pp, ldp, px, ldx, pg, ldg, dpre.data_ptr(), 4 * C, dx.data_ptr(), C,
-                                                     N, C, _lib.stream_ptr()), "rgbx_gru_gate_bwd_f32")
+    _launch("gru_gate_bwd", "rgbx_gru_gate_bwd_f32", _lib.mat(pre, "pre"), _lib.mat(x, "x"), _lib.mat(gout, "gout"),
+            dpre, 4 * C, dx, C, N, C, variant=f"d{C}" if _EVENT_SINK is not None else None)
     return dpre, dx
 
 
@@ -2053,13 +1987,10 @@ def gru_step_raw(x, graph, weff, wroot, bias, form, want_saved=False):
         z = torch.empty((N, C), dtype=torch.float32, device=dev) if want_saved else None
         pre = torch.empty((N, 4 * C), dtype=torch.float32, device=dev) if want_saved else None
         wt, wtr = weff.detach().t().contiguous(), wroot.detach().t().contiguous()
-        px, ldx = _lib.mat(x, "x")
+        xm = _lib.mat(x, "x")
         split, _scratch = graph.fwd.split_arg(C, dev, hub_rows=True)
-        with _Timed("gru_step_fwd", f"d{C}{'+z+pre' if want_saved else ''}" if _EVENT_SINK is not None else None):
-            _lib.check(_lib.load().rgbx_gru_step_f32(
-                _lib.ptr(graph.fwd.rowptr), _lib.ptr(graph.fwd.col), px, ldx, _lib.ptr(wt), _lib.ptr(wtr), _lib.ptr(b),
-                _lib.ptr(out), C, _lib.ptr(z), C, _lib.ptr(pre), 4 * C, N, C,
-                None if split is None else ctypes.byref(split), _lib.stream_ptr()), "rgbx_gru_step_f32")
+        _launch("gru_step_fwd", "rgbx_gru_step_f32", graph.fwd.rowptr, graph.fwd.col, xm, wt, wtr, b, out, C, z, C, pre,
+                4 * C, N, C, split, variant=f"d{C}{'+z+pre' if want_saved else ''}" if _EVENT_SINK is not None else None)
         return out, z, pre
     if form == "composed":
         pre, z = spmm_linear_raw(graph.fwd, None, None, x, weff.detach().t().contiguous(), b, want_saved, x,
@@ -2125,12 +2056,10 @@ class _GATScores(torch.autograd.Function):
         n = hfeat.size(0)
         a_src = torch.empty((n, H), dtype=torch.float32, device=hfeat.device)
         a_dst = torch.empty_like(a_src)
-        ph, ldh = _lib.mat(hfeat, "hfeat")
+        hm = _lib.mat(hfeat, "hfeat")
         att_s = att_src.reshape(H, C).contiguous()
         att_d = att_dst.reshape(H, C).contiguous()
-        _lib.check(
-            _lib.load().rgbx_gat_scores_f32(ph, ldh, _lib.ptr(att_s), _lib.ptr(att_d), _lib.ptr(a_src),
-                                            _lib.ptr(a_dst), n, H, C, _lib.stream_ptr()), "rgbx_gat_scores_f32")
+        _lib.launch("rgbx_gat_scores_f32", hm, att_s, att_d, a_src, a_dst, n, H, C)
         ctx.save_for_backward(hfeat, att_s, att_d)
         ctx.H, ctx.C, ctx.att_shape = H, C, att_src.shape
         return a_src, a_dst
@@ -2162,19 +2091,11 @@ class _GATAggregate(torch.autograd.Function):
         out = torch.empty((N, H * C), dtype=torch.float32, device=dev)
         m = torch.empty((N, H), dtype=torch.float32, device=dev)
         rden = torch.empty_like(m)
-        ph, ldh = _lib.mat(hfeat, "hfeat")
-        po, ldo = _lib.mat(out, "out")
         csr = graph.fwd
         opos, apos = _gat_train_extras(want_grad, N, H, C, dev)
         split, _scratch = csr.split_arg((2 * H * C + 3 * H) if want_grad else (H * C + 2 * H), dev)
-        with _Timed("gat_fwd"):
-            _lib.check(
-                _lib.load().rgbx_gat_aggregate_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), ph, ldh,
-                                                       _lib.ptr(a_src), _lib.ptr(att), _lib.ptr(a_dst), None, None, None,
-                                                       po, ldo, _lib.ptr(m), _lib.ptr(rden), _lib.ptr(opos),
-                                                       _lib.ptr(apos), N, H, C, float(slope),
-                                                       None if split is None else ctypes.byref(split),
-                                                       _lib.stream_ptr()), "rgbx_gat_aggregate_fwd_f32")
+        _launch("gat_fwd", "rgbx_gat_aggregate_fwd_f32", csr.rowptr, csr.col, _lib.mat(hfeat, "hfeat"), a_src, att, a_dst,
+                None, None, None, _lib.mat(out, "out"), m, rden, opos, apos, N, H, C, float(slope), split)
         ctx.save_for_backward(hfeat, a_src, a_dst, m, rden, out, opos, apos)
         ctx.graph, ctx.H, ctx.C, ctx.slope = graph, H, C, slope
         return out
@@ -2208,14 +2129,10 @@ def _gat_backward_core(g, hfeat, a_src, a_dst, m, rden, out, gout, H, C, slope, 
     opos / apos): the scores are products of hfeat with these vectors, so the source pass folds their backward into
     its g_hfeat store (and forms the source's own score from its row when `a_src` is None)."""
     N, n_src, dev = g.fwd.N, g.bwd.N, gout.device
-    lib = _lib.load()
     nodeq = torch.empty((N, H, 4), dtype=torch.float32, device=dev)  # (a_dst, max - log(1/sum), dsum, -) records
     g_as = torch.empty((n_src, H), dtype=torch.float32, device=dev)
     g_h = torch.empty_like(hfeat)
-    ph, ldh = _lib.mat(hfeat, "hfeat")
-    po, ldo = _lib.mat(out, "out")
-    pg, ldg = _lib.mat(gout, "gout")
-    pgh, ldgh = _lib.mat(g_h, "g_hfeat")
+    hm, gm = _lib.mat(hfeat, "hfeat"), _lib.mat(gout, "gout")
     per_node = opos is not None
     fold = per_node and att is not None
     if a_src is None and not fold:
@@ -2227,19 +2144,11 @@ def _gat_backward_core(g, hfeat, a_src, a_dst, m, rden, out, gout, H, C, slope, 
         g_ad = g_ad_full[:N]
     att2 = torch.cat([att[0].reshape(1, H, C), att[1].reshape(1, H, C)]).contiguous() if fold else None
     ds = None if per_node else torch.empty((max(g.bwd.nnz, 1), H), dtype=torch.float32, device=dev)
-    with _Timed("gat_bwd_prep"):
-        _lib.check(
-            lib.rgbx_gat_bwd_prep_f32(_lib.ptr(a_dst), _lib.ptr(m), _lib.ptr(rden), po, ldo, _lib.ptr(bias), pg, ldg,
-                                      _lib.ptr(nodeq), _lib.ptr(opos), _lib.ptr(apos), float(slope), _lib.ptr(g_ad),
-                                      N, H, C, _lib.stream_ptr()), "rgbx_gat_bwd_prep_f32")
+    _launch("gat_bwd_prep", "rgbx_gat_bwd_prep_f32", a_dst, m, rden, _lib.mat(out, "out"), bias, gm, nodeq, opos, apos,
+            float(slope), g_ad, N, H, C)
     split, _scratch = g.bwd.split_arg(H * C + 2 * H, dev)
-    with _Timed("gat_bwd_src"):
-        _lib.check(
-            lib.rgbx_gat_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), ph, ldh, _lib.ptr(a_src),
-                                     _lib.ptr(nodeq), pg, ldg, pgh, ldgh, _lib.ptr(g_as), _lib.ptr(ds),
-                                     _lib.ptr(att2), _lib.ptr(g_ad_full) if fold else None, n_src, H, C, float(slope),
-                                     None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-            "rgbx_gat_bwd_src_f32")
+    _launch("gat_bwd_src", "rgbx_gat_bwd_src_f32", g.bwd.rowptr, g.bwd.col, hm, a_src, nodeq, gm, _lib.mat(g_h, "g_hfeat"),
+            g_as, ds, att2, g_ad_full if fold else None, n_src, H, C, float(slope), split)
     if not per_node:
         g_ad = spmm_raw(gat_segment_csr(g), None, None, ds, kind="gat_bwd_segsum")
     return g_h, g_as, g_ad
@@ -2293,8 +2202,7 @@ class _GATAttend(torch.autograd.Function):
         att_s = att_src.detach().reshape(H, C).contiguous()
         att_d = att_dst.detach().reshape(H, C).contiguous()
         n_src, N, dev = hfeat.size(0), graph.fwd.N, hfeat.device
-        lib = _lib.load()
-        ph, ldh = _lib.mat(hfeat, "hfeat")
+        hm = _lib.mat(hfeat, "hfeat")
         want_grad = want_grad and sc is None
         in_kernel = _scores_in_kernel(C)
         if in_kernel:
@@ -2306,23 +2214,15 @@ class _GATAttend(torch.autograd.Function):
         else:
             a_src = torch.empty((n_src, H), dtype=torch.float32, device=dev)
             a_dst = torch.empty_like(a_src)
-            _lib.check(lib.rgbx_gat_scores_f32(ph, ldh, _lib.ptr(att_s), _lib.ptr(att_d), _lib.ptr(a_src),
-                                               _lib.ptr(a_dst), n_src, H, C, _lib.stream_ptr()), "rgbx_gat_scores_f32")
+            _lib.launch("rgbx_gat_scores_f32", hm, att_s, att_d, a_src, a_dst, n_src, H, C)
         out = torch.empty((N, H * C), dtype=torch.float32, device=dev)
         m = torch.empty((N, H), dtype=torch.float32, device=dev)
         rden = torch.empty_like(m)
-        po, ldo = _lib.mat(out, "out")
         opos, apos = _gat_train_extras(want_grad, N, H, C, dev)
         split, _scratch = graph.fwd.split_arg((2 * H * C + 3 * H) if want_grad else (H * C + 2 * H), dev)
-        with _Timed("gat_fwd"):
-            _lib.check(
-                lib.rgbx_gat_aggregate_fwd_f32(_lib.ptr(graph.fwd.rowptr), _lib.ptr(graph.fwd.col), ph, ldh,
-                                               _lib.ptr(a_src), _lib.ptr(att_s) if in_kernel else None,
-                                               _lib.ptr(a_dst), _lib.ptr(att_d) if in_kernel else None, _lib.ptr(sc),
-                                               _lib.ptr(b), po, ldo, _lib.ptr(m), _lib.ptr(rden), _lib.ptr(opos),
-                                               _lib.ptr(apos), N, H, C, float(slope),
-                                               None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-                "rgbx_gat_aggregate_fwd_f32")
+        _launch("gat_fwd", "rgbx_gat_aggregate_fwd_f32", graph.fwd.rowptr, graph.fwd.col, hm, a_src,
+                att_s if in_kernel else None, a_dst, att_d if in_kernel else None, sc, b, _lib.mat(out, "out"), m, rden,
+                opos, apos, N, H, C, float(slope), split)
         ctx.save_for_backward(hfeat, a_src, a_dst, m, rden, out, att_s, att_d, b, opos, apos)
         ctx.graph, ctx.H, ctx.C, ctx.slope = graph, H, C, slope
         ctx.att_shapes = (att_src.shape, att_dst.shape)
@@ -2341,21 +2241,15 @@ class _GATAttend(torch.autograd.Function):
         g_h, g_as, g_ad = _gat_backward_core(ctx.graph, hfeat, a_src, a_dst, m, rden, out, gout, H, C, ctx.slope, b,
                                              opos=opos, apos=apos, att=(att_s, att_d))
         g_b = gout.sum(0).reshape(ctx.bias_shape) if b is not None and ctx.needs_input_grad[7] else None
-        lib = _lib.load()
         n = hfeat.size(0)
         n_scr = ctypes.c_int64(0)
-        _lib.check(lib.rgbx_gat_scores_bwd_scratch_floats(n, H, C, ctypes.byref(n_scr)),
-                   "rgbx_gat_scores_bwd_scratch_floats")
+        _lib.call("rgbx_gat_scores_bwd_scratch_floats", n, H, C, ctypes.byref(n_scr))
         scratch = torch.empty(n_scr.value, dtype=torch.float32, device=hfeat.device)
         g_att_s = torch.empty((H, C), dtype=torch.float32, device=hfeat.device)
         g_att_d = torch.empty_like(g_att_s)
-        ph, ldh = _lib.mat(hfeat, "hfeat")
-        with _Timed("gat_scores_bwd"):  # the source pass folded the score terms into g_h: attention-vector sums only
-            _lib.check(
-                lib.rgbx_gat_scores_bwd_f32(ph, ldh, _lib.ptr(g_as), _lib.ptr(g_ad), g_ad.size(0), _lib.ptr(att_s),
-                                            _lib.ptr(att_d), None, 0, _lib.ptr(g_att_s), _lib.ptr(g_att_d),
-                                            _lib.ptr(scratch), n_scr.value, n, H, C, _lib.stream_ptr()),
-                "rgbx_gat_scores_bwd_f32")
+        # the source pass folded the score terms into g_h: attention-vector sums only
+        _launch("gat_scores_bwd", "rgbx_gat_scores_bwd_f32", _lib.mat(hfeat, "hfeat"), g_as, g_ad, g_ad.size(0), att_s,
+                att_d, None, 0, g_att_s, g_att_d, scratch, n_scr.value, n, H, C)
         return (g_h, g_att_s.reshape(ctx.att_shapes[0]), g_att_d.reshape(ctx.att_shapes[1]), None, None, None, None, g_b,
                 None, None)
 
@@ -2392,14 +2286,8 @@ def gat_edge_softmax(csr, a_src, a_dst, slope, train, N):
     rden = torch.empty_like(m)
     a_pos = torch.empty_like(m) if train else None
     split, _scratch = csr.split_arg(1, dev)  # hub rows: a workgroup each (no scratch used)
-    with _Timed("gat_edge_softmax"):
-        _lib.check(_lib.load().rgbx_gat_edge_softmax_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(a_src),
-                                                         _lib.ptr(a_dst), float(slope), _lib.ptr(alpha),
-                                                         _lib.ptr(alpha_pos), _lib.ptr(m), _lib.ptr(rden),
-                                                         _lib.ptr(a_pos), N,
-                                                         None if split is None else ctypes.byref(split),
-                                                         _lib.stream_ptr()),
-                   "rgbx_gat_edge_softmax_f32")
+    _launch("gat_edge_softmax", "rgbx_gat_edge_softmax_f32", csr.rowptr, csr.col, a_src, a_dst, float(slope), alpha,
+            alpha_pos, m, rden, a_pos, N, split)
     return alpha, alpha_pos, m, rden, a_pos
 
 
@@ -2427,9 +2315,7 @@ class _GATAttendLinear(torch.autograd.Function):
         n_src, N, dev = x.size(0), graph.fwd.N, x.device
         a_src = torch.empty(n_src, dtype=torch.float32, device=dev)
         a_dst = torch.empty_like(a_src)
-        px, ldx = _lib.mat(x, "x")
-        _lib.check(_lib.load().rgbx_gat_scores_f32(px, ldx, _lib.ptr(v[0]), _lib.ptr(v[1]), _lib.ptr(a_src),
-                                                   _lib.ptr(a_dst), n_src, 1, K, _lib.stream_ptr()), "rgbx_gat_scores_f32")
+        _lib.launch("rgbx_gat_scores_f32", _lib.mat(x, "x"), v[0], v[1], a_src, a_dst, n_src, 1, K)
         alpha, alpha_pos, m, rden, a_pos = gat_edge_softmax(graph.fwd, a_src, a_dst, slope, want_grad, N)
         ce = None
         if y is not None:
@@ -2463,19 +2349,14 @@ class _GATAttendLinear(torch.autograd.Function):
         gw, gcol = gemm_tn(dy, z, colsum=True)
         g_x, g_as, g_ad = _gat_backward_core(ctx.graph, x, a_src, a_dst, m, rden, z, g_z, 1, K, ctx.slope, opos=z_pos,
                                              apos=a_pos, att=(v[0:1], v[1:2]))
-        lib = _lib.load()
         n = x.size(0)
         n_scr = ctypes.c_int64(0)
-        _lib.check(lib.rgbx_gat_scores_bwd_scratch_floats(n, 1, K, ctypes.byref(n_scr)), "rgbx_gat_scores_bwd_scratch_floats")
+        _lib.call("rgbx_gat_scores_bwd_scratch_floats", n, 1, K, ctypes.byref(n_scr))
         scratch = torch.empty(n_scr.value, dtype=torch.float32, device=x.device)
         g_v = torch.empty((2, K), dtype=torch.float32, device=x.device)
-        px, ldx = _lib.mat(x, "x")
-        with _Timed("gat_scores_bwd"):  # the source pass folded the score terms into g_x: the vectors' sums only
-            _lib.check(
-                lib.rgbx_gat_scores_bwd_f32(px, ldx, _lib.ptr(g_as), _lib.ptr(g_ad), g_ad.size(0), _lib.ptr(v[0]),
-                                            _lib.ptr(v[1]), None, 0, _lib.ptr(g_v[0]), _lib.ptr(g_v[1]),
-                                            _lib.ptr(scratch), n_scr.value, n, 1, K, _lib.stream_ptr()),
-                "rgbx_gat_scores_bwd_f32")
+        # the source pass folded the score terms into g_x: the vectors' sums only
+        _launch("gat_scores_bwd", "rgbx_gat_scores_bwd_f32", _lib.mat(x, "x"), g_as, g_ad, g_ad.size(0), v[0], v[1], None, 0,
+                g_v[0], g_v[1], scratch, n_scr.value, n, 1, K)
         # v = att W: g_att = g_v W^T, and W collects att^T g_v next to dy^T z
         g_att = g_v @ W.t()
         if scalar is not None:
@@ -2499,21 +2380,13 @@ def gat_attend_linear(x, weight, att_src, att_dst, graph, slope=0.2, bias=None, 
 SUPERGAT_REDRAWS = 8  # candidate pairs a negative slot may draw before it is dropped from the loss
 
 
-def _attn_split(csr, width, dev):
-    """The hub-row plan of `csr` with `width` scratch floats per chunk, as (argument, plan, scratch owner)."""
-    split, scratch = csr.split_arg(width, dev)
-    return (None if split is None else ctypes.byref(split)), split, scratch
-
-
 def supergat_sample_negatives(graph, seed, n_neg):
     """(neg int64 [2, n_neg], valid uint8 [n_neg]): ordered non-edges drawn on the device (no host read)."""
     dev = seed.device
     neg = torch.empty((2, max(n_neg, 1)), dtype=torch.int64, device=dev)[:, :n_neg].contiguous()
     valid = torch.empty(n_neg, dtype=torch.uint8, device=dev)
     keys, n_keys = graph.undirected_keys
-    _lib.check(_lib.load().rgbx_supergat_sample_negatives(_lib.ptr(keys), n_keys, graph.N, _lib.ptr(seed), n_neg,
-                                                          SUPERGAT_REDRAWS, _lib.ptr(neg), _lib.ptr(valid),
-                                                          _lib.stream_ptr()), "rgbx_supergat_sample_negatives")
+    _lib.launch("rgbx_supergat_sample_negatives", keys, n_keys, graph.N, seed, n_neg, SUPERGAT_REDRAWS, neg, valid)
     return neg, valid
 
 
@@ -2526,9 +2399,8 @@ def supergat_random_choices(record, graph, H):
     nnz = csr.nnz
     pos = torch.empty(nnz, dtype=torch.uint8, device=dev)
     drop = torch.empty((nnz, H), dtype=torch.uint8, device=dev)
-    _lib.check(_lib.load().rgbx_supergat_draws_u8(_lib.ptr(record["seed"]), nnz, H, float(record["p_drop"]),
-                                                  float(record["pos_ratio"]), _lib.ptr(pos), _lib.ptr(drop),
-                                                  _lib.stream_ptr()), "rgbx_supergat_draws_u8")
+    _lib.launch("rgbx_supergat_draws_u8", record["seed"], nnz, H, float(record["p_drop"]), float(record["pos_ratio"]), pos,
+                drop)
     deg = (csr.rowptr[1:] - csr.rowptr[:-1]).long()
     dst = torch.repeat_interleave(torch.arange(csr.N, device=dev), deg)
     valid = record["valid"]
@@ -2547,7 +2419,6 @@ class _SuperGATAttend(torch.autograd.Function):
     def forward(ctx, hfeat, att_l, att_r, graph, H, C, slope, bias, train, p_drop, pos_ratio, neg_ratio, neg_edge_index,
                 record):
         _lib.require_device(hfeat, att_l, att_r, bias, neg_edge_index)
-        lib = _lib.load()
         hfeat = _rows_on_grid(hfeat.contiguous(), _head_vec(C))
         b = _vec_on_grid(bias, H * C)
         al = _vec_on_grid(att_l, H * C).view(H, C)
@@ -2558,9 +2429,8 @@ class _SuperGATAttend(torch.autograd.Function):
         out = torch.empty((N, H * C), dtype=torch.float32, device=dev)
         m = torch.empty((N, H), dtype=torch.float32, device=dev)
         rden = torch.empty_like(m)
-        ph, ldh = _lib.mat(hfeat, "hfeat")
-        po, ldo = _lib.mat(out, "out")
-        split_ref, split, _scratch = _attn_split(csr, H * C + 2 * H, dev)
+        hm = _lib.mat(hfeat, "hfeat")
+        split, _scratch = csr.split_arg(H * C + 2 * H, dev)
         seed = records = pos_stats = None
         n_rec = 0
         if train:
@@ -2568,17 +2438,12 @@ class _SuperGATAttend(torch.autograd.Function):
             # on the device: every kernel reads them there
             seed = torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32, device=dev)
             cnt = ctypes.c_int64(0)
-            _lib.check(lib.rgbx_supergat_loss_records(N, split_ref, ctypes.byref(cnt)), "rgbx_supergat_loss_records")
+            _lib.call("rgbx_supergat_loss_records", N, split, ctypes.byref(cnt))
             n_rec = max(cnt.value, 8192)
             records = torch.empty((n_rec, 2), dtype=torch.float32, device=dev)
             pos_stats = torch.empty(2, dtype=torch.float64, device=dev)
-        with _Timed("supergat_fwd"):
-            _lib.check(
-                lib.rgbx_supergat_aggregate_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), ph, ldh, _lib.ptr(al),
-                                                    _lib.ptr(ar), _lib.ptr(b), po, ldo, _lib.ptr(m), _lib.ptr(rden), N, H,
-                                                    C, float(slope), _lib.ptr(seed), float(p_drop), float(pos_ratio),
-                                                    _lib.ptr(records), n_rec, _lib.ptr(pos_stats), split_ref,
-                                                    _lib.stream_ptr()), "rgbx_supergat_aggregate_fwd_f32")
+        _launch("supergat_fwd", "rgbx_supergat_aggregate_fwd_f32", csr.rowptr, csr.col, hm, al, ar, b, _lib.mat(out, "out"),
+                m, rden, N, H, C, float(slope), seed, float(p_drop), float(pos_ratio), records, n_rec, pos_stats, split)
         ctx.train = train
         ctx.graph, ctx.H, ctx.C, ctx.slope = graph, H, C, slope
         ctx.att_shapes = (att_l.shape, att_r.shape)
@@ -2596,10 +2461,7 @@ class _SuperGATAttend(torch.autograd.Function):
             neg, valid = neg_edge_index.contiguous(), None
             n_neg = neg.size(1)
         neg_stats = torch.empty(2, dtype=torch.float64, device=dev)
-        with _Timed("supergat_neg_fwd"):
-            _lib.check(lib.rgbx_supergat_neg_loss_fwd_f32(ph, ldh, _lib.ptr(neg), _lib.ptr(valid), n_neg, H, C,
-                                                          _lib.ptr(records), n_rec, _lib.ptr(neg_stats),
-                                                          _lib.stream_ptr()), "rgbx_supergat_neg_loss_fwd_f32")
+        _launch("supergat_neg_fwd", "rgbx_supergat_neg_loss_fwd_f32", hm, neg, valid, n_neg, H, C, records, n_rec, neg_stats)
         terms = (pos_stats[1] + neg_stats[1]).clamp(min=1.0)
         loss = ((pos_stats[0] + neg_stats[0]) / terms).to(torch.float32)
         if record is not None:
@@ -2618,7 +2480,6 @@ class _SuperGATAttend(torch.autograd.Function):
             seed = neg = valid = None
         g, H, C, slope = ctx.graph, ctx.H, ctx.C, ctx.slope
         p_drop, pos_ratio = ctx.rng
-        lib = _lib.load()
         N, dev = g.fwd.N, hfeat.device
         gout = torch.zeros_like(out) if gout is None else _rows_on_grid(gout.contiguous(), _head_vec(C))
         gl = None
@@ -2629,42 +2490,23 @@ class _SuperGATAttend(torch.autograd.Function):
         g_h = torch.empty_like(hfeat)
         g_ar = torch.empty((N, H), dtype=torch.float32, device=dev)
         g_al = torch.empty_like(g_ar)
-        ph, ldh = _lib.mat(hfeat, "hfeat")
-        po, ldo = _lib.mat(out, "out")
-        pg, ldg = _lib.mat(gout, "gout")
-        pgh, ldgh = _lib.mat(g_h, "g_hfeat")
-        split_ref, split, _scratch = _attn_split(g.fwd, H * C + H, dev)
-        with _Timed("supergat_bwd_dst"):
-            _lib.check(
-                lib.rgbx_supergat_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), ph, ldh, _lib.ptr(al),
-                                              _lib.ptr(ar), _lib.ptr(m), _lib.ptr(rden), po, ldo, _lib.ptr(b), pg, ldg,
-                                              _lib.ptr(nodeq), pgh, ldgh, _lib.ptr(g_ar), N, H, C, float(slope),
-                                              _lib.ptr(seed), p_drop, pos_ratio, _lib.ptr(gl), split_ref,
-                                              _lib.stream_ptr()), "rgbx_supergat_bwd_dst_f32")
-        split_ref, split, _scratch2 = _attn_split(g.bwd, H * C + H, dev)
-        with _Timed("supergat_bwd_src"):
-            _lib.check(
-                lib.rgbx_supergat_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
-                                              _lib.ptr(g.t2f) if train else None, ph, ldh, _lib.ptr(al), _lib.ptr(nodeq),
-                                              pg, ldg, pgh, ldgh, _lib.ptr(g_al), N, H, C, float(slope), _lib.ptr(seed),
-                                              p_drop, pos_ratio, _lib.ptr(gl), split_ref, _lib.stream_ptr()),
-                "rgbx_supergat_bwd_src_f32")
+        hm, gm, ghm = _lib.mat(hfeat, "hfeat"), _lib.mat(gout, "gout"), _lib.mat(g_h, "g_hfeat")
+        split, _scratch = g.fwd.split_arg(H * C + H, dev)
+        _launch("supergat_bwd_dst", "rgbx_supergat_bwd_dst_f32", g.fwd.rowptr, g.fwd.col, hm, al, ar, m, rden,
+                _lib.mat(out, "out"), b, gm, nodeq, ghm, g_ar, N, H, C, float(slope), seed, p_drop, pos_ratio, gl, split)
+        split, _scratch2 = g.bwd.split_arg(H * C + H, dev)
+        _launch("supergat_bwd_src", "rgbx_supergat_bwd_src_f32", g.bwd.rowptr, g.bwd.col, g.t2f if train else None, hm, al,
+                nodeq, gm, ghm, g_al, N, H, C, float(slope), seed, p_drop, pos_ratio, gl, split)
         if train and neg.size(1):
-            with _Timed("supergat_neg_bwd"):
-                _lib.check(lib.rgbx_supergat_neg_loss_bwd_f32(ph, ldh, _lib.ptr(neg), _lib.ptr(valid), neg.size(1), H, C,
-                                                              _lib.ptr(gl), pgh, ldgh, _lib.stream_ptr()),
-                           "rgbx_supergat_neg_loss_bwd_f32")
+            _launch("supergat_neg_bwd", "rgbx_supergat_neg_loss_bwd_f32", hm, neg, valid, neg.size(1), H, C, gl, ghm)
         n_scr = ctypes.c_int64(0)
-        _lib.check(lib.rgbx_gat_scores_bwd_scratch_floats(N, H, C, ctypes.byref(n_scr)),
-                   "rgbx_gat_scores_bwd_scratch_floats")
+        _lib.call("rgbx_gat_scores_bwd_scratch_floats", N, H, C, ctypes.byref(n_scr))
         scratch = torch.empty(n_scr.value, dtype=torch.float32, device=dev)
         g_att_l = torch.empty((H, C), dtype=torch.float32, device=dev)
         g_att_r = torch.empty_like(g_att_l)
-        with _Timed("supergat_att_bwd"):  # g_att_l = sum_j g_al[j] h_j, g_att_r = sum_i g_ar[i] h_i, in workgroup order
-            _lib.check(
-                lib.rgbx_gat_scores_bwd_f32(ph, ldh, _lib.ptr(g_al), _lib.ptr(g_ar), N, _lib.ptr(al), _lib.ptr(ar), None,
-                                            0, _lib.ptr(g_att_l), _lib.ptr(g_att_r), _lib.ptr(scratch), n_scr.value, N, H,
-                                            C, _lib.stream_ptr()), "rgbx_gat_scores_bwd_f32")
+        # g_att_l = sum_j g_al[j] h_j, g_att_r = sum_i g_ar[i] h_i, in workgroup order
+        _launch("supergat_att_bwd", "rgbx_gat_scores_bwd_f32", hm, g_al, g_ar, N, al, ar, None, 0, g_att_l, g_att_r, scratch,
+                n_scr.value, N, H, C)
         g_b = gout.sum(0).reshape(ctx.bias_shape) if b is not None and ctx.needs_input_grad[7] else None
         return (g_h, g_att_l.reshape(ctx.att_shapes[0]), g_att_r.reshape(ctx.att_shapes[1]), None, None, None, None, g_b,
                 None, None, None, None, None, None)
@@ -2703,8 +2545,7 @@ def gatv2_random_choices(record, graph, H):
         keep = torch.ones((nnz, H), dtype=torch.uint8, device=dev)
     else:
         keep = torch.empty((nnz, H), dtype=torch.uint8, device=dev)
-        _lib.check(_lib.load().rgbx_gatv2_draws_u8(_lib.ptr(record["seed"]), nnz, H, float(record["p_drop"]),
-                                                   _lib.ptr(keep), _lib.stream_ptr()), "rgbx_gatv2_draws_u8")
+        _lib.launch("rgbx_gatv2_draws_u8", record["seed"], nnz, H, float(record["p_drop"]), keep)
     deg = (csr.rowptr[1:] - csr.rowptr[:-1]).long()
     return {"keep": keep.bool(), "src": csr.col[:nnz].long(),
             "dst": torch.repeat_interleave(torch.arange(csr.N, device=dev), deg)}
@@ -2718,7 +2559,6 @@ class _GATv2Attend(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xl, xr, att, graph, H, C, slope, bias, train, p_drop, record, want_grad):
         _lib.require_device(xl, xr, att, bias)
-        lib = _lib.load()
         # column blocks of one product stay views, where the widest head still fits a wave at the vector width they allow
         xl, xr = _rows_on_grid(xl, _head_vec(C)), _rows_on_grid(xr, _head_vec(C))
         b = _vec_on_grid(bias, H * C)
@@ -2738,15 +2578,9 @@ class _GATv2Attend(torch.autograd.Function):
         # m / rden are the backward's; without one the kernel runs its inference form
         m = torch.empty((N, H), dtype=torch.float32, device=dev) if want_grad or seed is not None else None
         rden = None if m is None else torch.empty_like(m)
-        pl, ldl = _lib.mat(xl, "xl")
-        pr, ldr = _lib.mat(xr, "xr")
-        po, ldo = _lib.mat(out, "out")
-        split_ref, split, _scratch = _attn_split(csr, H * C + 2 * H, dev)
-        with _Timed("gatv2_fwd"):
-            _lib.check(lib.rgbx_gatv2_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pl, ldl, pr, ldr, _lib.ptr(a),
-                                              _lib.ptr(b), po, ldo, _lib.ptr(m), _lib.ptr(rden), N, H, C, float(slope),
-                                              _lib.ptr(seed), float(p_drop), split_ref, _lib.stream_ptr()),
-                       "rgbx_gatv2_fwd_f32")
+        split, _scratch = csr.split_arg(H * C + 2 * H, dev)
+        _launch("gatv2_fwd", "rgbx_gatv2_fwd_f32", csr.rowptr, csr.col, _lib.mat(xl, "xl"), _lib.mat(xr, "xr"), a, b,
+                _lib.mat(out, "out"), m, rden, N, H, C, float(slope), seed, float(p_drop), split)
         ctx.graph, ctx.H, ctx.C, ctx.slope, ctx.p_drop = graph, H, C, float(slope), float(p_drop)
         ctx.att_shape = att.shape
         ctx.bias_shape = None if bias is None else bias.shape
@@ -2757,7 +2591,6 @@ class _GATv2Attend(torch.autograd.Function):
     def backward(ctx, gout):
         xl, xr, a, b, m, rden, out, seed = ctx.saved_tensors
         g, H, C, slope, p_drop = ctx.graph, ctx.H, ctx.C, ctx.slope, ctx.p_drop
-        lib = _lib.load()
         N, dev = g.fwd.N, xl.device
         F = H * C
         gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
@@ -2765,31 +2598,16 @@ class _GATv2Attend(torch.autograd.Function):
         g_xl = torch.empty((N, F), dtype=torch.float32, device=dev)
         g_xr = torch.empty_like(g_xl)
         g_att = torch.empty(F, dtype=torch.float32, device=dev)
-        pl, ldl = _lib.mat(xl, "xl")
-        pr, ldr = _lib.mat(xr, "xr")
-        po, ldo = _lib.mat(out, "out")
-        pg, ldg = _lib.mat(gout, "gout")
-        pgl, ldgl = _lib.mat(g_xl, "g_xl")
-        pgr, ldgr = _lib.mat(g_xr, "g_xr")
-        split_ref, split, _scratch = _attn_split(g.fwd, F, dev)
+        lm, rm, gm = _lib.mat(xl, "xl"), _lib.mat(xr, "xr"), _lib.mat(gout, "gout")
+        split, _scratch = g.fwd.split_arg(F, dev)
         n_part = ctypes.c_int64(0)
-        _lib.check(lib.rgbx_gatv2_att_partial_floats(N, H, C, split_ref, ctypes.byref(n_part)),
-                   "rgbx_gatv2_att_partial_floats")
+        _lib.call("rgbx_gatv2_att_partial_floats", N, H, C, split, ctypes.byref(n_part))
         part = torch.empty(max(n_part.value, 1), dtype=torch.float32, device=dev)
-        with _Timed("gatv2_bwd_dst"):
-            _lib.check(
-                lib.rgbx_gatv2_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pl, ldl, pr, ldr, _lib.ptr(a),
-                                           _lib.ptr(m), _lib.ptr(rden), po, ldo, _lib.ptr(b), pg, ldg, _lib.ptr(nodeq),
-                                           pgr, ldgr, _lib.ptr(g_att), _lib.ptr(part), n_part.value, N, H, C, slope,
-                                           _lib.ptr(seed), p_drop, split_ref, _lib.stream_ptr()),
-                "rgbx_gatv2_bwd_dst_f32")
-        split_ref, split, _scratch2 = _attn_split(g.bwd, F, dev)
-        with _Timed("gatv2_bwd_src"):
-            _lib.check(
-                lib.rgbx_gatv2_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
-                                           _lib.ptr(g.t2f) if seed is not None else None, pl, ldl, pr, ldr, _lib.ptr(a),
-                                           _lib.ptr(nodeq), pg, ldg, pgl, ldgl, N, H, C, slope, _lib.ptr(seed), p_drop,
-                                           split_ref, _lib.stream_ptr()), "rgbx_gatv2_bwd_src_f32")
+        _launch("gatv2_bwd_dst", "rgbx_gatv2_bwd_dst_f32", g.fwd.rowptr, g.fwd.col, lm, rm, a, m, rden, _lib.mat(out, "out"),
+                b, gm, nodeq, _lib.mat(g_xr, "g_xr"), g_att, part, n_part.value, N, H, C, slope, seed, p_drop, split)
+        split, _scratch2 = g.bwd.split_arg(F, dev)
+        _launch("gatv2_bwd_src", "rgbx_gatv2_bwd_src_f32", g.bwd.rowptr, g.bwd.col, g.t2f if seed is not None else None, lm,
+                rm, a, nodeq, gm, _lib.mat(g_xl, "g_xl"), N, H, C, slope, seed, p_drop, split)
         need = ctx.needs_input_grad
         g_b = gout.sum(0).reshape(ctx.bias_shape) if b is not None and need[7] else None
         return (g_xl if need[0] else None, g_xr if need[1] else None, g_att.reshape(ctx.att_shape) if need[2] else None,
@@ -2834,7 +2652,6 @@ class _TransformerAttend(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, graph, H, C, scale, train, p_drop, record, want_grad):
         _lib.require_device(q, k, v)
-        lib = _lib.load()
         # column blocks of one product stay views, where the widest head still fits a wave at the vector width they allow
         q, k, v = (_rows_on_grid(t, _head_vec(C)) for t in (q, k, v))
         csr, N, dev = graph.fwd, graph.fwd.N, q.device
@@ -2851,16 +2668,9 @@ class _TransformerAttend(torch.autograd.Function):
         # m / rden are the backward's; without one the kernel runs its inference form
         m = torch.empty((N, H), dtype=torch.float32, device=dev) if want_grad or seed is not None else None
         rden = None if m is None else torch.empty_like(m)
-        pq, ldq = _lib.mat(q, "q")
-        pk, ldk = _lib.mat(k, "k")
-        pv, ldv = _lib.mat(v, "v")
-        po, ldo = _lib.mat(out, "out")
-        split_ref, _, _scratch = _attn_split(csr, H * C + 2 * H, dev)
-        with _Timed("transformer_fwd"):
-            _lib.check(lib.rgbx_transformer_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pq, ldq, pk, ldk, pv, ldv,
-                                                    po, ldo, _lib.ptr(m), _lib.ptr(rden), N, H, C, float(scale),
-                                                    _lib.ptr(seed), float(p_drop), split_ref, _lib.stream_ptr()),
-                       "rgbx_transformer_fwd_f32")
+        split, _scratch = csr.split_arg(H * C + 2 * H, dev)
+        _launch("transformer_fwd", "rgbx_transformer_fwd_f32", csr.rowptr, csr.col, _lib.mat(q, "q"), _lib.mat(k, "k"),
+                _lib.mat(v, "v"), _lib.mat(out, "out"), m, rden, N, H, C, float(scale), seed, float(p_drop), split)
         ctx.graph, ctx.H, ctx.C, ctx.scale, ctx.p_drop = graph, H, C, float(scale), float(p_drop)
         ctx.save_for_backward(q, k, v, m, rden, out, seed)
         return out
@@ -2869,7 +2679,6 @@ class _TransformerAttend(torch.autograd.Function):
     def backward(ctx, gout):
         q, k, v, m, rden, out, seed = ctx.saved_tensors
         g, H, C, scale, p_drop = ctx.graph, ctx.H, ctx.C, ctx.scale, ctx.p_drop
-        lib = _lib.load()
         N, dev = g.fwd.N, q.device
         F = H * C
         gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
@@ -2878,29 +2687,14 @@ class _TransformerAttend(torch.autograd.Function):
         g_q = torch.empty((N, F), dtype=torch.float32, device=dev)
         g_k = torch.empty_like(g_q)
         g_v = torch.empty_like(g_q)
-        pq, ldq = _lib.mat(q, "q")
-        pk, ldk = _lib.mat(k, "k")
-        pv, ldv = _lib.mat(v, "v")
-        po, ldo = _lib.mat(out, "out")
-        pg, ldg = _lib.mat(gout, "gout")
-        pgq, ldgq = _lib.mat(g_q, "g_q")
-        pgk, ldgk = _lib.mat(g_k, "g_k")
-        pgv, ldgv = _lib.mat(g_v, "g_v")
-        split_ref, _, _scratch = _attn_split(g.fwd, F, dev)
-        with _Timed("transformer_bwd_dst"):
-            _lib.check(
-                lib.rgbx_transformer_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pq, ldq, pk, ldk, pv, ldv,
-                                                 _lib.ptr(m), _lib.ptr(rden), po, ldo, pg, ldg, _lib.ptr(nodeq), pgq,
-                                                 ldgq, N, H, C, scale, _lib.ptr(seed), p_drop, split_ref,
-                                                 _lib.stream_ptr()), "rgbx_transformer_bwd_dst_f32")
-        split_ref, _, _scratch2 = _attn_split(g.bwd, 2 * F, dev)
-        with _Timed("transformer_bwd_src"):
-            _lib.check(
-                lib.rgbx_transformer_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col),
-                                                 _lib.ptr(g.t2f) if seed is not None else None, pq, ldq, pk, ldk, pv,
-                                                 ldv, _lib.ptr(nodeq), pg, ldg, pgk, ldgk, pgv, ldgv, N, H, C, scale,
-                                                 _lib.ptr(seed), p_drop, split_ref, _lib.stream_ptr()),
-                "rgbx_transformer_bwd_src_f32")
+        qm, km, vm, gm = _lib.mat(q, "q"), _lib.mat(k, "k"), _lib.mat(v, "v"), _lib.mat(gout, "gout")
+        split, _scratch = g.fwd.split_arg(F, dev)
+        _launch("transformer_bwd_dst", "rgbx_transformer_bwd_dst_f32", g.fwd.rowptr, g.fwd.col, qm, km, vm, m, rden,
+                _lib.mat(out, "out"), gm, nodeq, _lib.mat(g_q, "g_q"), N, H, C, scale, seed, p_drop, split)
+        split, _scratch2 = g.bwd.split_arg(2 * F, dev)
+        _launch("transformer_bwd_src", "rgbx_transformer_bwd_src_f32", g.bwd.rowptr, g.bwd.col,
+                g.t2f if seed is not None else None, qm, km, vm, nodeq, gm, _lib.mat(g_k, "g_k"), _lib.mat(g_v, "g_v"),
+                N, H, C, scale, seed, p_drop, split)
         need = ctx.needs_input_grad
         return (g_q if need[0] else None, g_k if need[1] else None, g_v if need[2] else None, None, None, None, None,
                 None, None, None, None)
@@ -2938,7 +2732,6 @@ class _ResGatedAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, k, q, v, graph):
         _lib.require_device(k, q, v)
-        lib = _lib.load()
         C = k.size(1)
         # column blocks of one product stay views, where the row still fits a wave at the vector width they allow
         k, q, v = (_rows_on_grid(t, _head_vec(C)) for t in (k, q, v))
@@ -2947,14 +2740,9 @@ class _ResGatedAggregate(torch.autograd.Function):
             raise RuntimeError(f"resgated_aggregate: k {tuple(k.shape)} / q {tuple(q.shape)} / v {tuple(v.shape)} for a "
                                f"graph of {N} nodes")
         out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: zeros)
-        pk, ldk = _lib.mat(k, "k")
-        pq, ldq = _lib.mat(q, "q")
-        pv, ldv = _lib.mat(v, "v")
-        po, ldo = _lib.mat(out, "out")
-        split_ref, _, _scratch = _attn_split(csr, C, dev)
-        with _Timed("resgated_fwd"):
-            _lib.check(lib.rgbx_resgated_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pk, ldk, pq, ldq, pv, ldv, po,
-                                                 ldo, N, C, split_ref, _lib.stream_ptr()), "rgbx_resgated_fwd_f32")
+        split, _scratch = csr.split_arg(C, dev)
+        _launch("resgated_fwd", "rgbx_resgated_fwd_f32", csr.rowptr, csr.col, _lib.mat(k, "k"), _lib.mat(q, "q"),
+                _lib.mat(v, "v"), _lib.mat(out, "out"), N, C, split)
         ctx.graph = graph
         ctx.save_for_backward(k, q, v)
         return out
@@ -2963,35 +2751,22 @@ class _ResGatedAggregate(torch.autograd.Function):
     def backward(ctx, gout):
         k, q, v = ctx.saved_tensors
         g = ctx.graph
-        lib = _lib.load()
         N, C, dev = g.fwd.N, k.size(1), k.device
         need = ctx.needs_input_grad
         gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
-        pk, ldk = _lib.mat(k, "k")
-        pq, ldq = _lib.mat(q, "q")
-        pv, ldv = _lib.mat(v, "v")
-        pg, ldg = _lib.mat(gout, "gout")
+        km, qm, vm, gm = _lib.mat(k, "k"), _lib.mat(q, "q"), _lib.mat(v, "v"), _lib.mat(gout, "gout")
         g_k = g_q = g_v = None
         if need[0]:
             g_k = torch.empty((N, C), dtype=torch.float32, device=dev)
-            pgk, ldgk = _lib.mat(g_k, "g_k")
-            split_ref, _, _scratch = _attn_split(g.fwd, C, dev)
-            with _Timed("resgated_bwd_dst"):
-                _lib.check(
-                    lib.rgbx_resgated_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pk, ldk, pq, ldq, pv, ldv,
-                                                  pg, ldg, pgk, ldgk, N, C, split_ref, _lib.stream_ptr()),
-                    "rgbx_resgated_bwd_dst_f32")
+            split, _scratch = g.fwd.split_arg(C, dev)
+            _launch("resgated_bwd_dst", "rgbx_resgated_bwd_dst_f32", g.fwd.rowptr, g.fwd.col, km, qm, vm, gm,
+                    _lib.mat(g_k, "g_k"), N, C, split)
         if need[1] or need[2]:  # one pass forms both sums from the same two gathered rows
             g_q = torch.empty((N, C), dtype=torch.float32, device=dev)
             g_v = torch.empty_like(g_q)
-            pgq, ldgq = _lib.mat(g_q, "g_q")
-            pgv, ldgv = _lib.mat(g_v, "g_v")
-            split_ref, _, _scratch2 = _attn_split(g.bwd, 2 * C, dev)
-            with _Timed("resgated_bwd_src"):
-                _lib.check(
-                    lib.rgbx_resgated_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), pk, ldk, pq, ldq, pv, ldv,
-                                                  pg, ldg, pgq, ldgq, pgv, ldgv, N, C, split_ref, _lib.stream_ptr()),
-                    "rgbx_resgated_bwd_src_f32")
+            split, _scratch2 = g.bwd.split_arg(2 * C, dev)
+            _launch("resgated_bwd_src", "rgbx_resgated_bwd_src_f32", g.bwd.rowptr, g.bwd.col, km, qm, vm, gm,
+                    _lib.mat(g_q, "g_q"), _lib.mat(g_v, "g_v"), N, C, split)
         return g_k, g_q if need[1] else None, g_v if need[2] else None, None
 
 
@@ -3085,7 +2860,6 @@ class _GINEAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, e_slot, eps, graph):
         _lib.require_device(x, e_slot, eps)
-        lib = _lib.load()
         C = x.size(1)
         # column blocks of a wider matrix stay views, where the row still fits a wave at the vector width they allow
         x, e = (_rows_on_grid(t, _head_vec(C)) for t in (x, e_slot))
@@ -3094,13 +2868,9 @@ class _GINEAggregate(torch.autograd.Function):
         if csr.nnz == 0:  # no slot row is ever read: a pointer the entry point accepts
             e = torch.empty((1, C), dtype=torch.float32, device=dev)
         out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: the root)
-        px, ldx = _lib.mat(x, "x")
-        pe, lde = _lib.mat(e, "e_slot")
-        po, ldo = _lib.mat(out, "out")
-        split_ref, _, _scratch = _attn_split(csr, C, dev)
-        with _Timed("gine_fwd"):
-            _lib.check(lib.rgbx_gine_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), px, ldx, pe, lde, _lib.ptr(epsv),
-                                             po, ldo, N, C, split_ref, _lib.stream_ptr()), "rgbx_gine_fwd_f32")
+        split, _scratch = csr.split_arg(C, dev)
+        _launch("gine_fwd", "rgbx_gine_fwd_f32", csr.rowptr, csr.col, _lib.mat(x, "x"), _lib.mat(e, "e_slot"), epsv,
+                _lib.mat(out, "out"), N, C, split)
         ctx.graph, ctx.eps_shape = graph, None if eps is None else eps.shape
         ctx.save_for_backward(x, e, epsv)
         return out
@@ -3109,34 +2879,23 @@ class _GINEAggregate(torch.autograd.Function):
     def backward(ctx, gout):
         x, e, epsv = ctx.saved_tensors
         g = ctx.graph
-        lib = _lib.load()
         N, C, dev = g.fwd.N, x.size(1), x.device
         need = ctx.needs_input_grad
         gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
-        px, ldx = _lib.mat(x, "x")
-        pe, lde = _lib.mat(e, "e_slot")
-        pg, ldg = _lib.mat(gout, "gout")
+        xm, em, gm = _lib.mat(x, "x"), _lib.mat(e, "e_slot"), _lib.mat(gout, "gout")
         g_x = g_e = g_eps = None
         if need[1]:
             nnz = g.fwd.nnz
             g_e = torch.empty((nnz, C), dtype=torch.float32, device=dev)  # every slot row is written
             if nnz:
-                pge, ldge = _lib.mat(g_e, "g_e")
-                split_ref, _, _scratch = _attn_split(g.fwd, 1, dev)  # the plan only: this pass leaves no chunk record
-                with _Timed("gine_bwd_edge"):
-                    _lib.check(
-                        lib.rgbx_gine_bwd_edge_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), px, ldx, pe, lde, pg, ldg,
-                                                   pge, ldge, N, C, split_ref, _lib.stream_ptr()),
-                        "rgbx_gine_bwd_edge_f32")
+                split, _scratch = g.fwd.split_arg(1, dev)  # the plan only: this pass leaves no chunk record
+                _launch("gine_bwd_edge", "rgbx_gine_bwd_edge_f32", g.fwd.rowptr, g.fwd.col, xm, em, gm,
+                        _lib.mat(g_e, "g_e"), N, C, split)
         if need[0]:
             g_x = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (no out-edge: the root)
-            pgx, ldgx = _lib.mat(g_x, "g_x")
-            split_ref, _, _scratch2 = _attn_split(g.bwd, C, dev)
-            with _Timed("gine_bwd_src"):
-                _lib.check(
-                    lib.rgbx_gine_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(g.t2f), px, ldx, pe,
-                                              lde, pg, ldg, _lib.ptr(epsv), pgx, ldgx, N, C, split_ref,
-                                              _lib.stream_ptr()), "rgbx_gine_bwd_src_f32")
+            split, _scratch2 = g.bwd.split_arg(C, dev)
+            _launch("gine_bwd_src", "rgbx_gine_bwd_src_f32", g.bwd.rowptr, g.bwd.col, g.t2f, xm, em, gm, epsv,
+                    _lib.mat(g_x, "g_x"), N, C, split)
         if epsv is not None and need[2]:
             g_eps = (gout * x).sum().reshape(ctx.eps_shape)
         return g_x, g_e, g_eps, None
@@ -3187,7 +2946,6 @@ class _CGConvAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, c_slot, root, graph, C, mean):
         _lib.require_device(a, b, c_slot, root)
-        lib = _lib.load()
         # column blocks of one product stay views, where the row still fits a wave at the vector width they allow
         vec = _head_vec(C)
         a, b = (_rows_on_grid(t, vec) for t in (a, b))
@@ -3197,16 +2955,9 @@ class _CGConvAggregate(torch.autograd.Function):
             c = _rows_on_grid(c_slot, vec)
         rt = None if root is None else _rows_on_grid(root, vec)
         out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: the root)
-        pa, lda = _lib.mat(a, "a")
-        pb, ldb = _lib.mat(b, "b")
-        pc, ldc = (0, 0) if c is None else _lib.mat(c, "c_slot")
-        pr, ldr = (0, 0) if rt is None else _lib.mat(rt, "root")
-        po, ldo = _lib.mat(out, "out")
-        split_ref, _, _scratch = _attn_split(csr, C, dev)
-        with _Timed("cgconv_fwd"):
-            _lib.check(lib.rgbx_cgconv_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pa, lda, pb, ldb, pc, ldc, pr, ldr,
-                                               po, ldo, N, C, int(mean), split_ref, _lib.stream_ptr()),
-                       "rgbx_cgconv_fwd_f32")
+        split, _scratch = csr.split_arg(C, dev)
+        _launch("cgconv_fwd", "rgbx_cgconv_fwd_f32", csr.rowptr, csr.col, _lib.mat(a, "a"), _lib.mat(b, "b"),
+                _lib.mat_opt(c, "c_slot"), _lib.mat_opt(rt, "root"), _lib.mat(out, "out"), N, C, int(mean), split)
         ctx.graph, ctx.C, ctx.mean = graph, C, mean
         ctx.c_shape = None if c_slot is None else tuple(c_slot.shape)
         ctx.save_for_backward(a, b, c)
@@ -3216,14 +2967,10 @@ class _CGConvAggregate(torch.autograd.Function):
     def backward(ctx, gout):
         a, b, c = ctx.saved_tensors
         g = ctx.graph
-        lib = _lib.load()
         N, C, dev, mean = g.fwd.N, ctx.C, a.device, int(ctx.mean)
         need = ctx.needs_input_grad
         gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
-        pa, lda = _lib.mat(a, "a")
-        pb, ldb = _lib.mat(b, "b")
-        pc, ldc = (0, 0) if c is None else _lib.mat(c, "c_slot")
-        pg, ldg = _lib.mat(gout, "gout")
+        am, bm, cm, gm = _lib.mat(a, "a"), _lib.mat(b, "b"), _lib.mat_opt(c, "c_slot"), _lib.mat(gout, "gout")
         g_a = g_b = g_c = None
         want_c = need[2] and ctx.c_shape is not None
         if want_c:
@@ -3231,23 +2978,14 @@ class _CGConvAggregate(torch.autograd.Function):
         if need[0] or (want_c and g.fwd.nnz):  # one pass forms both from the same registers
             if need[0]:
                 g_a = torch.empty((N, 2 * C), dtype=torch.float32, device=dev)  # every row is written
-            pga, ldga = (0, 0) if g_a is None else _lib.mat(g_a, "g_a")
-            pgc, ldgc = (0, 0) if not (want_c and g.fwd.nnz) else _lib.mat(g_c, "g_c")
-            split_ref, _, _scratch = _attn_split(g.fwd, 2 * C, dev)
-            with _Timed("cgconv_bwd_dst"):
-                _lib.check(
-                    lib.rgbx_cgconv_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pa, lda, pb, ldb, pc, ldc, pg,
-                                                ldg, pga, ldga, pgc, ldgc, N, C, mean, split_ref, _lib.stream_ptr()),
-                    "rgbx_cgconv_bwd_dst_f32")
+            split, _scratch = g.fwd.split_arg(2 * C, dev)
+            _launch("cgconv_bwd_dst", "rgbx_cgconv_bwd_dst_f32", g.fwd.rowptr, g.fwd.col, am, bm, cm, gm,
+                    _lib.mat_opt(g_a, "g_a"), _lib.mat(g_c, "g_c") if want_c and g.fwd.nnz else (0, 0), N, C, mean, split)
         if need[1]:
             g_b = torch.empty((N, 2 * C), dtype=torch.float32, device=dev)  # every row is written
-            pgb, ldgb = _lib.mat(g_b, "g_b")
-            split_ref, _, _scratch2 = _attn_split(g.bwd, 2 * C, dev)
-            with _Timed("cgconv_bwd_src"):
-                _lib.check(
-                    lib.rgbx_cgconv_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(g.t2f),
-                                                _lib.ptr(g.fwd.rowptr), pa, lda, pb, ldb, pc, ldc, pg, ldg, pgb, ldgb, N,
-                                                C, mean, split_ref, _lib.stream_ptr()), "rgbx_cgconv_bwd_src_f32")
+            split, _scratch2 = g.bwd.split_arg(2 * C, dev)
+            _launch("cgconv_bwd_src", "rgbx_cgconv_bwd_src_f32", g.bwd.rowptr, g.bwd.col, g.t2f, g.fwd.rowptr, am, bm, cm, gm,
+                    _lib.mat(g_b, "g_b"), N, C, mean, split)
         return g_a, g_b, g_c, gout if need[3] else None, None, None, None
 
 
@@ -3340,7 +3078,6 @@ def pna_fwd_raw(csr, a, b, c, avg_deg, aggregators, scalers, F, keep=()):
     """(out [N, T*S*A*F], kept): rgbx_pna_fwd_f32 over `csr` on operands that are already on the vector grid (a, c may be
     None); `keep`: out of 'mean', 'var', 'std', 'argmax', 'argmin', the raw statistics of u stored beside (kept[name],
     [N, d]). No autograd, no checks beyond the entry point's."""
-    lib = _lib.load()
     names, scalers = multi_names(aggregators), pna_scaler_names(scalers)
     N, dev = csr.N, b.device
     d, S, A = b.size(1), len(scalers), len(names)
@@ -3361,23 +3098,18 @@ def pna_fwd_raw(csr, a, b, c, avg_deg, aggregators, scalers, F, keep=()):
             p, ld = _block_ptr(t, c0, c1)
             setattr(o, k, p)
             setattr(o, "ld_" + k, ld)
-        pa, lda = (0, 0) if a is None else _block_ptr(a, c0, c1)
-        pb, ldb = _block_ptr(b, c0, c1)
-        pc, ldc = (0, 0) if c is None else _block_ptr(c, c0, c1)
         split, words = None, 0
         if csr.split is not None:
             n_words = ctypes.c_int64(0)
-            _lib.check(lib.rgbx_pna_partial_words(csr.split["n_chunks"], w, bits | (MULTI_BITS["mean"] if "mean" in kept else 0),
-                                                  ctypes.byref(n_words)), "rgbx_pna_partial_words")
+            _lib.call("rgbx_pna_partial_words", csr.split["n_chunks"], w,
+                      bits | (MULTI_BITS["mean"] if "mean" in kept else 0), ctypes.byref(n_words))
             words = n_words.value
             split, _scratch = csr.split_arg(words // csr.split["n_chunks"], dev)
         variant = (f"rows+d{w}+{'+'.join(names)}x{S}" + ("+c" if c is not None else "") + ("+kept" if kept else "")
                    if _EVENT_SINK is not None else None)
-        with _Timed("pna_fwd", variant):
-            _lib.check(lib.rgbx_pna_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pa, lda, pb, ldb, pc, ldc,
-                                            _lib.ptr(avg), bits, order, kinds, S, ctypes.byref(o), N, w, F,
-                                            None if split is None else ctypes.byref(split), words,
-                                            _lib.stream_ptr()), "rgbx_pna_fwd_f32")
+        _launch("pna_fwd", "rgbx_pna_fwd_f32", csr.rowptr, csr.col, (0, 0) if a is None else _block_ptr(a, c0, c1),
+                _block_ptr(b, c0, c1), (0, 0) if c is None else _block_ptr(c, c0, c1), avg, bits, order, kinds, S, o, N, w, F,
+                split, words, variant=variant)
     return out, kept
 
 
@@ -3385,7 +3117,6 @@ def pna_bwd_raw(graph, terms, b, c, F, want_b=True, want_c=False):
     """(g_b [N, d] or None, g_c [nnz, d] or None): rgbx_pna_bwd_src_f32 over the transposed CSR and rgbx_pna_bwd_edge_f32
     over the forward one, each only where wanted. `terms`: the per-target rows A, B, gmax, argmax, gmin, argmin that are
     present ([N, d], on the vector grid); b and c are read with B alone (c may be None for the source pass). No autograd."""
-    lib = _lib.load()
     first = next(iter(terms.values()))
     N, d, dev = graph.fwd.N, first.size(1), first.device
     nnz = graph.fwd.nnz
@@ -3403,26 +3134,18 @@ def pna_bwd_raw(graph, terms, b, c, F, want_b=True, want_c=False):
             p, ld = _block_ptr(v, c0, c1)
             setattr(t, k, p)
             setattr(t, "ld_" + k, ld)
-        pb, ldb = _block_ptr(b, c0, c1) if with_b else (0, 0)
-        pc, ldc = _block_ptr(c, c0, c1) if (with_b and c is not None) else (0, 0)
-        variant = f"rows+d{w}+{'+'.join(terms)}" + ("+c" if pc else "") if _EVENT_SINK is not None else None
+        bm = _block_ptr(b, c0, c1) if with_b else (0, 0)
+        cm = _block_ptr(c, c0, c1) if (with_b and c is not None) else (0, 0)
+        variant = f"rows+d{w}+{'+'.join(terms)}" + ("+c" if cm[0] else "") if _EVENT_SINK is not None else None
         if want_c:
-            pg, ldg = _block_ptr(g_c, c0, c1)
             split, _scratch = graph.fwd.split_arg(1, dev)  # the plan only: this pass leaves no chunk record
-            with _Timed("pna_bwd_edge", variant):
-                _lib.check(lib.rgbx_pna_bwd_edge_f32(_lib.ptr(graph.fwd.rowptr), _lib.ptr(graph.fwd.col), pb, ldb, pc, ldc,
-                                                     ctypes.byref(t), pg, ldg, N, w,
-                                                     None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-                           "rgbx_pna_bwd_edge_f32")
+            _launch("pna_bwd_edge", "rgbx_pna_bwd_edge_f32", graph.fwd.rowptr, graph.fwd.col, bm, cm, t,
+                    _block_ptr(g_c, c0, c1), N, w, split, variant=variant)
         if want_b:
-            pg, ldg = _block_ptr(g_b, c0, c1)
             bwd = graph.bwd
             split, _scratch2 = bwd.split_arg(w, dev)
-            with _Timed("pna_bwd_src", variant):
-                _lib.check(lib.rgbx_pna_bwd_src_f32(_lib.ptr(bwd.rowptr), _lib.ptr(bwd.col), _lib.ptr(graph.t2f), pb, ldb, pc,
-                                                    ldc, ctypes.byref(t), pg, ldg, bwd.N, w,
-                                                    None if split is None else ctypes.byref(split), _lib.stream_ptr()),
-                           "rgbx_pna_bwd_src_f32")
+            _launch("pna_bwd_src", "rgbx_pna_bwd_src_f32", bwd.rowptr, bwd.col, graph.t2f, bm, cm, t,
+                    _block_ptr(g_b, c0, c1), bwd.N, w, split, variant=variant)
     return g_b, g_c
 
 
@@ -3652,11 +3375,8 @@ def typed_view(graph, edge_type, num_relations):
         etype_f = et[_slot_to_edge(graph)[0].long()].to(torch.int32).contiguous()
         etype_t = etype_f[t2f].contiguous()
         w_f = torch.empty(E, dtype=torch.float32, device=dev)
-        split_ref, _, _scratch = _attn_split(graph.fwd, 1, dev)  # the plan only: the count leaves no chunk record
-        with _Timed("rgcn_slot_norm"):
-            _lib.check(_lib.load().rgbx_rgcn_slot_norm_f32(_lib.ptr(graph.fwd.rowptr), _lib.ptr(etype_f), _lib.ptr(w_f),
-                                                           graph.fwd.N, R, split_ref, _lib.stream_ptr()),
-                       "rgbx_rgcn_slot_norm_f32")
+        split, _scratch = graph.fwd.split_arg(1, dev)  # the plan only: the count leaves no chunk record
+        _launch("rgcn_slot_norm", "rgbx_rgcn_slot_norm_f32", graph.fwd.rowptr, etype_f, w_f, graph.fwd.N, R, split)
         w_t = w_f[t2f].contiguous()
         rel_ptr = torch.zeros(R + 1, dtype=torch.int64)
         rel_ptr[1:] = torch.cumsum(host[2:], 0)
@@ -3713,7 +3433,6 @@ class _RGCNMix(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, comp, y0, view, aggr):
         _lib.require_device(h, comp, y0)
-        lib = _lib.load()
         R, B = comp.shape
         C = h.size(1) // B
         g = view.graph
@@ -3723,14 +3442,9 @@ class _RGCNMix(torch.autograd.Function):
         compv = comp.detach().contiguous()  # a contiguous parameter's own storage: a captured launch follows it
         y = None if y0 is None else _rows_on_grid(y0, vec)
         out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written
-        ph, ldh = _lib.mat(h, "h")
-        py, ldy = (0, 0) if y is None else _lib.mat(y, "y0")
-        po, ldo = _lib.mat(out, "out")
-        split_ref, _, _scratch = _attn_split(csr, C, dev)
-        with _Timed("rgcn_mix_fwd"):
-            _lib.check(lib.rgbx_rgcn_mix_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(view.etype_f),
-                                                 _lib.ptr(view.weights(aggr)), _lib.ptr(compv), ph, ldh, py, ldy, po, ldo,
-                                                 N, R, B, C, split_ref, _lib.stream_ptr()), "rgbx_rgcn_mix_fwd_f32")
+        split, _scratch = csr.split_arg(C, dev)
+        _launch("rgcn_mix_fwd", "rgbx_rgcn_mix_fwd_f32", csr.rowptr, csr.col, view.etype_f, view.weights(aggr), compv,
+                _lib.mat(h, "h"), _lib.mat_opt(y, "y0"), _lib.mat(out, "out"), N, R, B, C, split)
         ctx.view, ctx.aggr, ctx.dims = view, aggr, (R, B, C)
         ctx.save_for_backward(h, compv)
         return out
@@ -3740,32 +3454,23 @@ class _RGCNMix(torch.autograd.Function):
         h, compv = ctx.saved_tensors
         view, aggr, (R, B, C) = ctx.view, ctx.aggr, ctx.dims
         g = view.graph
-        lib = _lib.load()
         N, dev = g.fwd.N, h.device
         need = ctx.needs_input_grad
         gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
-        pg, ldg = _lib.mat(gout, "gout")
+        gm = _lib.mat(gout, "gout")
         g_h = g_comp = None
         if need[0]:
             g_h = torch.empty((N, B * C), dtype=torch.float32, device=dev)  # every row is written (no out-edge: zeros)
-            pgh, ldgh = _lib.mat(g_h, "g_h")
-            split_ref, _, _scratch = _attn_split(g.bwd, B * C, dev)
-            with _Timed("rgcn_mix_bwd_src"):
-                _lib.check(
-                    lib.rgbx_rgcn_mix_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(view.etype_t),
-                                                  _lib.ptr(view.weights(aggr, True)), _lib.ptr(compv), pg, ldg, pgh, ldgh,
-                                                  N, R, B, C, split_ref, _lib.stream_ptr()), "rgbx_rgcn_mix_bwd_src_f32")
+            split, _scratch = g.bwd.split_arg(B * C, dev)
+            _launch("rgcn_mix_bwd_src", "rgbx_rgcn_mix_bwd_src_f32", g.bwd.rowptr, g.bwd.col, view.etype_t,
+                    view.weights(aggr, True), compv, gm, _lib.mat(g_h, "g_h"), N, R, B, C, split)
         if need[1]:
             nnz = g.fwd.nnz
             if nnz:
                 d = torch.empty((nnz, B), dtype=torch.float32, device=dev)  # every (slot, head) is written
-                ph, ldh = _lib.mat(h, "h")
-                split_ref, _, _scratch2 = _attn_split(g.fwd, 1, dev)  # the plan only: this pass leaves no chunk record
-                with _Timed("rgcn_mix_bwd_coef"):
-                    _lib.check(
-                        lib.rgbx_rgcn_mix_bwd_coef_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col),
-                                                       _lib.ptr(view.weights(aggr)), ph, ldh, pg, ldg, _lib.ptr(d), N, R,
-                                                       B, C, split_ref, _lib.stream_ptr()), "rgbx_rgcn_mix_bwd_coef_f32")
+                split, _scratch2 = g.fwd.split_arg(1, dev)  # the plan only: this pass leaves no chunk record
+                _launch("rgcn_mix_bwd_coef", "rgbx_rgcn_mix_bwd_coef_f32", g.fwd.rowptr, g.fwd.col, view.weights(aggr),
+                        _lib.mat(h, "h"), gm, d, N, R, B, C, split)
                 g_comp = spmm_raw(view.rel, None, None, d, kind="rgcn_comp_reduce")  # a relation without slots: zeros
             else:
                 g_comp = torch.zeros((R, B), dtype=torch.float32, device=dev)
@@ -3840,21 +3545,14 @@ def film_fwd_raw(hv, fv, gofs, graph, view, mean, act, y0=None):
     """rgbx_film_fwd_f32 (no autograd): hv [N * R, C] and fv [N * R, gofs + C] (beta at column 0, gamma at column gofs)
     -> out [N, C]. `view`: the TypedView, or None for the single-relation call; `mean` / `act`: the kernels' ints."""
     _lib.require_device(hv, fv, y0)
-    lib = _lib.load()
     csr, N, C, dev = graph.fwd, graph.fwd.N, hv.size(1), hv.device
     R = 1 if view is None else view.R
     # the relation and the weight of every slot; one relation: none of either, the kernel divides by the row length
     etype, w = (None, None) if view is None else (view.etype_f, view.w_f if mean else view.ones)
     out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: y0 / zeros)
-    ph, ldh = _lib.mat(hv, "h")
-    pf, ldf = _lib.mat(fv, "fb")
-    py, ldy = (0, 0) if y0 is None else _lib.mat(y0, "y0")
-    po, ldo = _lib.mat(out, "out")
-    split_ref, _, _scratch = _attn_split(csr, C, dev)
-    with _Timed("film_fwd"):
-        _lib.check(lib.rgbx_film_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(etype), _lib.ptr(w), ph, ldh,
-                                         pf, ldf, gofs, py, ldy, po, ldo, N, R, C, int(mean), int(act), split_ref,
-                                         _lib.stream_ptr()), "rgbx_film_fwd_f32")
+    split, _scratch = csr.split_arg(C, dev)
+    _launch("film_fwd", "rgbx_film_fwd_f32", csr.rowptr, csr.col, etype, w, _lib.mat(hv, "h"), _lib.mat(fv, "fb"), gofs,
+            _lib.mat_opt(y0, "y0"), _lib.mat(out, "out"), N, R, C, int(mean), int(act), split)
     return out
 
 
@@ -3862,12 +3560,9 @@ def film_bwd_raw(hv, fv, gofs, gout, graph, view, mean, act, want_h=True, want_f
     """rgbx_film_bwd_src_f32 and rgbx_film_bwd_film_f32 (no autograd), each launched only when asked for: (g_h [N * R, C]
     or None, g_fb in fv's shape and layout or None)."""
     _lib.require_device(hv, fv, gout)
-    lib = _lib.load()
     N, C, dev = graph.fwd.N, hv.size(1), hv.device
     R = 1 if view is None else view.R
-    ph, ldh = _lib.mat(hv, "h")
-    pf, ldf = _lib.mat(fv, "fb")
-    pg, ldg = _lib.mat(gout, "gout")
+    hm, fm, gm = _lib.mat(hv, "h"), _lib.mat(fv, "fb"), _lib.mat(gout, "gout")
     g_h = g_fb = None
     if want_h:
         if view is None:  # the plain transposed CSR; the mean weight of a slot from its target's row length
@@ -3876,23 +3571,17 @@ def film_bwd_raw(hv, fv, gofs, gout, graph, view, mean, act, want_h=True, want_f
             _, csr, w_bwd = view.select
             w_t, deg_rowptr = (w_bwd if mean else None), None
         g_h = torch.empty((N * R, C), dtype=torch.float32, device=dev)  # every row is written (no out-edge: zeros)
-        pgh, ldgh = _lib.mat(g_h, "g_h")
-        split_ref, _, _scratch = _attn_split(csr, C, dev)
-        with _Timed("film_bwd_src"):
-            _lib.check(lib.rgbx_film_bwd_src_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w_t),
-                                                 _lib.ptr(deg_rowptr), ph, ldh, pf, ldf, gofs, pg, ldg, pgh, ldgh, N, R, C,
-                                                 int(act), split_ref, _lib.stream_ptr()), "rgbx_film_bwd_src_f32")
+        split, _scratch = csr.split_arg(C, dev)
+        _launch("film_bwd_src", "rgbx_film_bwd_src_f32", csr.rowptr, csr.col, w_t, deg_rowptr, hm, fm, gofs, gm,
+                _lib.mat(g_h, "g_h"), N, R, C, int(act), split)
     if want_fb:
         csr = graph.fwd if view is None else view.expand_fwd
         # the kernel writes the two blocks of every row; columns between them (a column block of a wider fb) stay zero
         alloc = torch.empty if gofs == C else torch.zeros
         g_fb = alloc((N * R, gofs + C), dtype=torch.float32, device=dev)
-        pgf, ldgf = _lib.mat(g_fb, "g_fb")
-        split_ref, _, _scratch2 = _attn_split(csr, 2 * C, dev)
-        with _Timed("film_bwd_film"):
-            _lib.check(lib.rgbx_film_bwd_film_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), ph, ldh, pf, ldf, gofs, pg, ldg,
-                                                  pgf, ldgf, N, R, C, int(mean), int(act), split_ref, _lib.stream_ptr()),
-                       "rgbx_film_bwd_film_f32")
+        split, _scratch2 = csr.split_arg(2 * C, dev)
+        _launch("film_bwd_film", "rgbx_film_bwd_film_f32", csr.rowptr, csr.col, hm, fm, gofs, gm, _lib.mat(g_fb, "g_fb"),
+                N, R, C, int(mean), int(act), split)
     return g_h, g_fb
 
 
@@ -4000,7 +3689,6 @@ class _GMMAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, e_slot, mu, sigma, y0, graph, aggr):
         _lib.require_device(h, e_slot, mu, sigma, y0)
-        lib = _lib.load()
         K, D = mu.shape
         M = h.size(1) // K
         csr, N, dev = graph.fwd, graph.fwd.N, h.device
@@ -4014,15 +3702,9 @@ class _GMMAggregate(torch.autograd.Function):
         y = None if y0 is None else _rows_on_grid(y0, vec)
         rs = graph.inv_deg if aggr == "mean" else None
         out = torch.empty((N, M), dtype=torch.float32, device=dev)  # every row is written
-        ph, ldh = _lib.mat(h, "h")
-        pe, lde = _lib.mat(e, "e_slot")
-        py, ldy = (0, 0) if y is None else _lib.mat(y, "y0")
-        po, ldo = _lib.mat(out, "out")
-        split_ref, _, _scratch = _attn_split(csr, M, dev)
-        with _Timed("gmm_fwd"):
-            _lib.check(lib.rgbx_gmm_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pe, lde, _lib.ptr(muv),
-                                            _lib.ptr(sigv), _lib.ptr(rs), ph, ldh, py, ldy, po, ldo, N, K, M, D,
-                                            split_ref, _lib.stream_ptr()), "rgbx_gmm_fwd_f32")
+        split, _scratch = csr.split_arg(M, dev)
+        _launch("gmm_fwd", "rgbx_gmm_fwd_f32", csr.rowptr, csr.col, _lib.mat(e, "e_slot"), muv, sigv, rs, _lib.mat(h, "h"),
+                _lib.mat_opt(y, "y0"), _lib.mat(out, "out"), N, K, M, D, split)
         ctx.graph, ctx.aggr, ctx.dims = graph, aggr, (K, M, D)
         ctx.save_for_backward(h, e, muv, sigv)
         return out
@@ -4031,23 +3713,17 @@ class _GMMAggregate(torch.autograd.Function):
     def backward(ctx, gout):
         h, e, muv, sigv = ctx.saved_tensors
         g, aggr, (K, M, D) = ctx.graph, ctx.aggr, ctx.dims
-        lib = _lib.load()
         N, nnz, dev = g.fwd.N, g.fwd.nnz, h.device
         need = ctx.needs_input_grad
         gout = _rows_on_grid(gout.contiguous(), _head_vec(M))
-        pg, ldg = _lib.mat(gout, "gout")
-        pe, lde = _lib.mat(e, "e_slot")
+        gm, em = _lib.mat(gout, "gout"), _lib.mat(e, "e_slot")
         g_h = g_e = g_mu = g_sigma = None
         if need[0]:
             g_h = torch.empty((N, K * M), dtype=torch.float32, device=dev)  # every row is written (no out-edge: zeros)
-            pgh, ldgh = _lib.mat(g_h, "g_h")
             w_t = g.w_mean_t if aggr == "mean" else None
-            split_ref, _, _scratch = _attn_split(g.bwd, K * M, dev)
-            with _Timed("gmm_bwd_src"):
-                _lib.check(
-                    lib.rgbx_gmm_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(g.t2f), _lib.ptr(w_t),
-                                             pe, lde, _lib.ptr(muv), _lib.ptr(sigv), pg, ldg, pgh, ldgh, N, K, M, D,
-                                             split_ref, _lib.stream_ptr()), "rgbx_gmm_bwd_src_f32")
+            split, _scratch = g.bwd.split_arg(K * M, dev)
+            _launch("gmm_bwd_src", "rgbx_gmm_bwd_src_f32", g.bwd.rowptr, g.bwd.col, g.t2f, w_t, em, muv, sigv, gm,
+                    _lib.mat(g_h, "g_h"), N, K, M, D, split)
         want_e, want_p = need[1], need[2] or need[3]
         if want_e:
             g_e = torch.empty((nnz, D), dtype=torch.float32, device=dev)  # every slot row is written
@@ -4056,19 +3732,13 @@ class _GMMAggregate(torch.autograd.Function):
                              torch.empty((K, D), dtype=torch.float32, device=dev) for _ in range(2))
         if nnz and (want_e or want_p):
             nbytes = ctypes.c_size_t(0)
-            _lib.check(lib.rgbx_gmm_bwd_edge_workspace_bytes(nnz, K, D, ctypes.byref(nbytes)),
-                       "rgbx_gmm_bwd_edge_workspace_bytes")
+            _lib.call("rgbx_gmm_bwd_edge_workspace_bytes", nnz, K, D, ctypes.byref(nbytes))
             ws = torch.empty(max(nbytes.value // 4, 1), dtype=torch.float32, device=dev)
-            ph, ldh = _lib.mat(h, "h")
-            pge, ldge = _lib.mat(g_e, "g_e") if want_e else (0, 0)
             rs = g.inv_deg if aggr == "mean" else None
-            split_ref, _, _scratch2 = _attn_split(g.fwd, 1, dev)  # the plan only: this pass leaves no chunk record
-            with _Timed("gmm_bwd_edge"):
-                _lib.check(
-                    lib.rgbx_gmm_bwd_edge_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), pe, lde, _lib.ptr(muv),
-                                              _lib.ptr(sigv), _lib.ptr(rs), ph, ldh, pg, ldg, pge, ldge, _lib.ptr(g_mu),
-                                              _lib.ptr(g_sigma), _lib.ptr(ws), ws.numel() * 4, N, nnz, K, M, D,
-                                              split_ref, _lib.stream_ptr()), "rgbx_gmm_bwd_edge_f32")
+            split, _scratch2 = g.fwd.split_arg(1, dev)  # the plan only: this pass leaves no chunk record
+            _launch("gmm_bwd_edge", "rgbx_gmm_bwd_edge_f32", g.fwd.rowptr, g.fwd.col, em, muv, sigv, rs, _lib.mat(h, "h"),
+                    gm, _lib.mat(g_e, "g_e") if want_e else (0, 0), g_mu, g_sigma, ws, ws.numel() * 4, N, nnz, K, M, D,
+                    split)
         return (g_h, g_e, g_mu if need[2] else None, g_sigma if need[3] else None, gout if need[4] else None, None,
                 None)
 
@@ -4140,11 +3810,8 @@ def degree_pseudo(graph):
         dev = csr.rowptr.device
         u = torch.empty((csr.nnz, 2), dtype=torch.float32, device=dev)  # every slot is written
         if csr.nnz:
-            split_ref, _, _scratch = _attn_split(csr, 1, dev)  # the plan only: no chunk record
-            with _Timed("gmm_degree_pseudo"):
-                _lib.check(_lib.load().rgbx_gmm_degree_pseudo_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(u),
-                                                                  csr.N, split_ref, _lib.stream_ptr()),
-                           "rgbx_gmm_degree_pseudo_f32")
+            split, _scratch = csr.split_arg(1, dev)  # the plan only: no chunk record
+            _launch("gmm_degree_pseudo", "rgbx_gmm_degree_pseudo_f32", csr.rowptr, csr.col, u, csr.N, split)
         cached = graph._degree_pseudo = u
     return cached
 
@@ -4159,7 +3826,6 @@ class _SoftmaxAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, m, t, graph, want_grad):
         _lib.require_device(m, t)
-        lib = _lib.load()
         C = m.size(1)
         m = _rows_on_grid(m, _head_vec(C))
         csr, N, dev = graph.fwd, graph.fwd.N, m.device
@@ -4167,14 +3833,9 @@ class _SoftmaxAggregate(torch.autograd.Function):
         out = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (rows without slots: zeros)
         # lse is the backward's; without one the kernel runs its inference form
         lse = torch.empty((N, C), dtype=torch.float32, device=dev) if want_grad else None
-        pm, ldm = _lib.mat(m, "m")
-        po, ldo = _lib.mat(out, "out")
-        pl, ldl = _lib.mat(lse, "lse") if lse is not None else (None, 0)
-        split_ref, _, _scratch = _attn_split(csr, 3 * C, dev)
-        with _Timed("softmax_aggr_fwd"):
-            _lib.check(lib.rgbx_softmax_aggr_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), pm, ldm, _lib.ptr(tv),
-                                                     int(tv.numel() > 1), po, ldo, pl, ldl, N, C, split_ref,
-                                                     _lib.stream_ptr()), "rgbx_softmax_aggr_fwd_f32")
+        split, _scratch = csr.split_arg(3 * C, dev)
+        _launch("softmax_aggr_fwd", "rgbx_softmax_aggr_fwd_f32", csr.rowptr, csr.col, _lib.mat(m, "m"), tv, tv.numel() > 1,
+                _lib.mat(out, "out"), _lib.mat_opt(lse, "lse"), N, C, split)
         ctx.graph, ctx.t_shape = graph, t.shape
         ctx.save_for_backward(m, tv, out, lse)
         return out
@@ -4186,29 +3847,19 @@ class _SoftmaxAggregate(torch.autograd.Function):
         need = ctx.needs_input_grad
         if not (need[0] or need[1]):
             return None, None, None, None
-        lib = _lib.load()
         N, C, dev = g.fwd.N, m.size(1), m.device
         gout = _rows_on_grid(gout.contiguous(), _head_vec(C))
         g_m = torch.empty((N, C), dtype=torch.float32, device=dev)  # every row is written (sources without slots: zeros)
-        pm, ldm = _lib.mat(m, "m")
-        po, ldo = _lib.mat(out, "out")
-        pl, ldl = _lib.mat(lse, "lse")
-        pg, ldg = _lib.mat(gout, "gout")
-        pgm, ldgm = _lib.mat(g_m, "g_m")
-        split_ref, split, _scratch = _attn_split(g.bwd, C, dev)
+        split, _scratch = g.bwd.split_arg(C, dev)
         g_t = part = None
         n_part = ctypes.c_int64(0)
         if need[1]:
-            _lib.check(lib.rgbx_softmax_aggr_gt_partial_floats(N, C, split_ref, ctypes.byref(n_part)),
-                       "rgbx_softmax_aggr_gt_partial_floats")
+            _lib.call("rgbx_softmax_aggr_gt_partial_floats", N, C, split, ctypes.byref(n_part))
             g_t = torch.empty(C, dtype=torch.float32, device=dev)
             part = torch.empty(max(n_part.value, 1), dtype=torch.float32, device=dev)
-        with _Timed("softmax_aggr_bwd", variant="g_t" if need[1] else None):
-            _lib.check(
-                lib.rgbx_softmax_aggr_bwd_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), pm, ldm, _lib.ptr(tv),
-                                              int(tv.numel() > 1), po, ldo, pl, ldl, pg, ldg, pgm, ldgm, _lib.ptr(g_t),
-                                              _lib.ptr(part), n_part.value, N, C, split_ref, _lib.stream_ptr()),
-                "rgbx_softmax_aggr_bwd_f32")
+        _launch("softmax_aggr_bwd", "rgbx_softmax_aggr_bwd_f32", g.bwd.rowptr, g.bwd.col, _lib.mat(m, "m"), tv,
+                tv.numel() > 1, _lib.mat(out, "out"), _lib.mat(lse, "lse"), _lib.mat(gout, "gout"), _lib.mat(g_m, "g_m"),
+                g_t, part, n_part.value, N, C, split, variant="g_t" if need[1] else None)
         if g_t is not None:  # the kernels leave g_t per channel: a scalar temperature's gradient is the sum
             g_t = (g_t if tv.numel() > 1 else g_t.sum()).reshape(ctx.t_shape)
         return g_m if need[0] else None, g_t, None, None
@@ -4266,8 +3917,7 @@ def faconv_random_choices(record, graph):
         keep = torch.ones(nnz, dtype=torch.uint8, device=dev)
     else:
         keep = torch.empty(nnz, dtype=torch.uint8, device=dev)
-        _lib.check(_lib.load().rgbx_faconv_draws_u8(_lib.ptr(record["seed"]), nnz, float(record["p_drop"]), _lib.ptr(keep),
-                                                    _lib.stream_ptr()), "rgbx_faconv_draws_u8")
+        _lib.launch("rgbx_faconv_draws_u8", record["seed"], nnz, float(record["p_drop"]), keep)
     deg = (csr.rowptr[1:] - csr.rowptr[:-1]).long()
     return {"keep": keep.bool(), "src": csr.col[:nnz].long(),
             "dst": torch.repeat_interleave(torch.arange(csr.N, device=dev), deg)}
@@ -4276,22 +3926,15 @@ def faconv_random_choices(record, graph):
 def _faconv_edge_coef(csr, w, slot, alr, transposed, seed, p_drop, want_q):
     coef = torch.empty(max(csr.nnz, 1), dtype=torch.float32, device=alr.device)
     q = torch.empty_like(coef) if want_q else None
-    with _Timed("faconv_edge_coef"):
-        _lib.check(_lib.load().rgbx_faconv_edge_coef_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w),
-                                                         _lib.ptr(slot), _lib.ptr(alr), int(transposed), csr.N,
-                                                         _lib.ptr(seed), float(p_drop), _lib.ptr(coef), _lib.ptr(q),
-                                                         _lib.stream_ptr()), "rgbx_faconv_edge_coef_f32")
+    _launch("faconv_edge_coef", "rgbx_faconv_edge_coef_f32", csr.rowptr, csr.col, w, slot, alr, int(transposed), csr.N,
+            seed, float(p_drop), coef, q)
     return coef, q
 
 
 def _faconv_edge_dot(csr, q, a, b, out, column):
     """out[:, column] = per-row sums of q[p] <a[row], b[col[p]]> (out [N, 2])."""
-    pa, lda = _lib.mat(a, "a")
-    pb, ldb = _lib.mat(b, "b")
-    with _Timed("faconv_edge_dot"):
-        _lib.check(_lib.load().rgbx_faconv_edge_dot_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(q), pa, lda, pb,
-                                                        ldb, out.data_ptr() + 4 * column, 2, csr.N, a.size(1),
-                                                        _lib.stream_ptr()), "rgbx_faconv_edge_dot_f32")
+    _launch("faconv_edge_dot", "rgbx_faconv_edge_dot_f32", csr.rowptr, csr.col, q, _lib.mat(a, "a"), _lib.mat(b, "b"),
+            out.data_ptr() + 4 * column, 2, csr.N, a.size(1))
 
 
 class _FAConv(torch.autograd.Function):
@@ -4302,7 +3945,6 @@ class _FAConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, x0, att_l, att_r, graph, eps, train, p_drop, form, record):
         _lib.require_device(x, x0, att_l, att_r)
-        lib = _lib.load()
         csr, N, dev = graph.fwd, graph.fwd.N, x.device
         C = x.size(1)
         vec = _width_vec(C)  # faconv.hip fa_vec: the kernels read rows that wide
@@ -4320,20 +3962,14 @@ class _FAConv(torch.autograd.Function):
         if record is not None:
             record.update(seed=seed, p_drop=float(p_drop))
         alr = torch.empty((N, 2), dtype=torch.float32, device=dev)
-        px, ldx = _lib.mat(x, "x")
-        with _Timed("faconv_scores"):
-            _lib.check(lib.rgbx_faconv_scores_f32(px, ldx, att[0].data_ptr(), att[1].data_ptr(), _lib.ptr(alr), N, C,
-                                                  _lib.stream_ptr()), "rgbx_faconv_scores_f32")
+        xm = _lib.mat(x, "x")
+        _launch("faconv_scores", "rgbx_faconv_scores_f32", xm, att[0], att[1], alr, N, C)
         if form == "fused":
             out = torch.empty((N, C), dtype=torch.float32, device=dev)
-            po, ldo = _lib.mat(out, "out")
-            p0, ld0 = _lib.mat(x0c, "x_0") if use_x0 else (None, 0)
             split, _scratch = csr.split_arg(C + 1, dev)
-            with _Timed("faconv_fwd"):
-                _lib.check(lib.rgbx_faconv_fwd_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(graph.w), px, ldx,
-                                                   _lib.ptr(alr), p0, ld0, float(eps), po, ldo, N, C, _lib.ptr(seed),
-                                                   float(p_drop), None if split is None else ctypes.byref(split),
-                                                   _lib.stream_ptr()), "rgbx_faconv_fwd_f32")
+            _launch("faconv_fwd", "rgbx_faconv_fwd_f32", csr.rowptr, csr.col, graph.w, xm, alr,
+                    _lib.mat(x0c, "x_0") if use_x0 else (0, 0), float(eps), _lib.mat(out, "out"), N, C, seed, float(p_drop),
+                    split)
         else:
             coef, _ = _faconv_edge_coef(csr, graph.w, None, alr, 0, seed, p_drop, False)
             out = spmm_raw(csr, coef, None, x, y=x0c, a=1.0, b=float(eps), kind="faconv_fwd_composed")
@@ -4346,29 +3982,19 @@ class _FAConv(torch.autograd.Function):
     def backward(ctx, gout):
         x, alr, att, seed = ctx.saved_tensors
         g, p_drop = ctx.graph, ctx.p_drop
-        lib = _lib.load()
         N, C, dev = x.size(0), x.size(1), x.device
         gout = _rows_on_grid(gout.contiguous(), _width_vec(C))
         g_alr = torch.empty((N, 2), dtype=torch.float32, device=dev)
-        px, ldx = _lib.mat(x, "x")
-        pg, ldg = _lib.mat(gout, "gout")
+        xm, gm = _lib.mat(x, "x"), _lib.mat(gout, "gout")
         t2f = g.t2f if seed is not None else None
         if ctx.form == "fused":
             g_x = torch.empty_like(x)
-            pgx, ldgx = _lib.mat(g_x, "g_x")
             split, _scratch = g.fwd.split_arg(C + 1, dev)
-            with _Timed("faconv_bwd_dst"):
-                _lib.check(lib.rgbx_faconv_bwd_dst_f32(_lib.ptr(g.fwd.rowptr), _lib.ptr(g.fwd.col), _lib.ptr(g.w), px, ldx,
-                                                       _lib.ptr(alr), pg, ldg, _lib.ptr(g_alr), N, C, _lib.ptr(seed), p_drop,
-                                                       None if split is None else ctypes.byref(split),
-                                                       _lib.stream_ptr()), "rgbx_faconv_bwd_dst_f32")
+            _launch("faconv_bwd_dst", "rgbx_faconv_bwd_dst_f32", g.fwd.rowptr, g.fwd.col, g.w, xm, alr, gm, g_alr, N, C,
+                    seed, p_drop, split)
             split, _scratch2 = g.bwd.split_arg(C + 1, dev)
-            with _Timed("faconv_bwd_src"):
-                _lib.check(lib.rgbx_faconv_bwd_src_f32(_lib.ptr(g.bwd.rowptr), _lib.ptr(g.bwd.col), _lib.ptr(g.w_t),
-                                                       _lib.ptr(t2f), px, ldx, _lib.ptr(alr), pg, ldg, att[0].data_ptr(),
-                                                       att[1].data_ptr(), _lib.ptr(g_alr), pgx, ldgx, N, C, _lib.ptr(seed),
-                                                       p_drop, None if split is None else ctypes.byref(split),
-                                                       _lib.stream_ptr()), "rgbx_faconv_bwd_src_f32")
+            _launch("faconv_bwd_src", "rgbx_faconv_bwd_src_f32", g.bwd.rowptr, g.bwd.col, g.w_t, t2f, xm, alr, gm, att[0],
+                    att[1], g_alr, _lib.mat(g_x, "g_x"), N, C, seed, p_drop, split)
         else:
             _, q = _faconv_edge_coef(g.fwd, g.w, None, alr, 0, seed, p_drop, True)
             _faconv_edge_dot(g.fwd, q, gout, x, g_alr, 1)
@@ -4408,24 +4034,18 @@ def _scores_in_kernel(C):
 def gather_rows(src, idx, out=None):
     """out[r] = src[idx[r]] (idx int32, device)."""
     _lib.require_device(src, idx)
-    ps, lds = _lib.mat(src, "src")
+    sm = _lib.mat(src, "src")
     n, d = idx.numel(), src.size(1)
     if out is None:
         out = torch.empty((n, d), dtype=torch.float32, device=src.device)
-    po, ldo = _lib.mat(out, "dst")
-    _lib.check(_lib.load().rgbx_gather_rows_f32(ps, lds, _lib.ptr(idx), n, d, po, ldo, _lib.stream_ptr()),
-               "rgbx_gather_rows_f32")
+    _lib.launch("rgbx_gather_rows_f32", sm, idx, n, d, _lib.mat(out, "dst"))
     return out
 
 
 def scatter_add_rows(src, idx, dst):
     """dst[idx[r]] += src[r]; idx entries unique."""
     _lib.require_device(src, idx, dst)
-    ps, lds = _lib.mat(src, "src")
-    pd, ldd = _lib.mat(dst, "dst")
-    _lib.check(
-        _lib.load().rgbx_scatter_add_rows_f32(ps, lds, _lib.ptr(idx), idx.numel(), src.size(1), pd, ldd,
-                                              _lib.stream_ptr()), "rgbx_scatter_add_rows_f32")
+    _lib.launch("rgbx_scatter_add_rows_f32", _lib.mat(src, "src"), idx, idx.numel(), src.size(1), _lib.mat(dst, "dst"))
     return dst
 
 
@@ -4443,12 +4063,10 @@ def gemm_tn(a, b, alpha=1.0, colsum=False, out=None, sums_out=None):
     # (align_rows: a read and a write of the operand) buys the 16-byte path — 3 ms for the 11.5 GB operand.
     if a.size(0) >= 4096:
         a, b = (_aligned_rows(t) for t in (a, b))
-    pa, lda = _lib.mat(a, "a")
-    pb, ldb = _lib.mat(b, "b")
+    am, bm = _lib.mat(a, "a"), _lib.mat(b, "b")
     K, M, N = a.size(0), a.size(1), b.size(1)
-    lib = _lib.load()
     nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.rgbx_gemm_tn_workspace_bytes(K, M, N, ctypes.byref(nbytes)), "rgbx_gemm_tn_workspace_bytes")
+    _lib.call("rgbx_gemm_tn_workspace_bytes", K, M, N, ctypes.byref(nbytes))
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=a.device)
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
@@ -4459,9 +4077,8 @@ def gemm_tn(a, b, alpha=1.0, colsum=False, out=None, sums_out=None):
         sums = sums_out if sums_out is not None else torch.empty(M, dtype=torch.float32, device=a.device)
         if tuple(sums.shape) != (M,) or not sums.is_contiguous() or sums.dtype != torch.float32:
             raise RuntimeError(f"gemm_tn: sums_out must be a contiguous float32 [{M}] tensor")
-    with _Timed("gemm_tn", f"{M}x{N}" if _EVENT_SINK is not None else None):
-        _lib.check(lib.rgbx_gemm_tn_f32(pa, lda, pb, ldb, _lib.ptr(out), N, _lib.ptr(sums), K, M, N, float(alpha),
-                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "rgbx_gemm_tn_f32")
+    _launch("gemm_tn", "rgbx_gemm_tn_f32", am, bm, out, N, sums, K, M, N, float(alpha), ws, ws.numel(),
+            variant=f"{M}x{N}" if _EVENT_SINK is not None else None)
     return (out, sums) if colsum else out
 
 
@@ -4474,7 +4091,7 @@ def _gemm_tn_v4(*mats):
 
 def _gemm_tn_buffers(K, M, N, device, colsum):
     nbytes = ctypes.c_size_t(0)
-    _lib.check(_lib.load().rgbx_gemm_tn_workspace_bytes(K, M, N, ctypes.byref(nbytes)), "rgbx_gemm_tn_workspace_bytes")
+    _lib.call("rgbx_gemm_tn_workspace_bytes", K, M, N, ctypes.byref(nbytes))
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=device)
     out = torch.empty((M, N), dtype=torch.float32, device=device)
     return ws, out, torch.empty(M, dtype=torch.float32, device=device) if colsum else None
@@ -4492,11 +4109,8 @@ def gemm_tn_bn_bwd(g, x, mean, rstd, ca, cb, ck, b, colsum=False):
     K, M, N = g.size(0), g.size(1), b.size(1)
     consts = [t.contiguous() for t in (mean, rstd, ca, cb, ck)]
     ws, out, sums = _gemm_tn_buffers(K, M, N, g.device, colsum)
-    (pg, ldg), (px, ldx), (pb, ldb) = (_lib.mat(t, n) for t, n in ((g, "g"), (x, "x"), (b, "b")))
-    with _Timed("gemm_tn", f"{M}x{N}+bn_bwd" if _EVENT_SINK is not None else None):
-        _lib.check(_lib.load().rgbx_gemm_tn_bn_bwd_f32(
-            pg, ldg, px, ldx, *(_lib.ptr(t) for t in consts), pb, ldb, _lib.ptr(out), N, _lib.ptr(sums), K, M, N, 1.0,
-            _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "rgbx_gemm_tn_bn_bwd_f32")
+    _launch("gemm_tn", "rgbx_gemm_tn_bn_bwd_f32", _lib.mat(g, "g"), _lib.mat(x, "x"), *consts, _lib.mat(b, "b"), out, N,
+            sums, K, M, N, 1.0, ws, ws.numel(), variant=f"{M}x{N}+bn_bwd" if _EVENT_SINK is not None else None)
     return out, sums
 
 
@@ -4513,11 +4127,8 @@ def gemm_tn_rows(a, b, rows, colsum=False, rows_only=False):
         return gemm_tn(a, b, colsum=colsum)
     K, M, N = a.size(0), a.size(1), b.size(1)
     ws, out, sums = _gemm_tn_buffers(K, M, N, a.device, colsum)
-    (pa, lda), (pb, ldb) = _lib.mat(a, "a"), _lib.mat(b, "b")
-    with _Timed("gemm_tn", f"{M}x{N}+rows" if _EVENT_SINK is not None else None):
-        _lib.check(_lib.load().rgbx_gemm_tn_rows_f32(
-            pa, lda, pb, ldb, _lib.ptr(rows), rows.numel(), _lib.ptr(out), N, _lib.ptr(sums), K, M, N, 1.0,
-            _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "rgbx_gemm_tn_rows_f32")
+    _launch("gemm_tn", "rgbx_gemm_tn_rows_f32", _lib.mat(a, "a"), _lib.mat(b, "b"), rows, rows.numel(), out, N, sums, K, M,
+            N, 1.0, ws, ws.numel(), variant=f"{M}x{N}+rows" if _EVENT_SINK is not None else None)
     return (out, sums) if colsum else out
 
 
@@ -4573,13 +4184,11 @@ def short_rows_ok(csr, table):
 def spmm_short_rows_raw(csr, w, x, bias=None, kind="spmm"):
     """out[i,:] = sum_p w[p] x[col[p],:] (+ bias) on rgbx_spmm_csr_short_rows_f32 (no autograd)."""
     _lib.require_device(x, w, bias)
-    px, ldx = _lib.mat(x, "x")
+    xm = _lib.mat(x, "x")
     N, d = csr.N, x.size(1)
     out = torch.empty((N, d), dtype=torch.float32, device=x.device)
-    with _Timed(kind, f"shortrows+d{d}" if _EVENT_SINK is not None else None):
-        _lib.check(_lib.load().rgbx_spmm_csr_short_rows_f32(_lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(w), px, ldx,
-                                                            _lib.ptr(bias), _lib.ptr(out), d, N, d, _lib.stream_ptr()),
-                   "rgbx_spmm_csr_short_rows_f32")
+    _launch(kind, "rgbx_spmm_csr_short_rows_f32", csr.rowptr, csr.col, w, xm, bias, out, d, N, d,
+            variant=f"shortrows+d{d}" if _EVENT_SINK is not None else None)
     return out
 
 
@@ -4712,18 +4321,15 @@ def _nll_stats(logp, y, mask, want_acc):
         raise RuntimeError(f"labels must be int64, got {y.dtype}")
     if mask is not None and mask.dtype not in (torch.bool, torch.uint8):
         raise RuntimeError(f"mask must be bool, got {mask.dtype}")
-    pl, ld = _lib.mat(logp, "logp")
-    lib = _lib.load()
+    lm = _lib.mat(logp, "logp")
     stats = torch.empty(3, dtype=torch.float64, device=logp.device)
     n_scr = ctypes.c_int64(0)
-    _lib.check(lib.rgbx_masked_nll_scratch_doubles(logp.size(0), int(want_acc), ctypes.byref(n_scr)),
-               "rgbx_masked_nll_scratch_doubles")
+    _lib.call("rgbx_masked_nll_scratch_doubles", logp.size(0), int(want_acc), ctypes.byref(n_scr))
     scratch = torch.empty(n_scr.value, dtype=torch.float64, device=logp.device)
     y = y.contiguous()
     mask = None if mask is None else mask.contiguous()
-    _lib.check(lib.rgbx_masked_nll_fwd_f32(pl, ld, _lib.ptr(y), _lib.ptr(mask), logp.size(0), logp.size(1),
-                                           _lib.ptr(stats), _lib.ptr(scratch), n_scr.value, int(want_acc),
-                                           _lib.stream_ptr()), "rgbx_masked_nll_fwd_f32")
+    _lib.launch("rgbx_masked_nll_fwd_f32", lm, y, mask, logp.size(0), logp.size(1), stats, scratch, n_scr.value,
+                int(want_acc))
     return stats, y, mask
 
 
@@ -4744,9 +4350,7 @@ class _MaskedNLL(torch.autograd.Function):
         scale = (g.double() / ctx.count if ctx.reduction == "mean" else g.double()).float().reshape(1).contiguous()
         N, C = ctx.shape
         grad = torch.empty((N, C), dtype=torch.float32, device=g.device)
-        _lib.check(_lib.load().rgbx_masked_nll_bwd_f32(_lib.ptr(ctx.y), _lib.ptr(ctx.mask), N, C, _lib.ptr(scale),
-                                                       _lib.ptr(grad), C, _lib.stream_ptr()),
-                   "rgbx_masked_nll_bwd_f32")
+        _lib.launch("rgbx_masked_nll_bwd_f32", ctx.y, ctx.mask, N, C, scale, grad, C)
         return grad, None, None, None
 
 
@@ -4760,18 +4364,14 @@ def _ce_stats(logits, y, mask):
         raise RuntimeError(f"labels must be int64, got {y.dtype}")
     if mask is not None and mask.dtype not in (torch.bool, torch.uint8):
         raise RuntimeError(f"mask must be bool, got {mask.dtype}")
-    pz, ld = _lib.mat(logits, "logits")
-    lib = _lib.load()
+    zm = _lib.mat(logits, "logits")
     stats = torch.empty(3, dtype=torch.float64, device=logits.device)
     n_scr = ctypes.c_int64(0)
-    _lib.check(lib.rgbx_masked_nll_scratch_doubles(logits.size(0), 1, ctypes.byref(n_scr)),
-               "rgbx_masked_nll_scratch_doubles")
+    _lib.call("rgbx_masked_nll_scratch_doubles", logits.size(0), 1, ctypes.byref(n_scr))
     scratch = torch.empty(n_scr.value, dtype=torch.float64, device=logits.device)
     y = y.contiguous()
     mask = None if mask is None else mask.contiguous()
-    _lib.check(lib.rgbx_masked_ce_fwd_f32(pz, ld, _lib.ptr(y), _lib.ptr(mask), logits.size(0), logits.size(1),
-                                          _lib.ptr(stats), _lib.ptr(scratch), n_scr.value, _lib.stream_ptr()),
-               "rgbx_masked_ce_fwd_f32")
+    _lib.launch("rgbx_masked_ce_fwd_f32", zm, y, mask, logits.size(0), logits.size(1), stats, scratch, n_scr.value)
     return stats, y, mask
 
 
@@ -4796,10 +4396,7 @@ class _MaskedCE(torch.autograd.Function):
         scale = (g.double() / ctx.count if ctx.reduction == "mean" else g.double()).float().reshape(1).contiguous()
         N, C = logits.shape
         grad = torch.empty((N, C), dtype=torch.float32, device=g.device)
-        pz, ld = _lib.mat(logits, "logits")
-        _lib.check(_lib.load().rgbx_masked_ce_bwd_f32(pz, ld, _lib.ptr(ctx.y), _lib.ptr(ctx.mask), N, C,
-                                                      _lib.ptr(scale), _lib.ptr(grad), C, _lib.stream_ptr()),
-                   "rgbx_masked_ce_bwd_f32")
+        _lib.launch("rgbx_masked_ce_bwd_f32", _lib.mat(logits, "logits"), ctx.y, ctx.mask, N, C, scale, grad, C)
         return grad, None, None, None
 
 
@@ -4827,17 +4424,14 @@ def masked_ce_accuracy_blocked(blk, y, mask=None, bias=None):
         raise RuntimeError(f"mask must be bool, got {mask.dtype}")
     ptr, bc, bs = _blocked(blk, "logits")
     n, C = blk.size(1), blk.size(0) * blk.size(2)
-    lib = _lib.load()
     stats = torch.empty(3, dtype=torch.float64, device=blk.device)
     n_scr = ctypes.c_int64(0)
-    _lib.check(lib.rgbx_masked_nll_scratch_doubles(n, 1, ctypes.byref(n_scr)), "rgbx_masked_nll_scratch_doubles")
+    _lib.call("rgbx_masked_nll_scratch_doubles", n, 1, ctypes.byref(n_scr))
     scratch = torch.empty(n_scr.value, dtype=torch.float64, device=blk.device)
     y = y.contiguous()
     mask = None if mask is None else mask.contiguous()
     b = None if bias is None else bias.detach().contiguous()
-    _lib.check(lib.rgbx_masked_ce_fwd_blocked_f32(ptr, bc, bs, _lib.ptr(b), _lib.ptr(y), _lib.ptr(mask), n, C,
-                                                  _lib.ptr(stats), _lib.ptr(scratch), n_scr.value, _lib.stream_ptr()),
-               "rgbx_masked_ce_fwd_blocked_f32")
+    _lib.launch("rgbx_masked_ce_fwd_blocked_f32", ptr, bc, bs, b, y, mask, n, C, stats, scratch, n_scr.value)
     return stats
 
 

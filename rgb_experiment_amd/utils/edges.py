@@ -13,7 +13,7 @@ import torch
 
 def _coalesce_device(edge_index, num_nodes, mirror):
     from .. import _lib
-    lib = _lib.load()
+    _lib.load()  # a library that is not built is reported first
     _lib.require_device(edge_index)
     if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
         raise RuntimeError(f"edge_index must be int64 [2, E], got {edge_index.dtype} {tuple(edge_index.shape)}")
@@ -24,19 +24,16 @@ def _coalesce_device(edge_index, num_nodes, mirror):
         return edge_index.new_empty((2, 0))
     row, col = edge_index[0].contiguous(), edge_index[1].contiguous()
     nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.rgbx_coalesce_workspace_bytes(E, N, int(mirror), ctypes.byref(nbytes)), "rgbx_coalesce_workspace_bytes")
+    _lib.call("rgbx_coalesce_workspace_bytes", E, N, int(mirror), ctypes.byref(nbytes))
     keys = torch.empty(M, dtype=torch.int64, device=dev)  # uint64 keys below 2^62
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
-    stream = _lib.stream_ptr()
-    _lib.check(lib.rgbx_coalesce_keys_i64(_lib.ptr(row), _lib.ptr(col), E, N, int(mirror), _lib.ptr(keys),
-                                          _lib.ptr(counts), _lib.ptr(ws), ws.numel(), stream), "rgbx_coalesce_keys_i64")
+    _lib.launch("rgbx_coalesce_keys_i64", row, col, E, N, int(mirror), keys, counts, ws, ws.numel())
     n_out, n_bad = counts.tolist()  # the one read-back: the output's size is a result
     if n_bad:
         raise RuntimeError(f"edge_index has {n_bad} endpoints outside [0, {N})")
     out = torch.empty((2, n_out), dtype=torch.int64, device=dev)
-    _lib.check(lib.rgbx_split_edge_keys_i64(_lib.ptr(keys), _lib.ptr(counts), n_out, N, _lib.ptr(out[0]),
-                                            _lib.ptr(out[1]), stream), "rgbx_split_edge_keys_i64")
+    _lib.launch("rgbx_split_edge_keys_i64", keys, counts, n_out, N, out[0], out[1])
     return out
 
 

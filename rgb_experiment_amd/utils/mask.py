@@ -45,7 +45,7 @@ def _py_shuffled_range(n, seed):
             lib = None
         if lib is not None:
             out = torch.empty(n, dtype=torch.int64)
-            _lib.check(lib.rgbx_py_random_shuffle_i64(seed, n, out.data_ptr()), "rgbx_py_random_shuffle_i64")
+            _lib.call("rgbx_py_random_shuffle_i64", seed, n, out)
             return out
     order = list(range(n))
     random.shuffle(order)
