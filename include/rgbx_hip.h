@@ -55,6 +55,8 @@
  *   rgbx_gather_rows_f32 / rgbx_scatter_add_rows_f32
  *                         halo pack / unpack for the 1-D node partition (new capability; the
  *                         reference is single-device, itexperiments.py:246).
+ *   rgbx_sample_*         fan-out neighbour sampling (GraphSAGE's mini-batches; new capability: the reference trains on
+ *                         the whole graph in every step, itexperiments.py:417-440).
  *
  * Conventions
  *   - Plain C types only. Every pointer except `rgbx_last_error_string`'s result is a DEVICE
@@ -1559,6 +1561,57 @@ int rgbx_faconv_edge_dot_f32(const int32_t* rowptr, const int32_t* col, const fl
 
 /* keep[p] = 1 where forward slot p survives the dropout of this seed. */
 int rgbx_faconv_draws_u8(const uint32_t* seed, int64_t nnz, float p_drop, uint8_t* keep, rgbx_stream_t stream);
+
+/* ---- neighbour sampling: fan-out mini-batches ------------------------------------------------ */
+
+/* One hop over the target-grouped CSR (graph mode keep: no slot is added, duplicate edges are separate slots). Row g =
+ * rows[r] (distinct global ids; an id outside [0, N) counts as a row without slots) has deg = rowptr[g + 1] - rowptr[g]
+ * slots and keeps min(fanout, deg) of them (fanout = -1: all): the ones with the smallest 64-bit keys
+ *   draw32(seed[0], seed[1], 0x082EFA98 + hop, g, t) << 32 | t,    t = slot - rowptr[g]   (draw32: csrc/rgbx_rng.h),
+ * written in ascending slot order — a uniform draw without replacement that depends on (seed, hop, g, t) only. `seed`
+ * points to two 32-bit words ON THE DEVICE. fanout == 0 or < -1: RGBX_E_ARG. */
+
+/* Bytes of workspace that rgbx_sample_count over n_rows rows and rgbx_sample_frontier over n_cand candidates take (the
+ * larger of the two). Asks rocPRIM for its temporary sizes: may return a hipError where no device is present. */
+int rgbx_sample_workspace_bytes(int64_t n_rows, int64_t n_cand, int64_t N, size_t* bytes);
+
+/* out_rowptr[0 .. n_rows] = exclusive scan of min(fanout, deg): out_rowptr[n_rows] is the hop's number of sampled
+ * edges. class_rows (NULL, or 2 words): the number of rows with more than 64 slots up to 1024, and with more than 1024
+ * — the row-length classes whose kernels rgbx_sample_pick may leave out when they are empty. */
+int rgbx_sample_count(const int32_t* rowptr, int64_t N, const int32_t* rows, int64_t n_rows, int fanout,
+                      int32_t* out_rowptr, int32_t* class_rows, void* workspace, size_t workspace_bytes,
+                      rgbx_stream_t stream);
+
+/* The row-length classes of rgbx_sample_pick: one kernel each. */
+#define RGBX_SAMPLE_SHORT_ROWS 1 /* deg <= 64: 16 lanes per row */
+#define RGBX_SAMPLE_WAVE_ROWS 2  /* 64 < deg <= 1024: a wave per row */
+#define RGBX_SAMPLE_HUB_ROWS 4   /* deg > 1024: a workgroup per row */
+#define RGBX_SAMPLE_ALL_ROWS 7
+
+/* out_col[p] = the source and out_slot[p] = the CSR slot of every kept slot, p in [out_rowptr[r], out_rowptr[r + 1]) for
+ * row r (out_rowptr from rgbx_sample_count with the same rows and fanout). `classes`: the kernels to launch
+ * (RGBX_SAMPLE_*); a class that is left out must have no rows. */
+int rgbx_sample_pick(const int32_t* rowptr, const int32_t* col, int64_t N, const int32_t* rows, int64_t n_rows,
+                     int fanout, const uint32_t* seed, int hop, const int32_t* out_rowptr, int32_t* out_col,
+                     int32_t* out_slot, int classes, rgbx_stream_t stream);
+
+/* local_of [N] maps a global id to its id in the batch, -1 = not in the batch. The distinct candidates cand[0 .. n_cand)
+ * with local_of < 0 get, in ascending global id, the local ids first_local, first_local + 1, ...; they are written to
+ * new_ids (room for n_cand) and *count = how many (device word). Radix sort of the candidates + a scan: O(n_cand). */
+int rgbx_sample_frontier(const int32_t* cand, int64_t n_cand, int32_t* local_of, int64_t N, int64_t first_local,
+                         int32_t* new_ids, int32_t* count, void* workspace, size_t workspace_bytes,
+                         rgbx_stream_t stream);
+
+/* local_of[ids[i]] = first_local + i, or -1 for every i when first_local < 0 (the reset after a batch: it touches the
+ * batch's entries only). ids distinct. */
+int rgbx_sample_set_local(const int32_t* ids, int64_t n, int64_t first_local, int32_t* local_of, int64_t N,
+                          rgbx_stream_t stream);
+
+/* A hop's edges in batch ids, int64 as edge_index is: src[p] = local_of[col[p]], dst[p] = first_row + r for p in row r
+ * (the rows of a hop hold consecutive local ids), e_id[p] = perm[slot[p]] (NULL perm: the slot itself; NULL e_id: skipped). */
+int rgbx_sample_relabel(const int32_t* out_rowptr, int64_t n_rows, const int32_t* col, const int32_t* slot,
+                        int64_t n_edges, const int32_t* local_of, int64_t N, const int32_t* perm, int64_t first_row,
+                        int64_t* src, int64_t* dst, int64_t* e_id, rgbx_stream_t stream);
 
 #ifdef __cplusplus
 }

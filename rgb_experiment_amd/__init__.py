@@ -4,6 +4,7 @@ from .data import Data
 from .initial_params import InitialParameters
 from .itexperiments import compare_pred_label, experiment, label_propagation, normalized_adjacency, test
 from .rd2pd import RD2PD
+from .sampler import NeighborSampler
 
 
 
@@ -16,4 +17,4 @@ def visualize_feature(x, y=None, pics_root=None, pic_name="pic1.png", title=None
 
 __version__ = "0.1.0"
 __all__ = ["experiment", "test", "compare_pred_label", "label_propagation", "normalized_adjacency",
-           "InitialParameters", "RD2PD", "Data", "visualize_feature"]
+           "InitialParameters", "RD2PD", "Data", "visualize_feature", "NeighborSampler"]

@@ -232,6 +232,12 @@ SIGNATURES = {
     "rgbx_faconv_edge_coef_f32": [_P, _P, _P, _P, _P, _I, _I64, _P, _F, _P, _P, _P],
     "rgbx_faconv_edge_dot_f32": [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P],
     "rgbx_faconv_draws_u8": [_P, _I64, _F, _P, _P],
+    "rgbx_sample_workspace_bytes": [_I64, _I64, _I64, ctypes.POINTER(ctypes.c_size_t)],
+    "rgbx_sample_count": [_P, _I64, _P, _I64, _I, _P, _P, _P, ctypes.c_size_t, _P],
+    "rgbx_sample_pick": [_P, _P, _I64, _P, _I64, _I, _P, _I, _P, _P, _P, _I, _P],
+    "rgbx_sample_frontier": [_P, _I64, _P, _I64, _I64, _P, _P, _P, ctypes.c_size_t, _P],
+    "rgbx_sample_set_local": [_P, _I64, _I64, _P, _I64, _P],
+    "rgbx_sample_relabel": [_P, _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P],
 }
 EXPORTS = ["rgbx_version", "rgbx_last_error_string"] + list(SIGNATURES)
 

@@ -386,3 +386,12 @@ def _get_weighted(edge_index, num_nodes, loops_mode, edge_weight):
 def clear_cache():
     _CACHE.clear()
     _PINNED.clear()
+
+
+def forget(edge_index):
+    """Drop the cached (not the pinned) graphs of this edge_index tensor. A sampled mini-batch's edge list lives for one
+    training step: left in the cache, sixteen of them would push the whole graph's own structures out between two
+    evaluation forwards."""
+    head = _key(edge_index, 0, 0)[:4]
+    for key in [k for k in _CACHE if k[:4] == head]:
+        del _CACHE[key]

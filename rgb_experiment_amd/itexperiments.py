@@ -231,7 +231,9 @@ def experiment(model_init_param: dict, *,
                task_split: str = "auto",
                use_edge_weight: bool = False,
                use_edge_attr: bool = False,
-               use_edge_type: bool = False):
+               use_edge_type: bool = False,
+               num_neighbors=None,
+               batch_size: int = 1024):
     """Train + evaluate one model on one graph; returns {'ACC', 'precision_score', 'recall_score',
     'f1_macro', 'f1_micro'} (reference :603-605). ``return_model=True`` (an addition) also returns
     the trained module and the per-epoch curves under 'model' / 'history'. ``use_hip_graph=True`` (an
@@ -288,7 +290,24 @@ def experiment(model_init_param: dict, *,
     the flag it runs with one relation) and for a caller's ``model=`` whose forward takes ``edge_type`` (any other
     model_name: ValueError). Not with ``to_undirected_graph`` (that call carries no types: ValueError) and not on the
     partitioned route (NotImplementedError). With the flag off a ``Data`` that happens to carry an ``edge_type`` behaves
-    exactly as one without."""
+    exactly as one without. ``num_neighbors`` (an addition; None, the default, changes nothing): a non-empty list of
+    fan-outs, each >= 1 or -1 for all neighbours, turns the TRAINING side of every epoch into neighbour-sampled
+    mini-batches (rgb_experiment_amd.NeighborSampler, drawn by HIP kernels): the training rows are permuted, cut into
+    batches of ``batch_size`` seeds, and each batch is sampled (hop h draws ``num_neighbors[h]`` in-edges of the nodes hop
+    h - 1 brought in), its feature rows and labels are gathered, the model's training forward runs on the batch's
+    ``(x, edge_index)``, the loss and the train accuracy are taken on its seed rows (the same masked cross-entropy as the
+    full-batch loop), followed by backward and ONE optimizer step per batch; the epoch's ``history`` entries are the
+    seed-weighted means over its batches. Validation and test forwards stay full-graph. The route runs eagerly
+    (``use_hip_graph`` is ignored: shapes change per batch) and ``cache_input_aggregate`` is off on it (a kept
+    whole-graph aggregate must never reach a batch forward). Layers that normalise by the source's degree (``GCNConv``'s
+    ``gcn_norm``) see the BATCH's degrees at its outer ring, as in PyG, and so are not exact there; layers that normalise by
+    the target only (mean or sum SAGE, GIN, the attention families) are exact on the seeds once there are as many hops as
+    layers and all fan-outs are -1. Refused before any device work: a malformed ``num_neighbors`` or ``batch_size`` < 1
+    (ValueError), ``model_name="pta"`` (ValueError), a layer that keeps its first call's propagated features —
+    ``SGConv(cached=True)``, the default of ``model_name="sgc"``: pass ``cached=False`` in ``model_init_param``; also looked for
+    in a caller's ``model=`` — (ValueError: the kept rows of the first batch would meet every other batch and the full-graph
+    evaluation), ``use_edge_weight`` / ``use_edge_attr`` / ``use_edge_type`` (ValueError:
+    the batch's ``e_id`` is what a later change needs for them) and the partitioned route (NotImplementedError)."""
     say = print if print_print else (lambda *a, **k: None)
     say(f"running node classification: {'custom' if specify_data else dataset_name} data, model {model_name}")
 
@@ -302,6 +321,25 @@ def experiment(model_init_param: dict, *,
         raise NotImplementedError("print_pics / vis_feat are reporting features outside the hot-path scope")
     if post_cs and name == "pta":
         raise ValueError("post_cs cannot be combined with PTA (reference :517)")
+    if num_neighbors is not None:
+        from .sampler import check_num_neighbors
+        num_neighbors = check_num_neighbors(num_neighbors)
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f"batch_size must be an int >= 1, got {batch_size!r}")
+        if name == "pta" and model is None:
+            raise ValueError("num_neighbors: PTA trains on labels propagated over the whole graph; it has no sampled form")
+        if use_edge_weight or use_edge_attr or use_edge_type:
+            raise ValueError("num_neighbors cannot be combined with use_edge_weight / use_edge_attr / use_edge_type yet "
+                             "(the sampled batch's e_id is what gathers them)")
+        # a layer that keeps its propagated features after the first call (SGConv(cached=True), SGC's default) would
+        # serve the first batch's rows to every later batch and to the full-graph evaluation
+        keeps = ([type(m).__name__ for m in model.modules() if getattr(m, "cached", False)]
+                 if isinstance(model, nn.Module) else
+                 ["SGConv"] if name == "sgc" and model is None and (model_init_param or {}).get("cached", True) else [])
+        if keeps:
+            raise ValueError(f"num_neighbors: {keeps[0]}(cached=True) keeps the first call's propagated features, which "
+                             "must never meet another batch or the full graph; build it with cached=False "
+                             "(model_name='sgc': model_init_param['cached'] = False)")
     if use_edge_weight:
         if name not in _EDGE_WEIGHT_MODELS or model is not None:
             raise ValueError(f"use_edge_weight=True: model_name={model_name!r} takes no edge weights; the routes that do "
@@ -367,6 +405,8 @@ def experiment(model_init_param: dict, *,
         from .dist.experiment import SUPPORTED
         distributed = world > 1 and name in SUPPORTED and not post_cs and model is None
     dist_ctx = None
+    if distributed and num_neighbors is not None:
+        raise NotImplementedError("num_neighbors is not implemented on the partitioned (distributed) route")
     if distributed and use_edge_weight:
         raise NotImplementedError("use_edge_weight=True is not implemented on the partitioned (distributed) route")
     if distributed and use_edge_attr:
@@ -469,6 +509,15 @@ def experiment(model_init_param: dict, *,
             raise ValueError("experiment(model=...): the module's forward must return a mapping with 'out' (log-"
                              "probabilities) and 'emb' (logits), as the models of this package do")
         del probe
+    sampler = None
+    if num_neighbors is not None:
+        # neighbour-sampled training: shapes change per batch (no capture), and a kept whole-graph aggregate must never
+        # reach a batch forward
+        from .sampler import NeighborSampler
+        sampler = NeighborSampler(data.edge_index, data.num_nodes, num_neighbors)
+        train_rows = train_mask.nonzero(as_tuple=True)[0]
+        cache_input_aggregate = False
+        use_hip_graph = False
     if cache_input_aggregate == "auto":  # memory guard: the kept aggregate is one more [N, F] fp32 matrix in HBM
         cache_input_aggregate = (device.type == "cuda" and name != "mlp" and dist_ctx is None  # partitioned: opt-in only
                                  and model is None
@@ -519,6 +568,49 @@ def experiment(model_init_param: dict, *,
     # prediction vectors), the full metrics once at the end: same return values, fewer syncs.
     loop_metrics = False
 
+    def sampled_epoch():
+        """An epoch on neighbour-sampled mini-batches (num_neighbors). Training: permute the training rows, cut them into
+        batches of batch_size seeds, and per batch sample, gather features and labels, run the training forward on the
+        batch's (x, edge_index), take the masked cross-entropy on the seed rows, backward, one optimizer step. Then the
+        full-graph eval forwards, as generic_epoch takes them on the GPU."""
+        from . import ops
+        from .graph import forget
+        from .models._stack import masked_ce, masked_ce_pair
+        net.train()
+        order = train_rows[torch.randperm(train_rows.numel(), device=device)]
+        sums = torch.zeros(3, dtype=torch.float64, device=device)  # loss * seeds, seeds, correct
+        for b0 in range(0, order.numel(), batch_size):
+            # (a slice of a permutation of in-range rows: distinct and in range by construction, no check and no read-back)
+            batch = sampler.sample_unchecked(order[b0:b0 + batch_size])
+            x_b = ops.gather_rows(features, batch.n_id.to(torch.int32))
+            y_b = y[batch.n_id]
+            seed_rows = torch.arange(batch.n_id.numel(), device=device) < batch.num_seeds
+            fwd_b = dict(fwd, x=x_b)
+            if "edge_index" in fwd_b:
+                fwd_b["edge_index"] = batch.edge_index
+            optimizer.zero_grad()
+            loss, stats = masked_ce(net, fwd_b, y_b, seed_rows)
+            if is_supergat:  # reference :431-432
+                loss = loss + supergat_graph_lambda * net.att_loss
+            loss.backward()
+            optimizer.step()
+            forget(batch.edge_index)  # the batch's CSRs are not met again: keep the whole graph's in the cache
+            sums += torch.stack([loss.detach().double() * stats[1], stats[1], stats[2]])
+        total_loss, seeds, hits = sums.tolist()  # the training side's one read-back of the epoch
+        hist["train_loss"].append(total_loss / seeds if seeds else float("nan"))
+        hist["train_acc"].append(hits / seeds if seeds else float("nan"))
+        net.eval()
+        with torch.no_grad():
+            if share_eval_forward:
+                st = masked_ce_pair(net, fwd, y, val_mask, test_mask)
+            else:
+                st = torch.stack([masked_ce(net, fwd, y, val_mask)[1], masked_ce(net, fwd, y, test_mask)[1]])
+        (vn, vc, vh), (sn, sc, sh) = st.tolist()
+        nan = float("nan")
+        hist["test_acc"].append(sh / sc if sc else nan)
+        hist["test_loss"].append(sn / sc if sc else nan)
+        return (vh / vc if vc else nan), (vn / vc if vc else nan), None
+
     def generic_epoch(i):
         """reference :427-440, :464-473: 1 train forward+backward, 2 eval forwards."""
         if runner is not None:  # the same epoch on the node partition; the five numbers are all-reduced over the ranks
@@ -535,6 +627,8 @@ def experiment(model_init_param: dict, *,
             hist["test_loss"].append(sl)
             hist["test_acc"].append(sa)
             return va, vl, None
+        if sampler is not None:
+            return sampled_epoch()
         net.train()
         optimizer.zero_grad()
         if device.type == "cuda":

@@ -4440,3 +4440,98 @@ def masked_nll_accuracy(logp, y, mask=None):
     logp = logp.detach()
     logp = logp if logp.stride(-1) == 1 else logp.contiguous()
     return _nll_stats(logp, y, mask, True)[0]
+
+
+# ---- neighbour sampling: fan-out mini-batches (csrc/sample.hip) -----------------------------------
+
+SAMPLE_STREAM = 0x082EFA98        # kStreamSample: the stream word of hop 0 (hop h: + h, modulo 2^32)
+SAMPLE_SHORT_ROW_SLOTS = 64       # rows up to here: 16 lanes per row
+SAMPLE_WAVE_ROW_SLOTS = 1024      # rows up to here: a wave per row; longer ones a workgroup per row
+
+
+def check_fanout(fanout):
+    """A fan-out is an int >= 1, or -1 for every slot (ValueError otherwise)."""
+    if isinstance(fanout, bool) or not isinstance(fanout, int) or fanout == 0 or fanout < -1:
+        raise ValueError(f"fan-out must be an int >= 1, or -1 for all neighbours; got {fanout!r}")
+    return fanout
+
+
+def sample_seed(device):
+    """Two 32-bit seed words on the device, from torch's device generator (as the attention dropouts take theirs)."""
+    return torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32, device=device)
+
+
+def _sample_workspace(n_rows, n_cand, N, device):
+    nbytes = ctypes.c_size_t(0)
+    _lib.call("rgbx_sample_workspace_bytes", n_rows, n_cand, N, ctypes.byref(nbytes))
+    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=device)
+
+
+def sample_hop_raw(csr, rows, fanout, seed, hop):
+    """One hop over `csr` for the int32 device vector `rows`: (rowptr int32 [n_rows + 1], col int32 [n_e], slot int32
+    [n_e]). One read-back: the hop's edge count (with the two row-length class counts, which decide the kernels)."""
+    n_rows, dev = rows.numel(), rows.device
+    head = torch.empty(n_rows + 3, dtype=torch.int32, device=dev)  # the row pointer, then the two class counts
+    ws = _sample_workspace(n_rows, 0, csr.N, dev)
+    _launch("sample_count", "rgbx_sample_count", csr.rowptr, csr.N, rows, n_rows, fanout, head, head[n_rows + 1:], ws,
+            ws.numel())
+    n_edges, n_wave, n_hub = head[n_rows:].tolist()
+    if n_edges < 0 or n_edges > csr.nnz:  # distinct rows keep at most every slot once
+        raise RuntimeError(f"sample_neighbors: {n_edges} sampled slots of {csr.nnz}: the rows are not distinct")
+    col = torch.empty(max(n_edges, 1), dtype=torch.int32, device=dev)  # (an empty tensor has no pointer to pass)
+    slot = torch.empty(max(n_edges, 1), dtype=torch.int32, device=dev)
+    classes = 1 | (2 if n_wave else 0) | (4 if n_hub else 0)
+    _launch("sample_pick", "rgbx_sample_pick", csr.rowptr, csr.col, csr.N, rows, n_rows, fanout, seed, hop, head, col, slot,
+            classes)
+    return head[:n_rows + 1], col[:n_edges], slot[:n_edges]
+
+
+def sample_neighbors(graph, rows, fanout, seed, hop):
+    """One hop of the neighbour sampler over `graph.fwd` (a graph.Graph in LOOPS_KEEP mode: nothing added, duplicate edges
+    are separate slots): row g of `rows` (distinct global ids, device) keeps min(fanout, deg) of its slots (fanout = -1:
+    all) — the ones with the smallest keys draw32(seed[0], seed[1], SAMPLE_STREAM + hop, g, t) << 32 | t — in ascending
+    slot order. Returns (rowptr int32 [n_rows + 1], col int32 [n_e] global source ids, slot int32 [n_e] CSR slots).
+    `seed`: two int32 words on the device. There is no CPU fallback."""
+    from .graph import LOOPS_KEEP
+    check_fanout(fanout)
+    if isinstance(hop, bool) or not isinstance(hop, int) or hop < 0:
+        raise ValueError(f"hop must be an int >= 0, got {hop!r}")
+    if getattr(graph, "is_distributed", False):
+        raise NotImplementedError("neighbour sampling on a partitioned graph is not implemented")
+    if graph.loops_mode != LOOPS_KEEP:
+        raise ValueError("sample_neighbors draws from the input edges: the graph must be built with LOOPS_KEEP")
+    _lib.require_device(rows, seed)
+    if rows.dim() != 1 or rows.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"rows must be a 1-D int32 / int64 tensor, got {rows.dtype} {tuple(rows.shape)}")
+    if seed.dtype != torch.int32 or seed.numel() != 2:
+        raise ValueError("seed must hold two int32 words")
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= graph.N):
+        raise ValueError(f"rows outside [0, {graph.N})")
+    return sample_hop_raw(graph.fwd, rows.to(torch.int32).contiguous(), fanout, seed.contiguous(), hop)
+
+
+def sample_frontier(cand, local_of, first_local):
+    """The distinct ids of `cand` (int32, device) that are not in the batch yet (local_of < 0), ascending: they get the
+    local ids first_local, first_local + 1, ... in `local_of` and are returned (int32). One read-back: their count."""
+    n, dev = cand.numel(), cand.device
+    new_ids = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = _sample_workspace(0, n, local_of.numel(), dev)
+    _launch("sample_frontier", "rgbx_sample_frontier", cand.data_ptr(), n, local_of, local_of.numel(), first_local, new_ids,
+            count, ws, ws.numel())
+    return new_ids[:int(count.item())]
+
+
+def sample_set_local(ids, first_local, local_of):
+    """local_of[ids[i]] = first_local + i; first_local = -1 resets them to -1 (touches len(ids) entries)."""
+    _launch("sample_local", "rgbx_sample_set_local", ids.data_ptr(), ids.numel(), first_local, local_of, local_of.numel())
+
+
+def sample_relabel(rowptr, col, slot, local_of, perm, first_row):
+    """A hop's edges in batch ids: (edge_index int64 [2, n_e] with source row 0 and target row 1, e_id int64 [n_e])."""
+    n_e, dev = col.numel(), col.device
+    ei = torch.empty((2, max(n_e, 1)), dtype=torch.int64, device=dev)
+    e_id = torch.empty(max(n_e, 1), dtype=torch.int64, device=dev)
+    _launch("sample_relabel", "rgbx_sample_relabel", rowptr, rowptr.numel() - 1, col.data_ptr(), slot.data_ptr(), n_e,
+            local_of, local_of.numel(), perm, first_row, ei[0], ei[1], e_id)
+    return ei[:, :n_e], e_id[:n_e]
