@@ -21,7 +21,7 @@
 // hub-row chunks in chunk order, the root term on the row's first chunk).
 #include <cmath>
 
-#include "attn_common.h"
+#include "edge_common.h"
 
 namespace rgbx {
 namespace {
@@ -335,30 +335,15 @@ cgconv_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ 
   }
 }
 
-// KERNEL<V, CHUNK, EDGE> over the rows and then, with a split plan, over the hub-row chunks. In the argument list
-// `n_items` is the pass's item count. Expects `vec`, `s`, `sd` and `split` in scope.
-#define RGBX_CGCONV_ROWS_E(KERNEL, E, n_rows, ...)                                   \
-  RGBX_VEC_SWITCH(vec, do {                                                          \
-    {                                                                                \
-      const int n_items = (int)(n_rows);                                             \
-      KERNEL<V, false, E><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);            \
-    }                                                                                \
-    if (sd.threshold > 0) {                                                          \
-      const int n_items = split->n_chunks;                                           \
-      KERNEL<V, true, E><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);             \
-    }                                                                                \
-  } while (0))
-
+// KERNEL<V, CHUNK, EDGE> through the shared ladder (edge_common.h), EDGE = the run-time `edge` as a constant.
 #define RGBX_CGCONV_ROWS(KERNEL, edge, n_rows, ...)                          \
   do {                                                                       \
-    if (edge) RGBX_CGCONV_ROWS_E(KERNEL, true, n_rows, __VA_ARGS__);         \
-    else RGBX_CGCONV_ROWS_E(KERNEL, false, n_rows, __VA_ARGS__);             \
+    if (edge) RGBX_EDGE_ROWS_X(KERNEL, (true), n_rows, __VA_ARGS__);         \
+    else RGBX_EDGE_ROWS_X(KERNEL, (false), n_rows, __VA_ARGS__);             \
   } while (0)
 
 int check_sizes(int64_t N, int C, int mean, const char* name) {
-  if (int rc = check_common(N, 1, C, name)) return rc;
-  if (!head_width_supported(C))
-    return fail(RGBX_E_SHAPE, "%s: %d channels (any C <= 64, even C <= 128, C %% 4 == 0 up to 256)", name, C);
+  if (int rc = check_sizes(N, C, name)) return rc;
   if (mean != 0 && mean != 1) return fail(RGBX_E_ARG, "%s: mean must be 0 or 1", name);
   return RGBX_OK;
 }

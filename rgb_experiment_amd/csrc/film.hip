@@ -16,7 +16,7 @@
 // z with the forward's own fmaf, so the relu mask is the forward's bit for bit (relu'(0) = 0). No float atomics, no
 // scratch, no LDS; every sum runs in a fixed order (slots of a lane group in slot order, lane groups by a butterfly,
 // hub-row chunks in chunk order), and every output row is written.
-#include "attn_common.h"
+#include "edge_common.h"
 
 namespace rgbx {
 namespace {
@@ -282,30 +282,12 @@ film_bwd_film_kernel(const int* __restrict__ rowptr_e, const int* __restrict__ c
   }
 }
 
-// The local row / chunk ladder: KERNEL<V, CHUNK, EXTRA...> over the rows and then, with a split plan, over the hub-row
-// chunks. In the argument list `n_items` is the pass's item count. Expects `vec`, `s`, `sd` and `split` in scope.
-#define RGBX_FILM_ROWS(KERNEL, TAIL, n_rows, ...)                                    \
-  RGBX_VEC_SWITCH(vec, do {                                                          \
-    {                                                                                \
-      const int n_items = (int)(n_rows);                                             \
-      KERNEL<V, false TAIL><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);          \
-    }                                                                                \
-    if (sd.threshold > 0) {                                                          \
-      const int n_items = split->n_chunks;                                           \
-      KERNEL<V, true TAIL><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);           \
-    }                                                                                \
-  } while (0))
-
-#define RGBX_FILM_COMMA ,
-
 int check_sizes(int64_t N, int R, int C, int act, const char* name) {
   if (R <= 0) return fail(RGBX_E_ARG, "%s: num_relations must be positive (got %d)", name, R);
   if (act != 0 && act != 1) return fail(RGBX_E_ARG, "%s: act must be 0 (identity) or 1 (relu), got %d", name, act);
   if (int rc = check_common(N, 1, C, name)) return rc;
   if (N * (int64_t)R >= INT32_MAX) return fail(RGBX_E_RANGE, "%s: N * R exceeds int32", name);
-  if (!head_width_supported(C))
-    return fail(RGBX_E_SHAPE, "%s: %d channels (any C <= 64, even C <= 128, C %% 4 == 0 up to 256)", name, C);
-  return RGBX_OK;
+  return check_width(C, name);
 }
 
 }  // namespace
@@ -338,11 +320,11 @@ extern "C" int rgbx_film_fwd_f32(const int32_t* rowptr, const int32_t* col, cons
   if (int rc = make_layout(1, C, vec, &L, "film_fwd")) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (etype)
-    RGBX_FILM_ROWS(film_fwd_kernel, RGBX_FILM_COMMA true, N, rowptr, col, etype, w, h, ldh, fb, ldfb, gofs, y0, ldy, out,
-                   ldo, n_items, R, mean, act, L, sd);
+    RGBX_EDGE_ROWS_X(film_fwd_kernel, (true), N, rowptr, col, etype, w, h, ldh, fb, ldfb, gofs, y0, ldy, out,
+                     ldo, n_items, R, mean, act, L, sd);
   else
-    RGBX_FILM_ROWS(film_fwd_kernel, RGBX_FILM_COMMA false, N, rowptr, col, etype, w, h, ldh, fb, ldfb, gofs, y0, ldy, out,
-                   ldo, n_items, R, mean, act, L, sd);
+    RGBX_EDGE_ROWS_X(film_fwd_kernel, (false), N, rowptr, col, etype, w, h, ldh, fb, ldfb, gofs, y0, ldy, out,
+                     ldo, n_items, R, mean, act, L, sd);
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(out, ldo, C, 0);  // a plain sum: the chunk partials added in chunk order
   RGBX_CHECK_LAUNCH("film_fwd_kernel");
   return RGBX_OK;
@@ -367,7 +349,7 @@ extern "C" int rgbx_film_bwd_src_f32(const int32_t* rowptr_x, const int32_t* col
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "film_bwd_src")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_FILM_ROWS(film_bwd_src_kernel, , N * R, rowptr_x, col_t, w_t, deg_rowptr, h, ldh, fb, ldfb, gofs, gout, ldg, g_h,
+  RGBX_EDGE_ROWS(film_bwd_src_kernel, N * R, rowptr_x, col_t, w_t, deg_rowptr, h, ldh, fb, ldfb, gofs, gout, ldg, g_h,
                  ldgh, n_items, R, act, L, sd);
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(g_h, ldgh, C, 0);
   RGBX_CHECK_LAUNCH("film_bwd_src_kernel");
@@ -394,7 +376,7 @@ extern "C" int rgbx_film_bwd_film_f32(const int32_t* rowptr_e, const int32_t* co
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "film_bwd_film")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_FILM_ROWS(film_bwd_film_kernel, , N * R, rowptr_e, col_e, h, ldh, fb, ldfb, gofs, gout, ldg, g_fb, ldgfb, n_items,
+  RGBX_EDGE_ROWS(film_bwd_film_kernel, N * R, rowptr_e, col_e, h, ldh, fb, ldfb, gofs, gout, ldg, g_fb, ldgfb, n_items,
                  R, mean, act, L, sd);
   if (sd.threshold > 0) {  // a chunk's record is (g_beta | g_gamma)
     RGBX_ATTN_BWD_COMBINE(g_fb, ldgfb, 2 * (int64_t)C, 0);

@@ -16,7 +16,7 @@
 // float32 add x[j,:] + e[p,:] (> 0; relu'(0) = 0). eps is read from DEVICE memory, so a captured launch follows a
 // parameter that an optimizer moves. No float atomics; every sum runs in a fixed order (slots of a lane group in slot
 // order, lane groups by a butterfly, hub-row chunks in chunk order, the root term on the row's first chunk).
-#include "attn_common.h"
+#include "edge_common.h"
 
 namespace rgbx {
 namespace {
@@ -99,7 +99,8 @@ gine_bwd_edge_kernel(const int* __restrict__ rowptr, const int* __restrict__ col
                      int64_t ldg, float* __restrict__ g_e, int64_t ldge, int N, const GatLayout L,
                      const AttnSplit sp) {
   constexpr int U = 4;
-  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
+  const LaneCoords lc = lane_coords<VEC>(L);
+  const int lane = lc.lane, NG = lc.NG, g = lc.g, ch = lc.ch, wpb = lc.wpb;
   const bool active = ch < L.C;
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
@@ -111,34 +112,20 @@ gine_bwd_edge_kernel(const int* __restrict__ rowptr, const int* __restrict__ col
     for (int i = 0; i < VEC; ++i) go[i] = 0.f;
     if (active) load_vec<VEC>(go, gout + (int64_t)row * ldg + ch);
 
-    for (int base = start; base < end; base += kWave) {
-      const int n = min(kWave, end - base);
-      const int mycol = lane < n ? col[base + lane] : 0;
-      for (int k = 0; k < n; k += NG * U) {
-        float xv[U][VEC], ev[U][VEC];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int idx = k + u * NG + g;
-          const int src = __shfl(mycol, idx & 63);
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) xv[u][i] = ev[u][i] = 0.f;
-          if (active && idx < n) {
-            load_vec<VEC>(xv[u], x + (int64_t)src * ldx + ch);
-            load_vec<VEC>(ev[u], e + (int64_t)(base + idx) * lde + ch);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int idx = k + u * NG + g;
-          if (active && idx < n) {
+    walk_slots<U, 2, VEC>(
+        col, start, end, lane, NG, g, active,
+        [&](float (&f)[2][VEC], int src, int slot) {
+          load_vec<VEC>(f[0], x + (int64_t)src * ldx + ch);
+          load_vec<VEC>(f[1], e + (int64_t)slot * lde + ch);
+        },
+        [&](const float (&f)[2][VEC], int slot, bool ok) {
+          if (ok) {
             float ge[VEC];
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) ge[i] = xv[u][i] + ev[u][i] > 0.f ? go[i] : 0.f;
-            store_vec<VEC>(g_e + (int64_t)(base + idx) * ldge + ch, ge);
+            for (int i = 0; i < VEC; ++i) ge[i] = f[0][i] + f[1][i] > 0.f ? go[i] : 0.f;
+            store_vec<VEC>(g_e + (int64_t)slot * ldge + ch, ge);
           }
-        }
-      }
-    }
+        });
   }
 }
 
@@ -205,27 +192,6 @@ gine_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict__ co
   }
 }
 
-// KERNEL<V, CHUNK> over the rows and then, with a split plan, over the hub-row chunks. In the argument list `n_items` is
-// the pass's item count. Expects `vec`, `s`, `sd` and `split` in scope.
-#define RGBX_GINE_ROWS(KERNEL, n_rows, ...)                                          \
-  RGBX_VEC_SWITCH(vec, do {                                                          \
-    {                                                                                \
-      const int n_items = (int)(n_rows);                                             \
-      KERNEL<V, false><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);               \
-    }                                                                                \
-    if (sd.threshold > 0) {                                                          \
-      const int n_items = split->n_chunks;                                           \
-      KERNEL<V, true><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);                \
-    }                                                                                \
-  } while (0))
-
-int check_sizes(int64_t N, int C, const char* name) {
-  if (int rc = check_common(N, 1, C, name)) return rc;
-  if (!head_width_supported(C))
-    return fail(RGBX_E_SHAPE, "%s: %d channels (any C <= 64, even C <= 128, C %% 4 == 0 up to 256)", name, C);
-  return RGBX_OK;
-}
-
 }  // namespace
 }  // namespace rgbx
 
@@ -247,7 +213,7 @@ extern "C" int rgbx_gine_fwd_f32(const int32_t* rowptr, const int32_t* col, cons
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "gine_fwd")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_GINE_ROWS(gine_fwd_kernel, N, rowptr, col, x, ldx, e, lde, eps, out, ldo, n_items, L, sd);
+  RGBX_EDGE_ROWS(gine_fwd_kernel, N, rowptr, col, x, ldx, e, lde, eps, out, ldo, n_items, L, sd);
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(out, ldo, C, 0);  // a plain sum: the chunk partials added in chunk order
   RGBX_CHECK_LAUNCH("gine_fwd_kernel");
   return RGBX_OK;
@@ -269,7 +235,7 @@ extern "C" int rgbx_gine_bwd_edge_f32(const int32_t* rowptr, const int32_t* col,
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "gine_bwd_edge")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_GINE_ROWS(gine_bwd_edge_kernel, N, rowptr, col, x, ldx, e, lde, gout, ldg, g_e, ldge, n_items, L, sd);
+  RGBX_EDGE_ROWS(gine_bwd_edge_kernel, N, rowptr, col, x, ldx, e, lde, gout, ldg, g_e, ldge, n_items, L, sd);
   RGBX_CHECK_LAUNCH("gine_bwd_edge_kernel");
   return RGBX_OK;
 }
@@ -290,7 +256,7 @@ extern "C" int rgbx_gine_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "gine_bwd_src")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_GINE_ROWS(gine_bwd_src_kernel, N, rowptr_t, col_t, t2f, x, ldx, e, lde, gout, ldg, eps, g_x, ldgx, n_items, L,
+  RGBX_EDGE_ROWS(gine_bwd_src_kernel, N, rowptr_t, col_t, t2f, x, ldx, e, lde, gout, ldg, eps, g_x, ldgx, n_items, L,
                  sd);
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(g_x, ldgx, C, 0);
   RGBX_CHECK_LAUNCH("gine_bwd_src_kernel");

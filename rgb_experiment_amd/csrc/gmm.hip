@@ -19,7 +19,7 @@
 // lane groups and then the heads of a group by a butterfly, the head chunks in ascending order, the hub-row chunks in
 // chunk order (y0 rides on a row's first chunk); the parameter gradients by slot ranges of a fixed length, the ranges
 // in ascending order.
-#include "attn_common.h"
+#include "edge_common.h"
 
 namespace rgbx {
 namespace {
@@ -397,20 +397,6 @@ gmm_degree_pseudo_kernel(const int* __restrict__ rowptr, const int* __restrict__
   }
 }
 
-// KERNEL<V, CHUNK> over the rows and then, with a split plan, over the hub-row chunks. In the argument list `n_items` is
-// the pass's item count. Expects `vec`, `s`, `sd` and `split` in scope.
-#define RGBX_GMM_ROWS(KERNEL, n_rows, ...)                                           \
-  RGBX_VEC_SWITCH(vec, do {                                                          \
-    {                                                                                \
-      const int n_items = (int)(n_rows);                                             \
-      KERNEL<V, false><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);               \
-    }                                                                                \
-    if (sd.threshold > 0) {                                                          \
-      const int n_items = split->n_chunks;                                           \
-      KERNEL<V, true><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);                \
-    }                                                                                \
-  } while (0))
-
 bool gmm_supported(int64_t K, int64_t M, int64_t D) {
   return K > 0 && K <= kMaxKernels && head_width_supported(M) && D > 0 && D <= kMaxDim;
 }
@@ -461,7 +447,7 @@ extern "C" int rgbx_gmm_fwd_f32(const int32_t* rowptr, const int32_t* col, const
   if (int rc = make_layout(K, M, vec, &L, "gmm_fwd")) return rc;
   if (int rc = make_layout(1, M, vec, &L1, "gmm_fwd")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_GMM_ROWS(gmm_fwd_kernel, N, rowptr, col, e, lde, mu, sigma, rs, h, ldh, y0, ldy, out, ldo, n_items, D, L, sd);
+  RGBX_EDGE_ROWS(gmm_fwd_kernel, N, rowptr, col, e, lde, mu, sigma, rs, h, ldh, y0, ldy, out, ldo, n_items, D, L, sd);
   if (sd.threshold > 0)  // a plain sum of one-head rows: the chunk partials added in chunk order
     RGBX_VEC_SWITCH(vec, attn_bwd_combine_kernel<V><<<row_grid(split->n_long), 256, 0, s>>>(
                              split->n_long, split->long_row, split->long_chunk_ptr, out, ldo, M, 0, L1, sd));
@@ -490,8 +476,8 @@ extern "C" int rgbx_gmm_bwd_src_f32(const int32_t* rowptr_t, const int32_t* col_
   GatLayout L;
   if (int rc = make_layout(K, M, vec, &L, "gmm_bwd_src")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_GMM_ROWS(gmm_bwd_src_kernel, N, rowptr_t, col_t, t2f, w_t, e, lde, mu, sigma, gout, ldg, g_h, ldgh, n_items, D, L,
-                sd);
+  RGBX_EDGE_ROWS(gmm_bwd_src_kernel, N, rowptr_t, col_t, t2f, w_t, e, lde, mu, sigma, gout, ldg, g_h, ldgh, n_items, D, L,
+                 sd);
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(g_h, ldgh, F, 0);
   RGBX_CHECK_LAUNCH("gmm_bwd_src_kernel");
   return RGBX_OK;
@@ -546,7 +532,7 @@ extern "C" int rgbx_gmm_bwd_edge_f32(const int32_t* rowptr, const int32_t* col, 
   if (int rc = make_layout(K, M, vec, &L, "gmm_bwd_edge")) return rc;
   float* s_tab = static_cast<float*>(workspace);
   float* part = s_tab + (size_t)nnz * K;
-  RGBX_GMM_ROWS(gmm_bwd_edge_kernel, N, rowptr, col, e, lde, mu, sigma, rs, h, ldh, gout, ldg, s_tab, n_items, D, L, sd);
+  RGBX_EDGE_ROWS(gmm_bwd_edge_kernel, N, rowptr, col, e, lde, mu, sigma, rs, h, ldh, gout, ldg, s_tab, n_items, D, L, sd);
   if (g_e)
     gmm_edge_attr_kernel<<<capped_grid(nnz, 256), 256, 0, s>>>(s_tab, e, lde, mu, sigma, g_e, ldge, nnz, K, D);
   if (g_mu) {

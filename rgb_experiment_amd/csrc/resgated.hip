@@ -15,7 +15,7 @@
 // groups by a butterfly, hub-row chunks in chunk order).
 #include <cmath>
 
-#include "attn_common.h"
+#include "edge_common.h"
 
 namespace rgbx {
 namespace {
@@ -36,7 +36,8 @@ resgated_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                     int64_t ldk, const float* __restrict__ qx, int64_t ldq, const float* __restrict__ vx, int64_t ldv,
                     float* __restrict__ out, int64_t ldo, int N, const GatLayout L, const AttnSplit sp) {
   constexpr int U = 4;  // neighbour rows in flight per lane group (q and v each)
-  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
+  const LaneCoords lc = lane_coords<VEC>(L);
+  const int lane = lc.lane, NG = lc.NG, g = lc.g, ch = lc.ch, wpb = lc.wpb, F = lc.F;
   const bool active = ch < L.C;  // H = 1: the group is the head, t / LPH = 0
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
@@ -47,29 +48,16 @@ resgated_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
     for (int i = 0; i < VEC; ++i) ki[i] = acc[i] = 0.f;
     if (active) load_vec<VEC>(ki, kx + (int64_t)row * ldk + ch);
 
-    for (int base = start; base < end; base += kWave) {
-      const int n = min(kWave, end - base);
-      const int mycol = lane < n ? col[base + lane] : 0;
-      for (int k = 0; k < n; k += NG * U) {
-        float qv[U][VEC], vv[U][VEC];
+    walk_slots<U, 2, VEC>(
+        col, start, end, lane, NG, g, active,
+        [&](float (&f)[2][VEC], int src, int) {
+          load_vec<VEC>(f[0], qx + (int64_t)src * ldq + ch);
+          load_vec<VEC>(f[1], vx + (int64_t)src * ldv + ch);
+        },
+        [&](const float (&f)[2][VEC], int, bool) {  // a slot past the row's end holds v = 0: its (finite) gate adds nothing
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int idx = k + u * NG + g;
-          const int src = __shfl(mycol, idx & 63);
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) qv[u][i] = vv[u][i] = 0.f;
-          if (active && idx < n) {
-            load_vec<VEC>(qv[u], qx + (int64_t)src * ldq + ch);
-            load_vec<VEC>(vv[u], vx + (int64_t)src * ldv + ch);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {  // a slot past the row's end holds v = 0: its (finite) gate adds nothing
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) acc[i] = fmaf(gate(ki[i] + qv[u][i]), vv[u][i], acc[i]);
-        }
-      }
-    }
+          for (int i = 0; i < VEC; ++i) acc[i] = fmaf(gate(ki[i] + f[0][i]), f[1][i], acc[i]);
+        });
     groups_sum<VEC>(acc, L.G);
     if (g == 0 && active) {
       if constexpr (CHUNK) store_vec<VEC>(sp.pacc + (int64_t)item * F + ch, acc);
@@ -92,7 +80,8 @@ resgated_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ 
                         int64_t ldv, const float* __restrict__ gout, int64_t ldg, float* __restrict__ g_k,
                         int64_t ldgk, int N, const GatLayout L, const AttnSplit sp) {
   constexpr int U = 4;
-  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
+  const LaneCoords lc = lane_coords<VEC>(L);
+  const int lane = lc.lane, NG = lc.NG, g = lc.g, ch = lc.ch, wpb = lc.wpb, F = lc.F;
   const bool active = ch < L.C;
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
@@ -103,32 +92,19 @@ resgated_bwd_dst_kernel(const int* __restrict__ rowptr, const int* __restrict__ 
     for (int i = 0; i < VEC; ++i) ki[i] = acc[i] = 0.f;
     if (active) load_vec<VEC>(ki, kx + (int64_t)row * ldk + ch);
 
-    for (int base = start; base < end; base += kWave) {
-      const int n = min(kWave, end - base);
-      const int mycol = lane < n ? col[base + lane] : 0;
-      for (int k = 0; k < n; k += NG * U) {
-        float qv[U][VEC], vv[U][VEC];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int idx = k + u * NG + g;
-          const int src = __shfl(mycol, idx & 63);
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) qv[u][i] = vv[u][i] = 0.f;
-          if (active && idx < n) {
-            load_vec<VEC>(qv[u], qx + (int64_t)src * ldq + ch);
-            load_vec<VEC>(vv[u], vx + (int64_t)src * ldv + ch);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
+    walk_slots<U, 2, VEC>(
+        col, start, end, lane, NG, g, active,
+        [&](float (&f)[2][VEC], int src, int) {
+          load_vec<VEC>(f[0], qx + (int64_t)src * ldq + ch);
+          load_vec<VEC>(f[1], vx + (int64_t)src * ldv + ch);
+        },
+        [&](const float (&f)[2][VEC], int, bool) {
 #pragma unroll
           for (int i = 0; i < VEC; ++i) {
-            const float s = gate(ki[i] + qv[u][i]);
-            acc[i] = fmaf(s * (1.f - s), vv[u][i], acc[i]);
+            const float s = gate(ki[i] + f[0][i]);
+            acc[i] = fmaf(s * (1.f - s), f[1][i], acc[i]);
           }
-        }
-      }
-    }
+        });
     groups_sum<VEC>(acc, L.G);
     if (g == 0 && active) {
       float go[VEC];
@@ -152,7 +128,8 @@ resgated_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict_
                         int64_t ldgq, float* __restrict__ g_v, int64_t ldgv, int N, const GatLayout L,
                         const AttnSplit sp) {
   constexpr int U = 4;
-  const auto [lane, NG, g, t, hl, ch, wpb, F] = lane_coords<VEC>(L);
+  const LaneCoords lc = lane_coords<VEC>(L);
+  const int lane = lc.lane, NG = lc.NG, g = lc.g, ch = lc.ch, wpb = lc.wpb, F = lc.F;
   const bool active = ch < L.C;
 
   for (int item = blockIdx.x * wpb + (threadIdx.x >> 6); item < N; item += gridDim.x * wpb) {
@@ -163,33 +140,20 @@ resgated_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict_
     for (int i = 0; i < VEC; ++i) qj[i] = aq[i] = av[i] = 0.f;
     if (active) load_vec<VEC>(qj, qx + (int64_t)row * ldq + ch);
 
-    for (int base = start; base < end; base += kWave) {
-      const int n = min(kWave, end - base);
-      const int mycol = lane < n ? col_t[base + lane] : 0;
-      for (int k = 0; k < n; k += NG * U) {
-        float kv[U][VEC], go[U][VEC];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int idx = k + u * NG + g;
-          const int tgt = __shfl(mycol, idx & 63);
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) kv[u][i] = go[u][i] = 0.f;
-          if (active && idx < n) {
-            load_vec<VEC>(kv[u], kx + (int64_t)tgt * ldk + ch);
-            load_vec<VEC>(go[u], gout + (int64_t)tgt * ldg + ch);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {  // a slot past the row's end holds gout = 0
+    walk_slots<U, 2, VEC>(
+        col_t, start, end, lane, NG, g, active,
+        [&](float (&f)[2][VEC], int tgt, int) {
+          load_vec<VEC>(f[0], kx + (int64_t)tgt * ldk + ch);
+          load_vec<VEC>(f[1], gout + (int64_t)tgt * ldg + ch);
+        },
+        [&](const float (&f)[2][VEC], int, bool) {  // a slot past the row's end holds gout = 0
 #pragma unroll
           for (int i = 0; i < VEC; ++i) {
-            const float s = gate(kv[u][i] + qj[i]);
-            aq[i] = fmaf(s * (1.f - s), go[u][i], aq[i]);
-            av[i] = fmaf(s, go[u][i], av[i]);
+            const float s = gate(f[0][i] + qj[i]);
+            aq[i] = fmaf(s * (1.f - s), f[1][i], aq[i]);
+            av[i] = fmaf(s, f[1][i], av[i]);
           }
-        }
-      }
-    }
+        });
     groups_sum<VEC>(aq, L.G);
     groups_sum<VEC>(av, L.G);
     if (g == 0 && active) {
@@ -206,28 +170,6 @@ resgated_bwd_src_kernel(const int* __restrict__ rowptr_t, const int* __restrict_
       }
     }
   }
-}
-
-// KERNEL<V, CHUNK> over the rows and then, with a split plan, over the hub-row chunks (RGBX_ATTN_ROWS without the
-// training form: there is no dropout here). In the argument list `n_items` is the pass's item count. Expects `vec`,
-// `s`, `sd` and `split` in scope.
-#define RGBX_RESGATED_ROWS(KERNEL, n_rows, ...)                                      \
-  RGBX_VEC_SWITCH(vec, do {                                                          \
-    {                                                                                \
-      const int n_items = (int)(n_rows);                                             \
-      KERNEL<V, false><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);               \
-    }                                                                                \
-    if (sd.threshold > 0) {                                                          \
-      const int n_items = split->n_chunks;                                           \
-      KERNEL<V, true><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);                \
-    }                                                                                \
-  } while (0))
-
-int check_sizes(int64_t N, int C, const char* name) {
-  if (int rc = check_common(N, 1, C, name)) return rc;
-  if (!head_width_supported(C))
-    return fail(RGBX_E_SHAPE, "%s: %d channels (any C <= 64, even C <= 128, C %% 4 == 0 up to 256)", name, C);
-  return RGBX_OK;
 }
 
 }  // namespace
@@ -252,7 +194,7 @@ extern "C" int rgbx_resgated_fwd_f32(const int32_t* rowptr, const int32_t* col, 
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "resgated_fwd")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_RESGATED_ROWS(resgated_fwd_kernel, N, rowptr, col, k, ldk, q, ldq, v, ldv, out, ldo, n_items, L, sd);
+  RGBX_EDGE_ROWS(resgated_fwd_kernel, N, rowptr, col, k, ldk, q, ldq, v, ldv, out, ldo, n_items, L, sd);
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(out, ldo, C, 0);  // a plain sum: the chunk partials added in chunk order
   RGBX_CHECK_LAUNCH("resgated_fwd_kernel");
   return RGBX_OK;
@@ -275,8 +217,8 @@ extern "C" int rgbx_resgated_bwd_dst_f32(const int32_t* rowptr, const int32_t* c
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "resgated_bwd_dst")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_RESGATED_ROWS(resgated_bwd_dst_kernel, N, rowptr, col, k, ldk, q, ldq, v, ldv, gout, ldg, g_k, ldgk, n_items, L,
-                     sd);
+  RGBX_EDGE_ROWS(resgated_bwd_dst_kernel, N, rowptr, col, k, ldk, q, ldq, v, ldv, gout, ldg, g_k, ldgk, n_items, L,
+                 sd);
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(g_k, ldgk, C, 0);
   RGBX_CHECK_LAUNCH("resgated_bwd_dst_kernel");
   return RGBX_OK;
@@ -300,8 +242,8 @@ extern "C" int rgbx_resgated_bwd_src_f32(const int32_t* rowptr_t, const int32_t*
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "resgated_bwd_src")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_RESGATED_ROWS(resgated_bwd_src_kernel, N, rowptr_t, col_t, k, ldk, q, ldq, v, ldv, gout, ldg, g_q, ldgq, g_v,
-                     ldgv, n_items, L, sd);
+  RGBX_EDGE_ROWS(resgated_bwd_src_kernel, N, rowptr_t, col_t, k, ldk, q, ldq, v, ldv, gout, ldg, g_q, ldgq, g_v,
+                 ldgv, n_items, L, sd);
   if (sd.threshold > 0) {  // a chunk's record is (g_q | g_v)
     RGBX_ATTN_BWD_COMBINE(g_q, ldgq, 2 * (int64_t)C, 0);
     RGBX_ATTN_BWD_COMBINE(g_v, ldgv, 2 * (int64_t)C, C);

@@ -16,7 +16,7 @@
 // Nothing per edge passes between forward and backward. No float atomics, no scratch, no LDS; every sum runs in a
 // fixed order: the slots of a lane group in slot order, the lane groups and then the heads of a group by a butterfly,
 // the head chunks in ascending order, the hub-row chunks in chunk order (y0 rides on a row's first chunk).
-#include "attn_common.h"
+#include "edge_common.h"
 
 namespace rgbx {
 namespace {
@@ -250,20 +250,6 @@ rgcn_mix_bwd_coef_kernel(const int* __restrict__ rowptr, const int* __restrict__
   }
 }
 
-// KERNEL<V, CHUNK> over the rows and then, with a split plan, over the hub-row chunks. In the argument list `n_items` is
-// the pass's item count. Expects `vec`, `s`, `sd` and `split` in scope.
-#define RGBX_RGCN_ROWS(KERNEL, n_rows, ...)                                          \
-  RGBX_VEC_SWITCH(vec, do {                                                          \
-    {                                                                                \
-      const int n_items = (int)(n_rows);                                             \
-      KERNEL<V, false><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);               \
-    }                                                                                \
-    if (sd.threshold > 0) {                                                          \
-      const int n_items = split->n_chunks;                                           \
-      KERNEL<V, true><<<row_grid(n_items), 256, 0, s>>>(__VA_ARGS__);                \
-    }                                                                                \
-  } while (0))
-
 bool mix_supported(int64_t B, int64_t C) { return B > 0 && B <= kMaxBases && head_width_supported(C); }
 
 int check_sizes(int64_t N, int R, int B, int C, const char* name) {
@@ -319,7 +305,7 @@ extern "C" int rgbx_rgcn_mix_fwd_f32(const int32_t* rowptr, const int32_t* col, 
   if (int rc = make_layout(B, C, vec, &L, "rgcn_mix_fwd")) return rc;
   if (int rc = make_layout(1, C, vec, &L1, "rgcn_mix_fwd")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_RGCN_ROWS(rgcn_mix_fwd_kernel, N, rowptr, col, etype, w, comp, h, ldh, y0, ldy, out, ldo, n_items, L, sd);
+  RGBX_EDGE_ROWS(rgcn_mix_fwd_kernel, N, rowptr, col, etype, w, comp, h, ldh, y0, ldy, out, ldo, n_items, L, sd);
   if (sd.threshold > 0)  // a plain sum of one-head rows: the chunk partials added in chunk order
     RGBX_VEC_SWITCH(vec, attn_bwd_combine_kernel<V><<<row_grid(split->n_long), 256, 0, s>>>(
                              split->n_long, split->long_row, split->long_chunk_ptr, out, ldo, C, 0, L1, sd));
@@ -347,7 +333,7 @@ extern "C" int rgbx_rgcn_mix_bwd_src_f32(const int32_t* rowptr_t, const int32_t*
   GatLayout L;
   if (int rc = make_layout(B, C, vec, &L, "rgcn_mix_bwd_src")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_RGCN_ROWS(rgcn_mix_bwd_src_kernel, N, rowptr_t, col_t, etype_t, w_t, comp, gout, ldg, g_h, ldgh, n_items, L, sd);
+  RGBX_EDGE_ROWS(rgcn_mix_bwd_src_kernel, N, rowptr_t, col_t, etype_t, w_t, comp, gout, ldg, g_h, ldgh, n_items, L, sd);
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(g_h, ldgh, F, 0);
   RGBX_CHECK_LAUNCH("rgcn_mix_bwd_src_kernel");
   return RGBX_OK;
@@ -368,7 +354,7 @@ extern "C" int rgbx_rgcn_mix_bwd_coef_f32(const int32_t* rowptr, const int32_t* 
   GatLayout L;
   if (int rc = make_layout(B, C, vec, &L, "rgcn_mix_bwd_coef")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_RGCN_ROWS(rgcn_mix_bwd_coef_kernel, N, rowptr, col, w, h, ldh, gout, ldg, d, n_items, L, sd);
+  RGBX_EDGE_ROWS(rgcn_mix_bwd_coef_kernel, N, rowptr, col, w, h, ldh, gout, ldg, d, n_items, L, sd);
   RGBX_CHECK_LAUNCH("rgcn_mix_bwd_coef_kernel");
   return RGBX_OK;
 }

@@ -19,7 +19,7 @@
 // chunks in chunk order, g_t's records in record order).
 #include <cmath>
 
-#include "attn_common.h"
+#include "edge_common.h"
 
 namespace rgbx {
 namespace {
@@ -291,32 +291,6 @@ int64_t gt_records(int64_t N, const rgbx_row_split_t* split) {
   return gt_grid(N) + (split && split->threshold > 0 && split->n_chunks > 0 ? gt_grid(split->n_chunks) : 0);
 }
 
-int check_sizes(int64_t N, int C, const char* name) {
-  if (int rc = check_common(N, 1, C, name)) return rc;
-  if (!head_width_supported(C))
-    return fail(RGBX_E_SHAPE, "%s: %d channels (any C <= 64, even C <= 128, C %% 4 == 0 up to 256)", name, C);
-  return RGBX_OK;
-}
-
-// KERNEL<V, CHUNK, ...> over the rows and then, with a split plan, over the hub-row chunks, each on GRID(items)
-// workgroups. In the argument list `n_items` is the pass's item count and `chunk_pass` tells the two passes apart.
-// Expects `s`, `sd` and `split` in scope.
-#define RGBX_SOFTMAX_AGGR_ROWS(GRID, n_rows, LAUNCH_ROW, LAUNCH_CHUNK, ...) \
-  do {                                                                      \
-    {                                                                       \
-      const int n_items = (int)(n_rows);                                    \
-      constexpr bool chunk_pass = false;                                    \
-      (void)chunk_pass;                                                     \
-      LAUNCH_ROW<<<GRID(n_items), 256, 0, s>>>(__VA_ARGS__);                \
-    }                                                                       \
-    if (sd.threshold > 0) {                                                 \
-      const int n_items = split->n_chunks;                                  \
-      constexpr bool chunk_pass = true;                                     \
-      (void)chunk_pass;                                                     \
-      LAUNCH_CHUNK<<<GRID(n_items), 256, 0, s>>>(__VA_ARGS__);              \
-    }                                                                       \
-  } while (0)
-
 }  // namespace
 }  // namespace rgbx
 
@@ -347,9 +321,7 @@ extern "C" int rgbx_softmax_aggr_fwd_f32(const int32_t* rowptr, const int32_t* c
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "softmax_aggr_fwd")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  RGBX_VEC_SWITCH(vec, RGBX_SOFTMAX_AGGR_ROWS(row_grid, N, (softmax_aggr_fwd_kernel<V, false>),
-                                              (softmax_aggr_fwd_kernel<V, true>), rowptr, col, m, ldm, t, t_stride, out,
-                                              ldo, lse, ldl, n_items, L, sd));
+  RGBX_EDGE_ROWS(softmax_aggr_fwd_kernel, N, rowptr, col, m, ldm, t, t_stride, out, ldo, lse, ldl, n_items, L, sd);
   if (sd.threshold > 0)
     RGBX_VEC_SWITCH(vec, softmax_aggr_fwd_combine_kernel<V><<<row_grid(split->n_long), 256, 0, s>>>(
                              split->n_long, split->long_row, split->long_chunk_ptr, out, ldo, lse, ldl, L, sd));
@@ -385,17 +357,15 @@ extern "C" int rgbx_softmax_aggr_bwd_f32(const int32_t* rowptr_t, const int32_t*
                       : pick_vec(C, {m, out, lse, gout, g_m, sd.pacc}, {ldm, ldo, ldl, ldg, ldgm});
   GatLayout L;
   if (int rc = make_layout(1, C, vec, &L, "softmax_aggr_bwd")) return rc;
-  if (g_t) {
+  if (g_t) {  // one g_t record per workgroup: the capped grid, the chunk pass's records behind the row pass's
     const int grid = gt_grid(N);
-    RGBX_VEC_SWITCH(vec, RGBX_SOFTMAX_AGGR_ROWS(gt_grid, N, (softmax_aggr_bwd_kernel<V, false, true>),
-                                                (softmax_aggr_bwd_kernel<V, true, true>), rowptr_t, col_t, m, ldm, t,
-                                                t_stride, out, ldo, lse, ldl, gout, ldg, g_m, ldgm,
-                                                gt_partial + (chunk_pass ? (int64_t)grid * C : 0), n_items, L, sd));
+    RGBX_VEC_SWITCH(vec, RGBX_EDGE_LAUNCH(gt_grid, N, (softmax_aggr_bwd_kernel<V, false, true>),
+                                          (softmax_aggr_bwd_kernel<V, true, true>), rowptr_t, col_t, m, ldm, t,
+                                          t_stride, out, ldo, lse, ldl, gout, ldg, g_m, ldgm,
+                                          gt_partial + (chunk_pass ? (int64_t)grid * C : 0), n_items, L, sd));
   } else {
-    RGBX_VEC_SWITCH(vec, RGBX_SOFTMAX_AGGR_ROWS(row_grid, N, (softmax_aggr_bwd_kernel<V, false, false>),
-                                                (softmax_aggr_bwd_kernel<V, true, false>), rowptr_t, col_t, m, ldm, t,
-                                                t_stride, out, ldo, lse, ldl, gout, ldg, g_m, ldgm, nullptr, n_items, L,
-                                                sd));
+    RGBX_EDGE_ROWS_X(softmax_aggr_bwd_kernel, (false), N, rowptr_t, col_t, m, ldm, t, t_stride, out, ldo, lse, ldl,
+                     gout, ldg, g_m, ldgm, nullptr, n_items, L, sd);
   }
   if (sd.threshold > 0) RGBX_ATTN_BWD_COMBINE(g_m, ldgm, C, 0);  // the chunk partials added in chunk order
   RGBX_CHECK_LAUNCH("softmax_aggr_bwd_kernel");

@@ -3481,7 +3481,7 @@ def rgcn_mix_supported(B, C):
     return bool(_lib.load().rgbx_rgcn_mix_supported(B, C))
 
 
-_RGCN_AGGRS = {"mean": "mean", "add": "add", "sum": "add"}
+_EDGE_AGGRS = {"mean": "mean", "add": "add", "sum": "add"}  # what rgcn / film / gmm_aggregate take as `aggr`
 
 
 def rgcn_aggregate(h, graph, edge_type, num_relations, comp=None, aggr="mean", y0=None):
@@ -3502,9 +3502,9 @@ def rgcn_aggregate(h, graph, edge_type, num_relations, comp=None, aggr="mean", y
     rgcn_mix_bwd_src, rgcn_mix_bwd_coef, rgcn_comp_reduce."""
     if _is_dist(graph):
         raise RuntimeError("RGCNConv has no node-partitioned form: run it on one GPU")
-    if aggr not in _RGCN_AGGRS:
+    if aggr not in _EDGE_AGGRS:
         raise ValueError(f"rgcn_aggregate: aggr={aggr!r} (mean, add or sum)")
-    aggr = _RGCN_AGGRS[aggr]
+    aggr = _EDGE_AGGRS[aggr]
     R = int(num_relations)
     N = graph.fwd.N
     heads = R if comp is None else (comp.size(1) if comp.dim() == 2 else -1)
@@ -3532,7 +3532,6 @@ def rgcn_aggregate(h, graph, edge_type, num_relations, comp=None, aggr="mean", y
 
 # ---- FiLMConv: the target modulates every message per channel, before the nonlinearity ---------------------------------
 
-_FILM_AGGRS = {"mean": "mean", "add": "add", "sum": "add"}
 _FILM_ACTS = {"relu": 1, "identity": 0, None: 0}  # the kernels' `act`
 FILM_BLOCK = 256  # wider inputs run as column blocks of this many channels
 
@@ -3633,14 +3632,14 @@ def film_aggregate(h, fb, graph, edge_type=None, num_relations=1, aggr="mean", a
     from .graph import LOOPS_KEEP
     if _is_dist(graph):
         raise RuntimeError("FiLMConv has no node-partitioned form: run it on one GPU")
-    if aggr not in _FILM_AGGRS:
+    if aggr not in _EDGE_AGGRS:
         raise ValueError(f"film_aggregate: aggr={aggr!r} (mean, add or sum)")
     if not (act is None or isinstance(act, str)) or act not in _FILM_ACTS:
         raise ValueError(f"film_aggregate: act={act!r} (relu, identity or None)")
     if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
         raise RuntimeError("film_aggregate: only a graph in mode LOOPS_KEEP takes the edges as given "
                            f"(got loops_mode={getattr(graph, 'loops_mode', None)!r})")
-    mean, act = int(_FILM_AGGRS[aggr] == "mean"), _FILM_ACTS[act]
+    mean, act = int(_EDGE_AGGRS[aggr] == "mean"), _FILM_ACTS[act]
     R = int(num_relations)
     if R <= 0:
         raise ValueError(f"film_aggregate: num_relations must be positive, got {num_relations}")
@@ -3747,9 +3746,6 @@ def gmm_supported(K, M, D):
     return bool(_lib.load().rgbx_gmm_supported(K, M, D))
 
 
-_GMM_AGGRS = {"mean": "mean", "add": "add", "sum": "add"}
-
-
 def gmm_aggregate(h, e_slot, mu, sigma, graph, aggr="mean", y0=None):
     """GMMConv's aggregation (MoNet; separate_gaussians=False) over a LOOPS_KEEP graph, the edges as given: self-loops
     stay, duplicates count twice. h [N, K * M] = x @ g, k-major columns (h.view(N, K, M)); e_slot [nnz, D] float32, the
@@ -3765,9 +3761,9 @@ def gmm_aggregate(h, e_slot, mu, sigma, graph, aggr="mean", y0=None):
     from .graph import LOOPS_KEEP
     if _is_dist(graph):
         raise RuntimeError("GMMConv has no node-partitioned form: run it on one GPU")
-    if aggr not in _GMM_AGGRS:
+    if aggr not in _EDGE_AGGRS:
         raise ValueError(f"gmm_aggregate: aggr={aggr!r} (mean, add or sum)")
-    aggr = _GMM_AGGRS[aggr]
+    aggr = _EDGE_AGGRS[aggr]
     if getattr(graph, "loops_mode", None) != LOOPS_KEEP:
         raise RuntimeError("gmm_aggregate: only a graph in mode LOOPS_KEEP keeps one CSR slot per input edge (got "
                            f"loops_mode={getattr(graph, 'loops_mode', None)!r})")

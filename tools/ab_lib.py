@@ -8,8 +8,10 @@ The layer cases set train() / eval() and drop the old gradients inside the timed
 gradients). The gat / gcn / sage cases did neither before the comparison was added, so their times are not those of
 A/B outputs recorded earlier.
 Usage: python tools/ab_lib.py <path to build B> [S|L] [rounds] [ops: gat,gcn,sage,spmm,gatv2,transformer,supergat,
-fagcn,...] [--a=<path to build A>]
-(--a binds another build than the in-tree one as A, e.g. B again for the A/A spread)"""
+fagcn,resgated,gine,cgconv,film,rgcn,gmm,genconv,...] [--a=<path to build A>] [--split=<slots>]
+(--a binds another build than the in-tree one as A, e.g. B again for the A/A spread; --split cuts rows longer than
+<slots> into hub-row chunks (graph.LONG_ROW_SLOTS), so that the chunk and combine kernels run on a graph whose longest
+row is below the default 1024)"""
 import os
 import sys
 
@@ -18,7 +20,7 @@ sys.path.insert(0, ROOT)
 import torch
 
 from bench import WORKLOADS, synth
-from rgb_experiment_amd import _lib, nn as RN, ops
+from rgb_experiment_amd import _lib, graph as rgraph, nn as RN, ops
 from rgb_experiment_amd.graph import get_graph
 
 
@@ -33,8 +35,11 @@ def timed(fn, reps):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if not a.startswith("--a=")]
+    argv = [a for a in sys.argv[1:] if not a.startswith("--")]
     path_a = next((a[4:] for a in sys.argv[1:] if a.startswith("--a=")), None)
+    split = next((int(a[8:]) for a in sys.argv[1:] if a.startswith("--split=")), None)
+    if split is not None:  # before any graph is built: the plan is made with the graph
+        rgraph.LONG_ROW_SLOTS = split
     path_b = argv[0]
     wl = WORKLOADS[argv[1] if len(argv) > 1 else "L"]
     rounds = int(argv[2]) if len(argv) > 2 else 4
@@ -44,20 +49,26 @@ def main():
     ei, x, _ = synth(N, E, d)
     ei, x = ei.to(dev), x.to(dev)
     gy = torch.randn_like(x)
+    if split is not None:  # how many rows of the forward and of the transposed CSR the plan cuts (0: no chunk kernel runs)
+        deg_in, deg_out = torch.bincount(ei[1], minlength=N), torch.bincount(ei[0], minlength=N)
+        print(f"--split={split}: longest row {int(deg_in.max())} in / {int(deg_out.max())} out; rows cut into chunks "
+              f"{int((deg_in > split).sum())} in / {int((deg_out > split).sum())} out", flush=True)
     lib_a = _lib.bind(path_a, strict=False) if path_a else _lib.load()
     lib_b = _lib.bind(path_b, strict=False)
     cases = {}
 
-    def add_layer(label, conv, call, aux_loss=None):
-        """An inference forward and a train forward + backward of a layer; each returns what the bit comparison
-        checks: the output, and after the backward the gradient of the input and of every parameter."""
-        h = x.clone().requires_grad_(True)
+    def add_layer(label, conv, call, aux_loss=None, inp=None):
+        """An inference forward and a train forward + backward of a layer on `inp` (x where None); each returns what
+        the bit comparison checks: the output, and after the backward the gradient of the input and of every
+        parameter."""
+        inp = x if inp is None else inp
+        h = inp.clone().requires_grad_(True)
         leaves = [h] + list(conv.parameters())
 
         def infer():
             conv.eval()
             with torch.no_grad():
-                return (call(conv, x),)
+                return (call(conv, inp),)
 
         def train():
             conv.train()
@@ -96,6 +107,30 @@ def main():
         add_layer("gcn", RN.GCNConv(d, d).to(dev), lambda conv, h: conv(h, ei))
     if "sage" in which:
         add_layer("sage", RN.SAGEConv(d, d).to(dev), lambda conv, h: conv(h, ei))
+    # the edge-message families (csrc/edge_common.h). Those with a feature row per edge run 32 channels wide: at L a
+    # 128-wide row per edge is 31 GB, and as much again for its gradient.
+    gen = torch.Generator().manual_seed(7)
+    xn = x[:, :32].contiguous()
+    if "resgated" in which:
+        add_layer(f"resgated C={d}", RN.ResGatedGraphConv(d, d).to(dev), lambda conv, h: conv(h, ei))
+    if "gine" in which:
+        ea = torch.randn(E, 4, generator=gen).to(dev)
+        add_layer("gine C=32 D=4", RN.GINEConv(torch.nn.Linear(32, 32), train_eps=True, edge_dim=4).to(dev),
+                  lambda conv, h: conv(h, ei, ea), inp=xn)
+    if "cgconv" in which:
+        ec = torch.randn(E, 4, generator=gen).to(dev)
+        add_layer("cgconv C=32 D=4", RN.CGConv(32, dim=4, aggr="mean").to(dev), lambda conv, h: conv(h, ei, ec), inp=xn)
+    if "film" in which or "rgcn" in which:
+        et = torch.randint(0, 4, (E,), generator=gen).to(dev)
+    if "film" in which:
+        add_layer(f"film R=4 C={d}", RN.FiLMConv(d, d, num_relations=4).to(dev), lambda conv, h: conv(h, ei, et))
+    if "rgcn" in which:
+        add_layer(f"rgcn R=4 B=2 C={d}", RN.RGCNConv(d, d, 4, num_bases=2).to(dev), lambda conv, h: conv(h, ei, et))
+    if "gmm" in which:
+        eu = torch.rand(E, 2, generator=gen).to(dev)
+        add_layer("gmm K=4 D=2 C=32", RN.GMMConv(d, 32, dim=2, kernel_size=4).to(dev), lambda conv, h: conv(h, ei, eu))
+    if "genconv" in which:
+        add_layer(f"genconv C={d}", RN.GENConv(d, d, learn_t=True).to(dev), lambda conv, h: conv(h, ei))
     if "spmm" in which:
         g = get_graph(ei, N, 1)
         out = torch.empty_like(x)
